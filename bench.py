@@ -14,10 +14,16 @@ q_proj/v_proj, random-init weights, inputs resident in HBM before the timed regi
 Data parallel: every rank runs the same step on its own shard of the global batch (weak scaling);
 the forward has no data-path collective.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
-  roofline     -- dominant kernel (gate|up projection GEMM with SiLU*up epilogue), timed in situ with
-                  HIP events on the launching stream during the timed steps
-  cpu_baseline -- the CPU oracle (oracle/forward.py, "port") on the host cores, bounded sample
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the driver's
+contract (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds, from un-timed
+passes after the timed steps:
+  roofline / kernels -- dominant kernel (gate|up projection GEMM with SiLU*up epilogue) and the other
+                        decoder kernels, timed in situ with HIP events on the launching stream
+  cpu_baseline       -- the CPU oracle (oracle/forward.py, "port") on the host cores, bounded sample,
+                        and the full-size parity check of the HIP path against it
+  dp_diagnostics     -- (data-parallel runs) exchange-off step, per-bucket all-reduce timings, stream use
+--dump-outputs DIR writes what the last timed step returned (loss, decoded trajectories) as
+DIR/<name>.npy in float32; inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -129,7 +135,15 @@ def parse():
                          "contract (the LoRA-trainable variant follows the same switch: fp16 tapes and device-scaled fp16 "
                          "gradients by default)")
     ap.add_argument("--tile", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the in-situ kernel "
+                         "roofline and per-kernel times, the sustained clock, the CPU baseline with its full-size parity "
+                         "check, and (data-parallel runs) dp_diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, decoded trajectories) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: no CPU-baseline leg.  Either way the weights are then drawn on the GPU instead of the "
+                         "host (different values for the same seed)")
     ap.add_argument("--cpu-batch", type=int, default=8,
                     help="samples in the CPU-baseline pass (SURVEY 8d asks for 32 or the largest that fits; 8 keeps the default "
                          "run within a few minutes -- the B=32 figure is recorded in DESIGN.md)")
@@ -167,7 +181,7 @@ def parse():
                                                       "the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument("--rccl-self-test", action="store_true",
                     help="--gpus 1 only: a one-rank RCCL process group takes Trainer's data-parallel path (real all-reduce per "
-                         "bucket, five-stream layout); adds dp_diagnostics to the line")
+                         "bucket, five-stream layout); with --full adds dp_diagnostics to the line")
     ap.add_argument("--feed", choices=["resident", "host"], default="resident",
                     help="resident (default, the driver's contract: inputs in HBM before the timed region): every step runs on one "
                          "resident batch.  host: every step collates a fresh batch on the host (data.custom_collate_fn over "
@@ -184,6 +198,16 @@ def log(msg):
     """Progress on stderr (the JSON line is the only thing on stdout)."""
     if int(os.environ.get("RANK", "0")) == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 .npy per returned array (the step's outputs are a few KB: no sampling needed)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
 
 
 def host_cores():
@@ -396,14 +420,17 @@ def main():
     log(f"building {args.preset} model on {dev}")
     with torch.device(dev):
         m = model.MultiModalTrajectoryModel.from_config(cfg)
-    # With the CPU baseline / full-size parity leg the weights are drawn ONCE on the host and copied to the GPU (torch's
-    # CPU and GPU generators give different streams for one seed); otherwise they are drawn on the GPU directly.
+    # Unless --no-cpu-baseline, the weights are drawn ONCE on the host and copied to the GPU, so that the --full run's CPU
+    # baseline / full-size parity leg sees the same values (torch's CPU and GPU generators give different streams for one
+    # seed); a plain run draws them the same way, so it times the same steps as --full.  Otherwise they are drawn on the GPU.
     W_cpu = None
     if not args.no_cpu_baseline and rank == 0 and world == 1:
         log("generating fp32 weights on the host (shared by the GPU model and the CPU oracle)")
         torch.set_num_threads(host_cores())
         W_cpu = make_weights(cfg, seed=1, backend="torch", device="cpu")
         m.load_weights(W_cpu)
+        if not args.full:
+            W_cpu = None
     else:
         W = make_weights(cfg, seed=1, backend="torch", device=dev)
         m.load_weights(W)
@@ -422,7 +449,7 @@ def main():
     # full-size parity sample (checked against the oracle in the cpu_baseline leg): eval-mode output of the freshly seeded
     # model on the cpu_baseline samples, before any optimizer step changes the weights
     parity_dec = None
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         pt = {k: v.to(dev) for k, v in parity_batch(cfg, args).items()}
         was = m.training
         m.eval()
@@ -523,17 +550,17 @@ def main():
 
         prefetch = graph is None and not args.no_prefetch
 
-        last = {"loss": loss}
+        last = {"out": (loss, decoded)}  # (loss, decoded) of the latest step
 
         def run_step():
             if graph is not None:
                 graph.replay()
-                last["loss"] = g_loss
+                last["out"] = (g_loss, g_decoded)
             else:
                 if trainer is not None or feeder is not None:  # batch i+1's Q-Former goes to a side stream and runs under step i's decoder
-                    last["loss"] = step(g["vision_emb"] if prefetch else None)[0]
+                    last["out"] = step(g["vision_emb"] if prefetch else None)
                 else:
-                    last["loss"] = step()[0]
+                    last["out"] = step()
                     if prefetch:
                         m.prefetch(g["vision_emb"])
 
@@ -555,76 +582,80 @@ def main():
         elapsed = time.perf_counter() - t_start
         log(f"host enqueue time {enqueue_s / args.steps * 1e3:.3f} ms/step")
         log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.3f} ms/step")
-        loss_timed = float(last["loss"].item())  # (read here: the un-timed passes below keep training)
+        loss_timed = float(last["out"][0].item())  # (read here: the un-timed passes below keep training)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"loss": last["out"][0], "decoded": last["out"][1]})
 
-        # in-situ kernel timing: tcavt_llama_stack_forward records HIP events on the launching stream around the five big
-        # kernels of every layer (ops.StackEvents); one pass = 16 launches of each, averaged over a few passes
-        from tcavt_amd import ops
-        timer = ops.StackEvents(cfg.llama.layers)
-        m.mllm.llama_wrapper.timer = timer
-        acc = {}
-        n_pass = max(2, min(5, args.steps))
-        for _ in range(n_pass):
-            step()
-            torch.cuda.synchronize()
-            for k, (cnt, ms) in timer.summary().items():
-                c0, t0_ = acc.get(k, (0, 0.0))
-                acc[k] = (c0 + cnt, t0_ + cnt * ms)
-        m.mllm.llama_wrapper.timer = None
-        timer.close()
-        ksum = {k: (c, t / c) for k, (c, t) in acc.items()}
-        # sustained clock / power of the same step loop (un-timed repeat, sampled from sysfs)
-        tele = CardTelemetry(local_dev)
-        tele.start()
-        for _ in range(max(20, min(args.steps, 60))):
-            run_step()
-        torch.cuda.synchronize()
-        clock = tele.stop()
-
-        # ---- data-parallel self-diagnosis (world > 1; un-timed repeats of the same steps): what the first multi-GPU run needs
-        # to check the overlap claims of DESIGN section 6 instead of arguing them -- (i) the same build's step time with the
-        # gradient exchange switched off (the N = 1 figure on this very card, all ranks running it at once), (ii) how long
-        # every bucket's all-reduce held its launching stream, (iii) busy / idle time of the MLLM stream per step, (iv) the
-        # number of HIP streams a rank uses (the five-stream budget)
-        dp_diag = None
-        if dp and trainer is not None and graph is None:
-            n_diag = max(5, min(args.steps, 20))
-
-            def timed_loop(n):
+        # --full only: un-timed passes after the timed steps (the model keeps training in them)
+        ksum, clock, dp_diag = None, None, None
+        if args.full:
+            # in-situ kernel timing: tcavt_llama_stack_forward records HIP events on the launching stream around the five big
+            # kernels of every layer (ops.StackEvents); one pass = 16 launches of each, averaged over a few passes
+            from tcavt_amd import ops
+            timer = ops.StackEvents(cfg.llama.layers)
+            m.mllm.llama_wrapper.timer = timer
+            acc = {}
+            n_pass = max(2, min(5, args.steps))
+            for _ in range(n_pass):
+                step()
                 torch.cuda.synchronize()
-                dist.barrier()
-                torch.cuda.synchronize()
-                t_ = time.perf_counter()
-                for _ in range(n):
-                    run_step()
-                torch.cuda.synchronize()
-                dist.barrier()
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t_) / n * 1e3
-
-            with trainer.local_steps():  # (re-synchronises the replicas from rank 0 on exit: they drift apart inside)
+                for k, (cnt, ms) in timer.summary().items():
+                    c0, t0_ = acc.get(k, (0, 0.0))
+                    acc[k] = (c0 + cnt, t0_ + cnt * ms)
+            m.mllm.llama_wrapper.timer = None
+            timer.close()
+            ksum = {k: (c, t / c) for k, (c, t) in acc.items()}
+            # sustained clock / power of the same step loop (un-timed repeat, sampled from sysfs)
+            tele = CardTelemetry(local_dev)
+            tele.start()
+            for _ in range(max(20, min(args.steps, 60))):
                 run_step()
-                ms_no_exchange = timed_loop(n_diag)
-            run_step()
-            trainer.enable_diagnostics(True)
-            m.pipe_trace = [] if m.pipeline_decoder else None
-            ms_diag = timed_loop(n_diag)
-            d = trainer.diagnostics()
-            trainer.enable_diagnostics(False)
-            ev, m.pipe_trace = m.pipe_trace, None
-            pipe = None
-            if ev:
-                busy = [a.elapsed_time(b_) for a, b_ in ev]
-                idle = [ev[i][1].elapsed_time(ev[i + 1][0]) for i in range(len(ev) - 1)] or [0.0]
-                pipe = {"mllm_pass_busy_ms": round(sum(busy) / len(busy), 3), "mllm_idle_between_passes_ms": round(sum(idle) / len(idle), 3),
-                        "mllm_idle_max_ms": round(max(idle), 3), "passes": len(busy)}
-            loc = torch.tensor([ms_no_exchange, ms_diag], dtype=torch.float64, device=dev)
-            dist.all_reduce(loc, op=dist.ReduceOp.MAX)
-            dp_diag = dict(d, ms_per_step_exchange_off=round(loc[0].item(), 3), ms_per_step_with_event_timing=round(loc[1].item(), 3),
-                           steps=n_diag, mllm_stream=pipe, backend=args.backend,
-                           note="rank 0's buckets and stream trace; step times are MAX over ranks between barriers; "
-                                "exchange_off = the same build and card without the gradient all-reduce (the N = 1 step)")
-            log(f"dp diagnostics: {dp_diag}")
+            torch.cuda.synchronize()
+            clock = tele.stop()
+
+            # ---- data-parallel self-diagnosis (world > 1; un-timed repeats of the same steps): what the first multi-GPU run needs
+            # to check the overlap claims of DESIGN section 6 instead of arguing them -- (i) the same build's step time with the
+            # gradient exchange switched off (the N = 1 figure on this very card, all ranks running it at once), (ii) how long
+            # every bucket's all-reduce held its launching stream, (iii) busy / idle time of the MLLM stream per step, (iv) the
+            # number of HIP streams a rank uses (the five-stream budget)
+            if dp and trainer is not None and graph is None:
+                n_diag = max(5, min(args.steps, 20))
+
+                def timed_loop(n):
+                    torch.cuda.synchronize()
+                    dist.barrier()
+                    torch.cuda.synchronize()
+                    t_ = time.perf_counter()
+                    for _ in range(n):
+                        run_step()
+                    torch.cuda.synchronize()
+                    dist.barrier()
+                    torch.cuda.synchronize()
+                    return (time.perf_counter() - t_) / n * 1e3
+
+                with trainer.local_steps():  # (re-synchronises the replicas from rank 0 on exit: they drift apart inside)
+                    run_step()
+                    ms_no_exchange = timed_loop(n_diag)
+                run_step()
+                trainer.enable_diagnostics(True)
+                m.pipe_trace = [] if m.pipeline_decoder else None
+                ms_diag = timed_loop(n_diag)
+                d = trainer.diagnostics()
+                trainer.enable_diagnostics(False)
+                ev, m.pipe_trace = m.pipe_trace, None
+                pipe = None
+                if ev:
+                    busy = [a.elapsed_time(b_) for a, b_ in ev]
+                    idle = [ev[i][1].elapsed_time(ev[i + 1][0]) for i in range(len(ev) - 1)] or [0.0]
+                    pipe = {"mllm_pass_busy_ms": round(sum(busy) / len(busy), 3), "mllm_idle_between_passes_ms": round(sum(idle) / len(idle), 3),
+                            "mllm_idle_max_ms": round(max(idle), 3), "passes": len(busy)}
+                loc = torch.tensor([ms_no_exchange, ms_diag], dtype=torch.float64, device=dev)
+                dist.all_reduce(loc, op=dist.ReduceOp.MAX)
+                dp_diag = dict(d, ms_per_step_exchange_off=round(loc[0].item(), 3), ms_per_step_with_event_timing=round(loc[1].item(), 3),
+                               steps=n_diag, mllm_stream=pipe, backend=args.backend,
+                               note="rank 0's buckets and stream trace; step times are MAX over ranks between barriers; "
+                                    "exchange_off = the same build and card without the gradient all-reduce (the N = 1 step)")
+                log(f"dp diagnostics: {dp_diag}")
 
     if trainer is not None:
         trainer.release_graph()
@@ -633,30 +664,44 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
 
-    ll = cfg.llama
-    M = B * L
-    gu_ms = ksum["gateup"][1]
-    gu_flops = 2.0 * M * (2 * ll.inter) * ll.hidden
-    gu_tflops = gu_flops / (gu_ms * 1e-3) / 1e12
-    attn_ms = ksum["attn"][1]
-    attn_bytes = B * ATTN_MB_PER_SAMPLE * 1e6 / ll.layers
-    kernels = {}
-    for name, n_, k_ in (("qkv", (ll.n_q_heads + 2 * ll.n_kv_heads) * ll.head_dim, ll.hidden),
-                         ("o", ll.hidden, ll.n_q_heads * ll.head_dim), ("gateup", 2 * ll.inter, ll.hidden),
-                         ("down", ll.hidden, ll.inter)):
-        ms = ksum[name][1]
-        kernels[name] = {"avg_us": round(ms * 1e3, 1), "tflops": round(2.0 * M * n_ * k_ / (ms * 1e-3) / 1e12, 1)}
-    kernels["attn"] = {"avg_us": round(attn_ms * 1e3, 1), "algorithmic_GBps": round(attn_bytes / (attn_ms * 1e-3) / 1e9, 1),
-                       "hbm_frac": round(attn_bytes / (attn_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    figs = {}  # --full: roofline / kernels from the in-situ timing
+    if ksum is not None:
+        ll = cfg.llama
+        M = B * L
+        gu_ms = ksum["gateup"][1]
+        gu_flops = 2.0 * M * (2 * ll.inter) * ll.hidden
+        gu_tflops = gu_flops / (gu_ms * 1e-3) / 1e12
+        attn_ms = ksum["attn"][1]
+        attn_bytes = B * ATTN_MB_PER_SAMPLE * 1e6 / ll.layers
+        kernels = {}
+        for name, n_, k_ in (("qkv", (ll.n_q_heads + 2 * ll.n_kv_heads) * ll.head_dim, ll.hidden),
+                             ("o", ll.hidden, ll.n_q_heads * ll.head_dim), ("gateup", 2 * ll.inter, ll.hidden),
+                             ("down", ll.hidden, ll.inter)):
+            ms = ksum[name][1]
+            kernels[name] = {"avg_us": round(ms * 1e3, 1), "tflops": round(2.0 * M * n_ * k_ / (ms * 1e-3) / 1e12, 1)}
+        kernels["attn"] = {"avg_us": round(attn_ms * 1e3, 1), "algorithmic_GBps": round(attn_bytes / (attn_ms * 1e-3) / 1e9, 1),
+                           "hbm_frac": round(attn_bytes / (attn_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
 
-    # HBM-side traffic of the dominant kernel: PMC counters cannot be read inside this process, they come
-    # from the committed rocprofv3 --pmc passes of the same kernel / shape (profiles/)
-    traffic, traffic_src = None, None
-    pmc_path = os.path.join(ROOT, "profiles", "r04_gateup_gemm_pmc.json")
-    if os.path.exists(pmc_path) and (M, 2 * ll.inter, ll.hidden) == (8192, 16384, 2048):
-        with open(pmc_path) as f:
-            traffic = json.load(f)["traffic_bytes_per_launch"]
-        traffic_src = "profiles/r04_gateup_gemm_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, gfx950-corrected)"
+        # HBM-side traffic of the dominant kernel: PMC counters cannot be read inside this process, they come
+        # from the committed rocprofv3 --pmc passes of the same kernel / shape (profiles/)
+        traffic, traffic_src = None, None
+        pmc_path = os.path.join(ROOT, "profiles", "r04_gateup_gemm_pmc.json")
+        if os.path.exists(pmc_path) and (M, 2 * ll.inter, ll.hidden) == (8192, 16384, 2048):
+            with open(pmc_path) as f:
+                traffic = json.load(f)["traffic_bytes_per_launch"]
+            traffic_src = "profiles/r04_gateup_gemm_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, gfx950-corrected)"
+        figs = {"roofline": {
+            "kernel": "gemm_bf16_w4_kernel<SILU> (256x256 tile, 4 waves x 128x128; gate|up projection with the post-attention RMSNorm "
+                      "fused in as a row scale, SiLU*up epilogue; M=%d N=%d K=%d)" % (M, 2 * ll.inter, ll.hidden),
+            "bound": "mfma", "achieved": round(gu_tflops, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(gu_tflops / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_unit": "bytes/launch",
+            "traffic_source": traffic_src, "algorithmic_bytes": int(2 * (M * ll.hidden + 2 * ll.inter * ll.hidden + M * ll.inter)),
+            "launches_timed": ksum["gateup"][0], "avg_launch_us": round(gu_ms * 1e3, 1),
+            # the chip holds its clock down at the power cap on real data: clock and power of the step loop (sysfs,
+            # un-timed repeat of the same steps) and the fraction against the MFMA peak at THAT clock
+            "sustained_clock": (dict(clock, frac_at_sustained_clock=round(
+                gu_tflops / (MFMA_BF16_PEAK_TFLOPS * clock["sclk_mhz"] / RATED_SCLK_MHZ), 4)) if clock else None),
+        }, "kernels": kernels}
 
     if rank == 0:
         total = world * B * args.steps
@@ -698,19 +743,7 @@ def main():
             },
             "achieved_model_tflops": round(value * gflop_per_sample(cfg, L) / 1e3, 1),
             "gflop_per_sample_forward": round(gflop_per_sample(cfg, L), 1),
-            "roofline": {
-                "kernel": "gemm_bf16_w4_kernel<SILU> (256x256 tile, 4 waves x 128x128; gate|up projection with the post-attention RMSNorm "
-                          "fused in as a row scale, SiLU*up epilogue; M=%d N=%d K=%d)" % (M, 2 * ll.inter, ll.hidden),
-                "bound": "mfma", "achieved": round(gu_tflops, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(gu_tflops / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_unit": "bytes/launch",
-                "traffic_source": traffic_src, "algorithmic_bytes": int(2 * (M * ll.hidden + 2 * ll.inter * ll.hidden + M * ll.inter)),
-                "launches_timed": ksum["gateup"][0], "avg_launch_us": round(gu_ms * 1e3, 1),
-                # the chip holds its clock down at the power cap on real data: clock and power of the step loop (sysfs,
-                # un-timed repeat of the same steps) and the fraction against the MFMA peak at THAT clock
-                "sustained_clock": (dict(clock, frac_at_sustained_clock=round(
-                    gu_tflops / (MFMA_BF16_PEAK_TFLOPS * clock["sclk_mhz"] / RATED_SCLK_MHZ), 4)) if clock else None),
-            },
-            "kernels": kernels,
+            **figs,
             "setup_s": round(setup_s, 1),
             # the synthetic batch is the same every step: in train mode the loss must fall as the optimizer fits it
             "loss_first_step": round(first_loss, 3), "loss_last_timed_step": round(loss_timed, 3),
@@ -723,7 +756,7 @@ def main():
                 log(f"WARNING: {skipped} of {applied + skipped} optimizer updates were SKIPPED (non-finite loss or gradient norm)")
         if dp_diag is not None:
             out["dp_diagnostics"] = dp_diag
-        if not args.no_cpu_baseline and world >= 1:
+        if args.full and not args.no_cpu_baseline and world >= 1:
             out["cpu_baseline"] = cpu_baseline(cfg, args, gpu_decoded=parity_dec, W=W_cpu) if args.gpus == 1 or world == 1 else None
             if out["cpu_baseline"]:
                 out["speedup_vs_cpu_port"] = round(value / out["cpu_baseline"]["value"], 1)

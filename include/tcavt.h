@@ -34,7 +34,7 @@ extern "C" {
 
 typedef void* tcavt_stream_t; /* hipStream_t */
 
-#define TCAVT_ABI_VERSION 4
+#define TCAVT_ABI_VERSION 5
 
 #define TCAVT_OK 0
 #define TCAVT_ERR_ARG 1  /* shape / alignment / null-pointer contract violated */
@@ -424,10 +424,13 @@ int tcavt_traj_metrics(const float* pred, const float* gt, const float* norm_sta
 
 /* fp32 dense layer with general element strides: A[m][k] = A[m*rsA + k*csA], W[n][k] = W[n*rsW + k*csW];
  * C[M,N] = A . W^T (+bias)(+relu)(+residual).  Lets the backward of an fp32 nn.Linear run without
- * transposes: gx = gy . W  (rsW = 1, csW = ldw)  and  gW = gy^T . x  (rsA = 1, csA = ld_gy; rsW = 1, csW = ld_x). */
+ * transposes: gx = gy . W  (rsW = 1, csW = ldw)  and  gW = gy^T . x  (rsA = 1, csA = ld_gy; rsW = 1, csW = ld_x).
+ * ws (may be NULL): ws_elems floats of scratch for split-K partial sums, added in a fixed order (up to 8 splits, as many
+ * as M*N-float slices fit); without it at most 2 splits.  Either way the result is reproducible from run to run. */
 int tcavt_gemm_f32_strided(const float* A, int64_t rsA, int64_t csA, const float* W, int64_t rsW,
                            int64_t csW, const float* bias, const float* residual, int64_t ldr, float* C,
-                           int64_t ldc, int M, int N, int K, int flags, tcavt_stream_t stream);
+                           int64_t ldc, int M, int N, int K, int flags, float* ws, int64_t ws_elems,
+                           tcavt_stream_t stream);
 
 /* ========================================================================
  * Training step of scripts/train.py (:1168-1183): backward through the trainable part (lane-polygon
@@ -445,9 +448,10 @@ int tcavt_transpose16(const void* in, int64_t ld_in, void* out, int64_t ld_out, 
 /* fp32 [rows][cols] -> bf16 [cols][rows_pad], zero padded */
 int tcavt_transpose_f32_bf16(const float* in, int64_t ld_in, void* out, int64_t ld_out, int rows,
                              int cols, int rows_pad, tcavt_stream_t stream);
-/* out[n] (+)= sum_m g[m][n]  (bias gradient); dtype of g: TCAVT_F32 or TCAVT_BF16 */
+/* out[n] (+)= sum_m g[m][n]  (bias gradient); dtype of g: TCAVT_F32 or TCAVT_BF16.  ws: >= ceil(M / 128) * N floats of
+   scratch for the per-block partial sums, which are added in a fixed order (reproducible from run to run) */
 int tcavt_colsum(const void* g, int64_t ld, int dtype, float* out, int M, int N, int accumulate,
-                 tcavt_stream_t stream);
+                 float* ws, int64_t ws_elems, tcavt_stream_t stream);
 /* g[i] = 0 where the saved post-ReLU activation y[i] <= 0 */
 int tcavt_relu_bwd(float* g, const void* y, int y_dtype, int64_t n, tcavt_stream_t stream);
 /* a[i] += b[i] */
@@ -550,9 +554,10 @@ int tcavt_lora_wgrad_a(const void* x16, const float* part, int npart, float eps,
    (pass grad_scale = 1 to tcavt_adamw afterwards).  Fixed summation order, no host synchronisation; scratch: >= 1026
    floats (scratch[1024] = the total factor applied, [1025] = the norm of the scaled gradient before clipping) */
 int tcavt_clip_grad_norm(float* g, int64_t n, float max_norm, float grad_scale, float* scratch, tcavt_stream_t stream);
-/* nn.LayerNorm backward; x is the LayerNorm input; ggamma / gbeta are ACCUMULATED (zero them first) */
+/* nn.LayerNorm backward (D <= 2048); x is the LayerNorm input; ggamma / gbeta are ACCUMULATED (zero them first).
+   ws: >= ceil(M / 16) * 2 * D floats of scratch for the per-block partial sums, added in a fixed order (reproducible) */
 int tcavt_layernorm_bwd(const float* x, const float* gamma, const float* gy, float eps, float* gx,
-                        float* ggamma, float* gbeta, int M, int D, tcavt_stream_t stream);
+                        float* ggamma, float* gbeta, int M, int D, float* ws, int64_t ws_elems, tcavt_stream_t stream);
 /* backward of tcavt_mha (fp32 operands): gq, gk, gv share leading dimension ldg; dropout_p > 0 regenerates the
    attention-weight mask of the forward call with the same (seed, site) */
 int tcavt_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
@@ -838,6 +843,9 @@ typedef struct tcavt_tstack_bwd_args {
   float *g_tmp, *g_y2, *g_y2d, *g_x1, *g_y, *g_yd, *g_att; /* [M][E] each (g_y2d / g_yd: train mode only) */
   float* g_f;                      /* [M][FF] */
   float* g_qkv;                    /* [M][3E] */
+  /* scratch of the bias / LayerNorm gradient reductions (tcavt_colsum / tcavt_layernorm_bwd ws), red_ws_elems floats */
+  float* red_ws;
+  int64_t red_ws_elems;
 } tcavt_tstack_bwd_args;
 
 int tcavt_tlayer_stack_backward(const tcavt_tstack_bwd_args* args, tcavt_stream_t stream);
@@ -887,6 +895,9 @@ typedef struct tcavt_cross_attn_bwd_args {
   void* d_s;             /* bf16 [B*nhead*To][Lp] */
   void* g_qp;            /* bf16 [nhead][B*To][H] */
   void* p_undropped;     /* fp16 [B*nhead*To][Lp]: needed when the forward ran with dropout */
+  /* scratch of the bias / LayerNorm gradient reductions (tcavt_colsum / tcavt_layernorm_bwd ws), red_ws_elems floats */
+  float* red_ws;
+  int64_t red_ws_elems;
 } tcavt_cross_attn_bwd_args;
 
 int tcavt_cross_attn_backward(const tcavt_cross_attn_bwd_args* args, tcavt_stream_t stream);
@@ -976,6 +987,9 @@ typedef struct tcavt_ltsf_bwd_args {
   void *s_gyb, *s_gyt, *s_xt, *s_wt; /* bf16 scratch of the 16-bit linear backwards: [Mo][H], [H][Mp], [H][Mp], [H][H] */
   int64_t dec_stride, enc_stride;
   int32_t pos_ld, reserved0;
+  /* scratch of the bias / LayerNorm gradient reductions (tcavt_colsum / tcavt_layernorm_bwd ws), red_ws_elems floats */
+  float* red_ws;
+  int64_t red_ws_elems;
 } tcavt_ltsf_bwd_args;
 
 int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* args, int phase, tcavt_stream_t stream);

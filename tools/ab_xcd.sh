@@ -3,7 +3,7 @@
 for gx in 8 4 2 1; do
   echo "== gx=$gx"
   TCAVT_GEMM_XCD_GX=$gx python tools/bench_gemm_cold.py 2>/dev/null | grep -E "tile=256 rotate"
-  TCAVT_GEMM_XCD_GX=$gx timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --mode forward 2>/dev/null | tail -1 > /tmp/ab_x.json
+  TCAVT_GEMM_XCD_GX=$gx timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --mode forward 2>/dev/null | tail -1 > /tmp/ab_x.json
   python - <<PY
 import json
 d = json.load(open("/tmp/ab_x.json"))

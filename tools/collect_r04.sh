@@ -12,8 +12,8 @@ O=$R/gpurun_out/r04; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 part=${1:-a}
 if [ "$part" = "a" ]; then
-  python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -2 $O/bench_default.err
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_step -o step -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/prof_step.log 2>&1; echo "rocprof rc=$?"
+  python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -2 $O/bench_default.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_step -o step -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/prof_step.log 2>&1; echo "rocprof rc=$?"
   cp $O/prof_step/step_kernel_stats.csv $O/train_step_kernel_stats.csv; rm -rf $O/prof_step
   for sh in gateup down o attn; do
     D=/tmp/pmc_r04_$sh; rm -rf $D; i=0
@@ -29,12 +29,12 @@ if [ "$part" = "a" ]; then
 fi
 for v in "forward:--mode forward" "nopipeline:--no-pipeline" "bf16:--storage bf16" "feed_host:--feed host" "rccl1:--rccl-self-test"; do
   n=${v%%:*}; f=${v#*:}
-  python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline $f > $O/bench_$n.json 2> $O/bench_$n.err; echo "$n: $(tail -1 $O/bench_$n.err)"
+  python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $f > $O/bench_$n.json 2> $O/bench_$n.err; echo "$n: $(tail -1 $O/bench_$n.err)"
 done
-python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable > $O/bench_lora.json 2> $O/bench_lora.err; tail -1 $O/bench_lora.err
-python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable --train-mllm-front > $O/bench_lora_full.json 2> $O/bench_lora_full.err; tail -1 $O/bench_lora_full.err
-python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable --storage bf16 > $O/bench_lora_bf16.json 2> $O/bench_lora_bf16.err; tail -1 $O/bench_lora_bf16.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_lora -o lora -- python3 $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --lora-trainable > $O/prof_lora.log 2>&1; echo "rocprof lora rc=$?"
+python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable > $O/bench_lora.json 2> $O/bench_lora.err; tail -1 $O/bench_lora.err
+python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable --train-mllm-front > $O/bench_lora_full.json 2> $O/bench_lora_full.err; tail -1 $O/bench_lora_full.err
+python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --lora-trainable --storage bf16 > $O/bench_lora_bf16.json 2> $O/bench_lora_bf16.err; tail -1 $O/bench_lora_bf16.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_lora -o lora -- python3 $R/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --lora-trainable > $O/prof_lora.log 2>&1; echo "rocprof lora rc=$?"
 python3 $R/tools/lora_timeline.py $O/prof_lora/lora_kernel_trace.csv > $O/lora_timeline.txt 2>&1; head -3 $O/lora_timeline.txt
 cp $O/prof_lora/lora_kernel_stats.csv $O/lora_kernel_stats.csv; rm -rf $O/prof_lora
 for bs in 8 16 32; do python3 $R/tools/bench_generate.py --batch $bs 2>/dev/null | tail -1 > $O/generate_b$bs.json; cut -c1-330 $O/generate_b$bs.json; done
@@ -50,4 +50,4 @@ python3 $R/tools/pipe_trace.py 2>/dev/null | tail -1 > $O/pipe_trace.txt; cat $O
 python3 $R/tools/bench_sampler.py > $O/bench_sampler.txt 2>&1
 python3 $R/tools/bench_eval_k.py 512 > $O/config5_eval_k.txt 2>&1; tail -3 $O/config5_eval_k.txt
 bash $R/tools/sweep_config4.sh > $O/config4_sweep.txt 2>&1; tail -4 $O/config4_sweep.txt
-cd $R && timeout -k 10 300 python3 bench.py --gpus 2 --steps 8 --warmup 2 --backend gloo --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err; echo "gloo2 rc=$?"; tail -2 $O/bench_gloo2.err
+cd $R && timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 8 --warmup 2 --backend gloo --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err; echo "gloo2 rc=$?"; tail -2 $O/bench_gloo2.err

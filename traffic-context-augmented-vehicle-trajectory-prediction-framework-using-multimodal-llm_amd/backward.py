@@ -20,6 +20,9 @@ from . import ops, streams
 from .model import XATTN_PAD
 
 
+SPLITK_WS = 8 * 127 * 64 * 64  # floats: 8 split-K slices of the largest output tcavt_gemm_f32_strided splits (< 128 tiles)
+
+
 def _rup(n, m):
     return (n + m - 1) // m * m
 
@@ -406,6 +409,11 @@ class Backward:
             setattr(a, f"g_{name}_b", flat.data_ptr() + 4 * ob)
             setattr(a, f"{name}_stride", off[prefix + "1.weight"][0] - o0 if C > 1 else 0)
         a.pos_ld = G[pl + "pos_encoding"].shape[-1]
+        R, W = max(Mo, Mt, B), max(4 * C, H, C * To, post, F * To)
+        red = b("lt.red", (max(_rup(R, 16) // 16 * 2 * C, _rup(R, 128) // 128 * W, SPLITK_WS),))
+        a.red_ws = a.xattn.red_ws = red.data_ptr()
+        a.red_ws_elems = a.xattn.red_ws_elems = red.numel()
+        keep.append(red)
         if on_poly_grad is None:
             ops.ltsf_backward(a, 3)
         elif self.poly_after_chain and torch.cuda.is_available():
@@ -572,6 +580,9 @@ class Backward:
                 bufs["p_undropped"] = self._buf("xa.Pu", (B * nh * To, Lp), torch.float16)
             for k_, t_ in bufs.items():
                 setattr(a, k_, t_.data_ptr())
+            red = self._buf("xa.red", (_rup(M, 128) // 128 * H,))
+            a.red_ws, a.red_ws_elems = red.data_ptr(), red.numel()
+            bufs["red"] = red
             ops.cross_attn_backward(a)
             del fwd, bufs
             return g_q
@@ -758,6 +769,9 @@ class Backward:
             g_qkv=b("po.g_qkv", (M, 3 * D)))
         if p > 0.0:
             put(a, g_y2d=b("po.g_y2d", (M, D)), g_yd=b("po.g_yd", (M, D)))
+        red = b("po.red", (max(_rup(M, 16) // 16 * 2 * D, _rup(M, 128) // 128 * max(ff, 3 * D), SPLITK_WS),))
+        a.red_ws, a.red_ws_elems = red.data_ptr(), red.numel()
+        keep.append(red)
         ops.tlayer_stack_backward(a)
         del keep
         return True

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libtcavt_hip.so")
 if os.environ.get("TCAVT_LIB") == "exp":  # tools/ only: the -DTCAVT_EXPERIMENTS build (python -m tcavt_amd.build --experiments)
     LIB_PATH = os.path.join(_HERE, "libtcavt_hip_exp.so")
 
-ABI_VERSION = 4  # TCAVT_ABI_VERSION of include/tcavt.h
+ABI_VERSION = 5  # TCAVT_ABI_VERSION of include/tcavt.h
 F32, BF16, F16 = 0, 1, 2
 EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_SILU_MUL, EPI_ROPE, EPI_BIAS_ROW, EPI_ACCUM = 1, 2, 4, 8, 16, 32, 64
 EPI_NORM_OUT, EPI_ROWSCALE, EPI_SILU_BWD = 128, 256, 512
@@ -114,14 +114,16 @@ class TStackBwdArgs(ctypes.Structure):
     """Mirror of ``tcavt_tstack_bwd_args`` (include/tcavt.h)."""
 
     _fields_ = [("fwd", ctypes.POINTER(TStackArgs)), ("grads", ctypes.POINTER(TLayerGrads))] + [(n, c_void_p) for n in (
-        "g_out", "g_x", "g_tmp", "g_y2", "g_y2d", "g_x1", "g_y", "g_yd", "g_att", "g_f", "g_qkv")]
+        "g_out", "g_x", "g_tmp", "g_y2", "g_y2d", "g_x1", "g_y", "g_yd", "g_att", "g_f", "g_qkv")] + [
+        ("red_ws", c_void_p), ("red_ws_elems", c_int64)]
 
 
 class CrossAttnBwdArgs(ctypes.Structure):
     """Mirror of ``tcavt_cross_attn_bwd_args`` (include/tcavt.h)."""
 
     _fields_ = [("fwd", ctypes.POINTER(CrossAttnArgs))] + [(n, c_void_p) for n in (
-        "g_att", "w_in", "gw_in", "gb_in", "g_q", "fh_tb", "fh_b", "ga_t", "g_ctx", "w_t", "x_t", "d_p", "d_s", "g_qp", "p_undropped")]
+        "g_att", "w_in", "gw_in", "gb_in", "g_q", "fh_tb", "fh_b", "ga_t", "g_ctx", "w_t", "x_t", "d_p", "d_s", "g_qp", "p_undropped")] + [
+        ("red_ws", c_void_p), ("red_ws_elems", c_int64)]
 
 
 class LtsfArgs(ctypes.Structure):
@@ -145,7 +147,7 @@ class LtsfBwdArgs(ctypes.Structure):
         "g_f2", "g_f1", "g_fn", "g_dec_t", "g_dt2", "g_cross", "g_proj", "g_d1", "g_hid", "g_d0", "g_dw", "g_db", "g_e",
         "g_e_d", "g_res1_d", "g_ff", "g_rn", "g_res1", "g_att_sa", "g_qkv", "g_xn", "g_tok", "g_ew", "g_eb", "g_xp",
         "s_gyb", "s_gyt", "s_xt", "s_wt")] + [("dec_stride", c_int64), ("enc_stride", c_int64), ("pos_ld", ctypes.c_int32),
-                                              ("reserved0", ctypes.c_int32)]
+                                              ("reserved0", ctypes.c_int32), ("red_ws", c_void_p), ("red_ws_elems", c_int64)]
 
 
 class LlamaStackArgs(ctypes.Structure):
@@ -250,10 +252,10 @@ _SIGNATURES = {
     "tcavt_traj_metrics": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                            c_void_p],
     "tcavt_gemm_f32_strided": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
-                               c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
+                               c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p],
     "tcavt_transpose16": [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p],
     "tcavt_transpose_f32_bf16": [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p],
-    "tcavt_colsum": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    "tcavt_colsum": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p],
     "tcavt_relu_bwd": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
     "tcavt_add_inplace": [c_void_p, c_void_p, c_int64, c_void_p],
     "tcavt_silu_mul_bwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
@@ -282,7 +284,8 @@ _SIGNATURES = {
     "tcavt_lora_wgrad_a": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
                            ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, c_void_p],
     "tcavt_clip_grad_norm": [c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p],
-    "tcavt_layernorm_bwd": [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "tcavt_layernorm_bwd": [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                            c_int64, c_void_p],
     "tcavt_mha_bwd": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                       c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_uint64,
                       ctypes.c_uint32, c_void_p],

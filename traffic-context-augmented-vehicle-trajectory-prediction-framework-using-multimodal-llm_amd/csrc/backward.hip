@@ -57,8 +57,12 @@ __global__ __launch_bounds__(256) void transpose_f32_bf16_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------
-// out[n] (+)= sum_m g[m][n]   (bias gradients).  One block per 64 columns.
+// out[n] (+)= sum_m g[m][n]   (bias gradients).  One block per 64 columns x 128 rows writes its partial sums to a
+// workspace row; reduce_partials_kernel adds the rows in index order.  Float atomics would make the sum depend on the
+// order in which blocks finish, and the training step would not be reproducible from run to run.
 // ---------------------------------------------------------------------------
+constexpr int kColsumRows = 128;  // rows per block of colsum_kernel
+constexpr int kLnRows = 16;       // rows per block of layernorm_bwd_kernel (4 per wave)
 template <typename T>
 __device__ __forceinline__ float ldv(const T* p);
 template <>
@@ -67,7 +71,7 @@ template <>
 __device__ __forceinline__ float ldv<bf16_t>(const bf16_t* p) { return bf16_to_f32(*p); }
 
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ g, long ld, float* __restrict__ out,
+__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ g, long ld, float* __restrict__ part_out,
                                                      int M, int N, int rows_per_block) {
   __shared__ float part[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -78,7 +82,30 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ g, lo
     for (int m = m_lo + ty; m < m_hi; m += 4) s += ldv<T>(g + (long)m * ld + n);
   part[ty][tx] = s;
   __syncthreads();
-  if (ty == 0 && n < N) atomicAdd(&out[n], part[0][tx] + part[1][tx] + part[2][tx] + part[3][tx]);
+  if (ty == 0 && n < N) part_out[(long)blockIdx.y * N + n] = part[0][tx] + part[1][tx] + part[2][tx] + part[3][tx];
+}
+
+// out[c] (+)= sum_b part[b * ld + c] over b = 0 .. nb-1, in a fixed order: 16 waves sum contiguous ranges of b, and the
+// 16 sums are added in wave order.  One block per 64 columns.
+__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ part, long ld, int nb, int ncols,
+                                                               float* __restrict__ out, int accumulate) {
+  __shared__ float red[16][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx;
+  const int per = (nb + 15) / 16, b_lo = min(nb, ty * per), b_hi = min(nb, b_lo + per);
+  float s = 0.f;
+  if (c < ncols) {
+#pragma unroll 8
+    for (int b = b_lo; b < b_hi; ++b) s += part[(long)b * ld + c];
+  }
+  red[ty][tx] = s;
+  __syncthreads();
+  if (ty == 0 && c < ncols) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) t += red[w][tx];
+    out[c] = accumulate ? out[c] + t : t;
+  }
 }
 
 // g[i] = y[i] > 0 ? g[i] : 0      (ReLU backward against the saved post-activation)
@@ -95,23 +122,24 @@ __global__ void add_inplace_kernel(float* __restrict__ a, const float* __restric
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm backward (one wave per row, D <= 1024, D % 4 == 0):
+// LayerNorm backward (one wave per row, D <= 2048, D % 4 == 0):
 //   xhat = (x - mean) * rstd;  gx = rstd * (gy*gamma - mean(gy*gamma) - xhat * mean(gy*gamma*xhat))
-//   ggamma += sum_rows gy * xhat;  gbeta += sum_rows gy      (block partials -> atomics)
-// x is the LayerNorm INPUT (residual already added).
+//   ggamma += sum_rows gy * xhat;  gbeta += sum_rows gy
+// x is the LayerNorm INPUT (residual already added).  One block per kLnRows rows, wave w takes rows w, w + 4, ...; every
+// lane sums its columns in its wave's slice of LDS, the block adds the four slices in wave order and writes the [2][D]
+// partial to its workspace row (reduce_partials_kernel adds the rows in order: no float atomics, reproducible).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ gy, float eps,
-                                                            float* __restrict__ gx, float* __restrict__ ggamma,
-                                                            float* __restrict__ gbeta, int M, int D) {
-  extern __shared__ float sh[];  // [2][D] partial sums of this block
-  float* sg = sh;
-  float* sb = sh + D;
-  for (int i = threadIdx.x; i < 2 * D; i += blockDim.x) sh[i] = 0.f;
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row < M) {
+                                                            float* __restrict__ gx, float* __restrict__ part, int M,
+                                                            int D) {
+  extern __shared__ float sh[];  // [4 waves][2][D] partial sums, each column owned by one lane of its wave
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float* sg = sh + (long)w * 2 * D;
+  float* sb = sg + D;
+  for (int c = lane; c < D; c += 64) sg[c] = sb[c] = 0.f;
+  const int r_hi = min(M, (blockIdx.x + 1) * kLnRows);
+  for (int row = blockIdx.x * kLnRows + w; row < r_hi; row += 4) {
     const float* xr = x + (long)row * D;
     const float* gr = gy + (long)row * D;
     float s = 0.f;
@@ -131,15 +159,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     for (int c = lane; c < D; c += 64) {
       const float xh = (xr[c] - mean) * rstd;
       gx[(long)row * D + c] = rstd * (gr[c] * gamma[c] - a - xh * b);
-      atomicAdd(&sg[c], gr[c] * xh);
-      atomicAdd(&sb[c], gr[c]);
+      sg[c] += gr[c] * xh;
+      sb[c] += gr[c];
     }
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < D; c += blockDim.x) {
-    atomicAdd(&ggamma[c], sg[c]);
-    atomicAdd(&gbeta[c], sb[c]);
-  }
+  for (int c = threadIdx.x; c < 2 * D; c += blockDim.x)
+    part[(long)blockIdx.x * 2 * D + c] = sh[c] + sh[2 * D + c] + sh[4 * D + c] + sh[6 * D + c];
 }
 
 // ---------------------------------------------------------------------------
@@ -644,28 +670,25 @@ extern "C" int tcavt_transpose_f32_bf16(const float* in, int64_t ld_in, void* ou
 }
 
 extern "C" int tcavt_colsum(const void* g, int64_t ld, int dtype, float* out, int M, int N, int accumulate,
-                            tcavt_stream_t stream) {
+                            float* ws, int64_t ws_elems, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(g && out && M > 0 && N > 0 && ld >= N, "colsum: bad args");
-  if (!accumulate) {
-    hipError_t e = hipMemsetAsync(out, 0, (size_t)N * sizeof(float), S_(stream));
-    if (e != hipSuccess) {
-      set_error("colsum: hipMemsetAsync failed: %s", hipGetErrorString(e));
-      return TCAVT_ERR_HIP;
-    }
-  }
-  const int rpb = 128;  // rows per block: partial sums meet in `out` through float atomics
-  dim3 grid((N + 63) / 64, (M + rpb - 1) / rpb);
+  const int nb = (M + kColsumRows - 1) / kColsumRows;
+  TCAVT_CHECK_ARG(ws && ws_elems >= (int64_t)nb * N, "colsum: workspace of ceil(M / 128) * N floats required");
+  dim3 grid((N + 63) / 64, nb);
   if (dtype == TCAVT_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, S_(stream), static_cast<const float*>(g), (long)ld, out,
-                       M, N, rpb);
+    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, S_(stream), static_cast<const float*>(g), (long)ld, ws,
+                       M, N, kColsumRows);
   else if (dtype == TCAVT_BF16)
     hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, S_(stream), static_cast<const bf16_t*>(g), (long)ld,
-                       out, M, N, rpb);
+                       ws, M, N, kColsumRows);
   else {
     set_error("colsum: dtype must be f32 or bf16");
     return TCAVT_ERR_ARG;
   }
   TCAVT_CHECK_LAUNCH("colsum");
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((N + 63) / 64), dim3(1024), 0, S_(stream), ws, (long)N, nb, N, out,
+                     accumulate);
+  TCAVT_CHECK_LAUNCH("colsum reduce");
   return TCAVT_OK;
 }
 
@@ -688,11 +711,18 @@ extern "C" int tcavt_add_inplace(float* a, const float* b, int64_t n, tcavt_stre
 }
 
 extern "C" int tcavt_layernorm_bwd(const float* x, const float* gamma, const float* gy, float eps, float* gx,
-                                   float* ggamma, float* gbeta, int M, int D, tcavt_stream_t stream) {
-  TCAVT_CHECK_ARG(x && gamma && gy && gx && ggamma && gbeta && M > 0 && D > 0 && D <= 4096, "layernorm_bwd: bad args");
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 2 * D * sizeof(float), S_(stream), x, gamma,
-                     gy, eps, gx, ggamma, gbeta, M, D);
+                                   float* ggamma, float* gbeta, int M, int D, float* ws, int64_t ws_elems,
+                                   tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(x && gamma && gy && gx && ggamma && gbeta && M > 0 && D > 0 && D <= 2048, "layernorm_bwd: bad args");
+  const int nb = (M + kLnRows - 1) / kLnRows;
+  TCAVT_CHECK_ARG(ws && ws_elems >= (int64_t)nb * 2 * D, "layernorm_bwd: workspace of ceil(M / 16) * 2 * D floats required");
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 8 * D * sizeof(float), S_(stream), x, gamma, gy, eps, gx,
+                     ws, M, D);
   TCAVT_CHECK_LAUNCH("layernorm_bwd");
+  const dim3 rgrid((D + 63) / 64);
+  hipLaunchKernelGGL(reduce_partials_kernel, rgrid, dim3(1024), 0, S_(stream), ws, (long)(2 * D), nb, D, ggamma, 1);
+  hipLaunchKernelGGL(reduce_partials_kernel, rgrid, dim3(1024), 0, S_(stream), ws + D, (long)(2 * D), nb, D, gbeta, 1);
+  TCAVT_CHECK_LAUNCH("layernorm_bwd reduce");
   return TCAVT_OK;
 }
 

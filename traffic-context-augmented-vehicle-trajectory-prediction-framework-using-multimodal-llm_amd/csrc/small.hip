@@ -38,9 +38,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
                                                        const float* __restrict__ bias,
                                                        const float* __restrict__ res, long ldr,
                                                        float* __restrict__ C, long ldc, int M, int N,
-                                                       int K, int flags, int k_chunk, DropoutP drop) {
-  // split-K: blockIdx.z owns k in [kb, ke); partial sums meet in C (zeroed by the launcher) through float
-  // atomics, split 0 adds bias / residual.  Used when the output has too few tiles to fill the chip.
+                                                       int K, int flags, int k_chunk, DropoutP drop,
+                                                       float* __restrict__ part) {
+  // split-K: blockIdx.z owns k in [kb, ke).  With `part`, every split writes its raw partial sums to its slice
+  // part[z][M][N] and splitk_reduce_f32_kernel adds the slices in order (reproducible); without, partial sums meet in C
+  // (zeroed by the launcher) through float atomics, split 0 adds bias / residual (reproducible for 2 splits only).
+  // Used when the output has too few tiles to fill the chip.
   const int kb = blockIdx.z * k_chunk, ke = min(K, kb + k_chunk);
   __shared__ float As[64][17];
   __shared__ float Ws[64][17];
@@ -96,6 +99,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
         if (m >= M) continue;
         float v = acc[i][j][r];
         if (gridDim.z > 1) {
+          if (part) {
+            part[((long)blockIdx.z * M + m) * N + n] = v;
+            continue;
+          }
           if (blockIdx.z == 0) {
             if (flags & TCAVT_EPI_BIAS) v += bias[n];
             if (flags & TCAVT_EPI_RESIDUAL) v += res[(long)m * ldr + n];
@@ -287,36 +294,65 @@ __global__ __launch_bounds__(1024) void traj_metrics_kernel(const float* __restr
 
 using namespace tcavt;
 
+// C = part[0] + part[1] + ... (slice order) followed by the unsplit kernel's epilogue (ACCUM, BIAS, RESIDUAL)
+__global__ __launch_bounds__(256) void splitk_reduce_f32_kernel(const float* __restrict__ part, int S,
+                                                                const float* __restrict__ bias,
+                                                                const float* __restrict__ res, long ldr, float* C,
+                                                                long ldc, int M, int N, int flags) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)M * N) return;
+  const int m = (int)(i / N), n = (int)(i % N);
+  float v = part[i];
+  for (int s = 1; s < S; ++s) v += part[(long)s * M * N + i];
+  if (flags & TCAVT_EPI_ACCUM) v += C[(long)m * ldc + n];
+  if (flags & TCAVT_EPI_BIAS) v += bias[n];
+  if (flags & TCAVT_EPI_RESIDUAL) v += res[(long)m * ldr + n];
+  C[(long)m * ldc + n] = v;
+}
+
 // Launch with split-K when the 64x64 output tiles cannot fill the chip and K is long (lane-polygon FFN:
 // K = 2048 or a contraction over 2048 tokens with 32 output tiles).  Not with ReLU (needs the full sum),
 // not when C aliases the residual (split 0 would read what other splits already added to).
-// max_splits = 2 keeps the result run-to-run reproducible (0 + a + b == 0 + b + a in IEEE arithmetic; three or
-// more addends are order dependent): the forward entry point uses that, because a 1-ulp difference in the
-// lane-polygon embedding is amplified to ~1e-4 by the bf16 decoder downstream; the backward entry point
-// (gradients, tolerance-checked) uses up to 8.
+// Every form is run-to-run reproducible, so that a training step computes the same gradients every run (a 1-ulp
+// difference in the lane-polygon embedding is amplified to ~1e-4 by the bf16 decoder downstream, and AdamW carries any
+// difference on): with a workspace `ws` the splits' partial sums are added in slice order by splitk_reduce_f32_kernel (up
+// to max_splits, as many as ws holds; ACCUM and a residual aliasing C are fine); without one, at most 2 splits meet in
+// the zeroed C through atomics (0 + a + b == 0 + b + a in IEEE arithmetic; three or more addends, or a nonzero C under
+// ACCUM, would be order dependent).
 static int launch_gemm_f32(int max_splits, const float* A, long rsA, long csA, const float* W, long rsW, long csW, const float* bias,
                            const float* residual, long ldr, float* C, long ldc, int M, int N, int K, int flags,
-                           DropoutP drop, hipStream_t stream, const char* what) {
+                           DropoutP drop, float* ws, int64_t ws_elems, hipStream_t stream, const char* what) {
   const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
   int splits = 1;
-  if (tiles < 128 && K >= 512 && !(flags & TCAVT_EPI_RELU) && residual != C && ldc == N && drop.p == 0.f) {
-    splits = K / 256;
-    if (splits > max_splits) splits = max_splits;
+  if (tiles < 128 && K >= 512 && !(flags & TCAVT_EPI_RELU) && drop.p == 0.f) {
+    int cap = 0;
+    if (ws)
+      cap = (int)std::min<int64_t>(max_splits, ws_elems / ((int64_t)M * N));
+    else if (!(flags & TCAVT_EPI_ACCUM) && residual != C && ldc == N)
+      cap = std::min(max_splits, 2);
+    splits = std::min(K / 256, cap);
     while (splits > 1 && tiles * splits > 512) splits >>= 1;
+    if (splits < 1) splits = 1;
   }
   int k_chunk = K;
+  const bool partials = splits > 1 && ws;
   if (splits > 1) {
     k_chunk = (((K + splits - 1) / splits) + 15) / 16 * 16;
     splits = (K + k_chunk - 1) / k_chunk;
-    hipError_t e = (flags & TCAVT_EPI_ACCUM) ? hipSuccess : hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), stream);
-    if (e != hipSuccess) {
-      set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e));
-      return TCAVT_ERR_HIP;
+    if (!partials) {
+      hipError_t e = hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), stream);
+      if (e != hipSuccess) {
+        set_error("%s: hipMemsetAsync failed: %s", what, hipGetErrorString(e));
+        return TCAVT_ERR_HIP;
+      }
     }
   }
   dim3 grid((N + 63) / 64, (M + 63) / 64, splits), block(256);
   hipLaunchKernelGGL(gemm_f32_kernel, grid, block, 0, stream, A, rsA, csA, W, rsW, csW, bias, residual, ldr, C, ldc, M,
-                     N, K, flags, k_chunk, drop);
+                     N, K, flags, k_chunk, drop, splits > 1 && partials ? ws : nullptr);
+  if (splits > 1 && partials)
+    hipLaunchKernelGGL(splitk_reduce_f32_kernel, dim3((unsigned)(((int64_t)M * N + 255) / 256)), dim3(256), 0, stream, ws,
+                       splits, bias, residual, ldr, C, ldc, M, N, flags);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s: launch failed: %s", what, hipGetErrorString(e));
@@ -335,19 +371,22 @@ extern "C" int tcavt_gemm_f32(const float* A, int64_t lda, const float* W, int64
   TCAVT_CHECK_ARG(!(flags & TCAVT_EPI_RESIDUAL) || residual, "gemm_f32: RESIDUAL without residual");
   TCAVT_CHECK_ARG(!(flags & ~(TCAVT_EPI_BIAS | TCAVT_EPI_RELU | TCAVT_EPI_RESIDUAL)), "gemm_f32: unsupported flag");
   return launch_gemm_f32(2, A, (long)lda, 1L, W, (long)ldw, 1L, bias, residual, (long)ldr, C, (long)ldc, M, N, K, flags,
-                         make_dropout(dropout_p, dropout_seed, dropout_site), static_cast<hipStream_t>(stream), "gemm_f32");
+                         make_dropout(dropout_p, dropout_seed, dropout_site), nullptr, 0, static_cast<hipStream_t>(stream),
+                         "gemm_f32");
 }
 
 extern "C" int tcavt_gemm_f32_strided(const float* A, int64_t rsA, int64_t csA, const float* W, int64_t rsW,
                                       int64_t csW, const float* bias, const float* residual, int64_t ldr, float* C,
-                                      int64_t ldc, int M, int N, int K, int flags, tcavt_stream_t stream) {
+                                      int64_t ldc, int M, int N, int K, int flags, float* ws, int64_t ws_elems,
+                                      tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0, "gemm_f32_strided: null pointer or bad shape");
   TCAVT_CHECK_ARG(!(flags & TCAVT_EPI_BIAS) || bias, "gemm_f32_strided: BIAS without bias");
   TCAVT_CHECK_ARG(!(flags & TCAVT_EPI_RESIDUAL) || residual, "gemm_f32_strided: RESIDUAL without residual");
   TCAVT_CHECK_ARG(!(flags & ~(TCAVT_EPI_BIAS | TCAVT_EPI_RELU | TCAVT_EPI_RESIDUAL | TCAVT_EPI_ACCUM)), "gemm_f32_strided: unsupported flag");
   TCAVT_CHECK_ARG(!((flags & TCAVT_EPI_ACCUM) && (flags & TCAVT_EPI_RELU)), "gemm_f32_strided: ACCUM excludes RELU");
   return launch_gemm_f32(8, A, (long)rsA, (long)csA, W, (long)rsW, (long)csW, bias, residual, (long)ldr, C, (long)ldc, M,
-                         N, K, flags, make_dropout(0.f, 0, 0), static_cast<hipStream_t>(stream), "gemm_f32_strided");
+                         N, K, flags, make_dropout(0.f, 0, 0), ws, ws_elems, static_cast<hipStream_t>(stream),
+                         "gemm_f32_strided");
 }
 
 extern "C" int tcavt_poly_embed(const float* polygon, const float* w_in, const float* b_in,

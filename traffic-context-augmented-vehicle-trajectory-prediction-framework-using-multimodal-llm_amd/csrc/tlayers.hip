@@ -124,9 +124,9 @@ extern "C" int tcavt_tlayer_stack_backward(const tcavt_tstack_bwd_args* a, tcavt
   const float p = f.dropout_p;
   const float scale = (float)(1.0 / sqrt((double)dh));
   auto lin32 = [&](const float* x, const float* W, const float* gy, float* gW, float* gb, float* gx, int Mr, int N, int K) -> int {
-    TCAVT_TRY(tcavt_gemm_f32_strided(gy, 1, N, x, 1, K, nullptr, nullptr, 0, gW, K, N, K, Mr, TCAVT_EPI_ACCUM, stream));
-    TCAVT_TRY(tcavt_colsum(gy, N, TCAVT_F32, gb, Mr, N, 1, stream));
-    return tcavt_gemm_f32_strided(gy, N, 1, W, 1, K, nullptr, nullptr, 0, gx, K, Mr, K, N, 0, stream);
+    TCAVT_TRY(tcavt_gemm_f32_strided(gy, 1, N, x, 1, K, nullptr, nullptr, 0, gW, K, N, K, Mr, TCAVT_EPI_ACCUM, a->red_ws, a->red_ws_elems, stream));
+    TCAVT_TRY(tcavt_colsum(gy, N, TCAVT_F32, gb, Mr, N, 1, a->red_ws, a->red_ws_elems, stream));
+    return tcavt_gemm_f32_strided(gy, N, 1, W, 1, K, nullptr, nullptr, 0, gx, K, Mr, K, N, 0, a->red_ws, a->red_ws_elems, stream);
   };
   const float* g_in = a->g_out;
   for (int li = f.n_layers - 1; li >= 0; --li) {
@@ -144,7 +144,7 @@ extern "C" int tcavt_tlayer_stack_backward(const tcavt_tstack_bwd_args* a, tcavt
       return tcavt_dropout(gi, go, n, TCAVT_F32, p, f.dropout_seed, site, nullptr, stream);
     };
     // feed-forward block
-    TCAVT_TRY(tcavt_layernorm_bwd(l.y2, l.n2_w, g_in, 1e-5f, a->g_y2, g.g_n2_w, g.g_n2_b, M, E, stream));
+    TCAVT_TRY(tcavt_layernorm_bwd(l.y2, l.n2_w, g_in, 1e-5f, a->g_y2, g.g_n2_w, g.g_n2_b, M, E, a->red_ws, a->red_ws_elems, stream));
     const float* g_y2d = a->g_y2;
     if (p > 0.f) {
       TCAVT_TRY(drop(a->g_y2, a->g_y2d, (int64_t)M * E, s + 3));
@@ -157,7 +157,7 @@ extern "C" int tcavt_tlayer_stack_backward(const tcavt_tstack_bwd_args* a, tcavt
     TCAVT_TRY(lin32(l.x1, static_cast<const float*>(l.w1), a->g_f, g.g_w1, g.g_b1, a->g_x1, M, FF, E));
     TCAVT_TRY(tcavt_add_inplace(a->g_x1, a->g_y2, (int64_t)M * E, stream));
     // self-attention block
-    TCAVT_TRY(tcavt_layernorm_bwd(l.y, l.n1_w, a->g_x1, 1e-5f, a->g_y, g.g_n1_w, g.g_n1_b, M, E, stream));
+    TCAVT_TRY(tcavt_layernorm_bwd(l.y, l.n1_w, a->g_x1, 1e-5f, a->g_y, g.g_n1_w, g.g_n1_b, M, E, a->red_ws, a->red_ws_elems, stream));
     const float* g_yd = a->g_y;
     if (p > 0.f) {
       TCAVT_TRY(drop(a->g_y, a->g_yd, (int64_t)M * E, s + 1));
@@ -352,7 +352,7 @@ extern "C" int tcavt_cross_attn_backward(const tcavt_cross_attn_bwd_args* a, tca
   TCAVT_TRY(tcavt_transpose16(f.fh, H, a->fh_tb, (int64_t)B * Lp, L, H, Lp, B, (int64_t)L * H, Lp, 1, stream));
   TCAVT_TRY(tcavt_transpose16(a->fh_tb, (int64_t)B * Lp, a->fh_b, H, H, B * Lp, H, 1, 0, 0, 0, stream));
   // ---- value side
-  TCAVT_TRY(tcavt_colsum(a->g_att, H, BF, a->gb_in + 2 * H, M, H, 1, stream));
+  TCAVT_TRY(tcavt_colsum(a->g_att, H, BF, a->gb_in + 2 * H, M, H, 1, a->red_ws, a->red_ws_elems, stream));
   TCAVT_TRY(tcavt_transpose16(a->g_att, H, a->ga_t, Mp, M, H, Mp, 1, 0, 0, 0, stream));
   for (int h = 0; h < nh; ++h) {
     const float* Wv_h = a->w_in + (size_t)(2 * H + h * dh) * H;
@@ -434,9 +434,9 @@ extern "C" int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* a, int phase, tcav
   const int BF = TCAVT_BF16;
   // fp32 nn.Linear backward: x [M][K], W [N][K], gy [M][N]
   auto lin32 = [&](const float* x, const float* W, const float* gy, float* gW, float* gb, float* gx, int M, int N, int K) -> int {
-    TCAVT_TRY(tcavt_gemm_f32_strided(gy, 1, N, x, 1, K, nullptr, nullptr, 0, gW, K, N, K, M, TCAVT_EPI_ACCUM, stream));
-    TCAVT_TRY(tcavt_colsum(gy, N, TCAVT_F32, gb, M, N, 1, stream));
-    if (gx) TCAVT_TRY(tcavt_gemm_f32_strided(gy, N, 1, W, 1, K, nullptr, nullptr, 0, gx, K, M, K, N, 0, stream));
+    TCAVT_TRY(tcavt_gemm_f32_strided(gy, 1, N, x, 1, K, nullptr, nullptr, 0, gW, K, N, K, M, TCAVT_EPI_ACCUM, a->red_ws, a->red_ws_elems, stream));
+    TCAVT_TRY(tcavt_colsum(gy, N, TCAVT_F32, gb, M, N, 1, a->red_ws, a->red_ws_elems, stream));
+    if (gx) TCAVT_TRY(tcavt_gemm_f32_strided(gy, N, 1, W, 1, K, nullptr, nullptr, 0, gx, K, M, K, N, 0, a->red_ws, a->red_ws_elems, stream));
     return TCAVT_OK;
   };
   // 16-bit projection backward over the Mo decoder-token rows: x16 fp16 [Mo][K] (forward activation), W fp32 [N][K],
@@ -454,7 +454,7 @@ extern "C" int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* a, int phase, tcav
     g.A = a->s_gyt; g.lda = Mp; g.W = a->s_xt; g.ldw = Mp; g.C = gW; g.ldc = K; g.M = N; g.N = K; g.K = Mp;
     g.out_dtype = TCAVT_F32; g.in_dtype = BF;
     TCAVT_TRY(tcavt_gemm_bf16(&g, stream));
-    TCAVT_TRY(tcavt_colsum(gy, N, gy_dtype, gb, Mo, N, 1, stream));
+    TCAVT_TRY(tcavt_colsum(gy, N, gy_dtype, gb, Mo, N, 1, a->red_ws, a->red_ws_elems, stream));
     TCAVT_TRY(tcavt_transpose_f32_bf16(W, K, a->s_wt, N, N, K, N, stream));
     tcavt_gemm_args d = {};
     d.A = gyb; d.lda = N; d.W = a->s_wt; d.ldw = N; d.C = gx; d.ldc = K; d.M = Mo; d.N = K; d.K = N;
@@ -483,7 +483,7 @@ extern "C" int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* a, int phase, tcav
     TCAVT_TRY(lin32(f.f1, f.fl3_w, a->g_f2, a->g_fl3_w, a->g_fl3_b, a->g_f1, Mo, C, C));
     TCAVT_TRY(tcavt_relu_bwd(a->g_f1, f.f1, TCAVT_F32, (int64_t)Mo * C, stream));
     TCAVT_TRY(lin32(f.fn, f.fl1_w, a->g_f1, a->g_fl1_w, a->g_fl1_b, a->g_fn, Mo, C, C));
-    TCAVT_TRY(tcavt_layernorm_bwd(f.fused, f.fl_n_w, a->g_fn, 1e-5f, a->g_dec_t, a->g_fl_n_w, a->g_fl_n_b, Mo, C, stream));
+    TCAVT_TRY(tcavt_layernorm_bwd(f.fused, f.fl_n_w, a->g_fn, 1e-5f, a->g_dec_t, a->g_fl_n_w, a->g_fl_n_b, Mo, C, a->red_ws, a->red_ws_elems, stream));
     // fused = cross W_un^T + b_un + dec_t;  cross = att W_co^T + b_co
     TCAVT_TRY(lin16(f.cross, a->w_un, a->g_dec_t, TCAVT_F32, a->g_un_w, a->g_un_b, a->g_cross, BF, C, H));
     TCAVT_TRY(lin16(f.xattn.att, a->w_co, a->g_cross, BF, a->g_co_w, a->g_co_b, const_cast<void*>(a->xattn.g_att), BF, H, H));
@@ -535,7 +535,7 @@ extern "C" int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* a, int phase, tcav
     TCAVT_TRY(tcavt_relu_bwd(a->g_ff, f.sa_f, TCAVT_F32, (int64_t)Mt * 4 * C, stream));
     TCAVT_TRY(lin32(f.sa_rn, f.sa_f0_w, a->g_ff, a->g_sa_f0_w, a->g_sa_f0_b, a->g_rn, Mt, 4 * C, C));
     TCAVT_TRY(tcavt_add_inplace(a->g_rn, a->g_e, (int64_t)Mt * C, stream));
-    TCAVT_TRY(tcavt_layernorm_bwd(f.sa_res1, f.sa_n2_w, a->g_rn, 1e-5f, a->g_res1, a->g_sa_n2_w, a->g_sa_n2_b, Mt, C, stream));
+    TCAVT_TRY(tcavt_layernorm_bwd(f.sa_res1, f.sa_n2_w, a->g_rn, 1e-5f, a->g_res1, a->g_sa_n2_w, a->g_sa_n2_b, Mt, C, a->red_ws, a->red_ws_elems, stream));
     const float* g_res1_d = a->g_res1;
     if (p > 0.f) {
       TCAVT_TRY(drop(a->g_res1, a->g_res1_d, (int64_t)Mt * C, 1));
@@ -548,7 +548,7 @@ extern "C" int tcavt_ltsf_backward(const tcavt_ltsf_bwd_args* a, int phase, tcav
                             p > 0.f ? s0 : 0u, stream));
     TCAVT_TRY(lin32(f.sa_xn, f.sa_in_w, a->g_qkv, a->g_sa_in_w, a->g_sa_in_b, a->g_xn, Mt, 3 * C, C));
     TCAVT_TRY(tcavt_add_inplace(a->g_xn, a->g_res1, (int64_t)Mt * C, stream));
-    TCAVT_TRY(tcavt_layernorm_bwd(f.tok, f.sa_n1_w, a->g_xn, 1e-5f, a->g_tok, a->g_sa_n1_w, a->g_sa_n1_b, Mt, C, stream));
+    TCAVT_TRY(tcavt_layernorm_bwd(f.tok, f.sa_n1_w, a->g_xn, 1e-5f, a->g_tok, a->g_sa_n1_w, a->g_sa_n1_b, Mt, C, a->red_ws, a->red_ws_elems, stream));
     // front: tok = NLinear_enc(conv(x)) + pos
     TCAVT_TRY(tcavt_nlinear_bwd(f.xp_tok, f.enc_w, a->g_tok, (int64_t)T * C, 1, C, a->g_ew, a->g_eb, a->g_xp, B, C, T, T, stream));
     TCAVT_TRY(copy_rows(a->g_ew, (long)T * T, a->g_enc_w, a->enc_stride, C, T * T, stream));

@@ -494,9 +494,13 @@ def gemm_f32_strided(a, rsA, csA, w, rsW, csW, out, M, N, K, bias=None, relu=Fal
         raise capi.TcavtError("gemm_f32_strided.out: buffer too small")
     flags = (EPI_BIAS if bias is not None else 0) | (EPI_RELU if relu else 0) | (
         EPI_RESIDUAL if residual is not None else 0) | (capi.EPI_ACCUM if accumulate else 0)
+    ws = None  # split-K partial sums (added in a fixed order), when the launcher may split: few output tiles, long K
+    if -(-M // 64) * -(-N // 64) < 128 and K >= 512 and not relu:
+        ws = torch.empty(min(8, K // 256) * M * N, dtype=torch.float32, device=out.device)
     check(lib().tcavt_gemm_f32_strided(ptr(a), rsA, csA, ptr(w), rsW, csW, ptr(bias), ptr(residual),
                                        residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0), M, N,
-                                       K, flags, stream_ptr()), "tcavt_gemm_f32_strided")
+                                       K, flags, ptr(ws), ws.numel() if ws is not None else 0, stream_ptr()),
+          "tcavt_gemm_f32_strided")
     return out
 
 
@@ -530,8 +534,9 @@ def colsum(g, out, M, N, accumulate=False):
     _need(out, N, "colsum.out")
     if _avail(g) < (M - 1) * g.stride(0) + N:
         raise capi.TcavtError("colsum.g: buffer too small")
-    check(lib().tcavt_colsum(ptr(g), g.stride(0), _DT[g.dtype], ptr(out), M, N, int(accumulate), stream_ptr()),
-          "tcavt_colsum")
+    ws = torch.empty(-(-M // 128) * N, dtype=torch.float32, device=g.device)  # per-block partial sums (fixed-order reduce)
+    check(lib().tcavt_colsum(ptr(g), g.stride(0), _DT[g.dtype], ptr(out), M, N, int(accumulate), ptr(ws), ws.numel(),
+                             stream_ptr()), "tcavt_colsum")
 
 
 def relu_bwd(g, y):
@@ -737,8 +742,9 @@ def layernorm_bwd(x, gamma, gy, gx, ggamma, gbeta, eps=1e-5):
     for t, n, nm in ((gamma, D, "gamma"), (gy, M * D, "gy"), (gx, M * D, "gx"), (ggamma, D, "ggamma"), (gbeta, D, "gbeta")):
         _req(t, torch.float32, "layernorm_bwd." + nm)
         _need(t, n, "layernorm_bwd." + nm)
+    ws = torch.empty(-(-M // 16) * 2 * D, dtype=torch.float32, device=x.device)  # per-block partial sums (fixed-order reduce)
     check(lib().tcavt_layernorm_bwd(ptr(x), ptr(gamma), ptr(gy), eps, ptr(gx), ptr(ggamma), ptr(gbeta), M, D,
-                                    stream_ptr()), "tcavt_layernorm_bwd")
+                                    ptr(ws), ws.numel(), stream_ptr()), "tcavt_layernorm_bwd")
 
 
 def mha_bwd(q, k, v, go, gq, gk, gv, B, Lq, Lk, nh, dh, scale, key_len=None, ldq=None, ldk=None, ldv=None, ldo=None,
