@@ -363,8 +363,9 @@ def test_softmax_rows(gpu):
 
 @pytest.mark.parametrize("M,N,K", [(2048, 64, 2048), (64, 2048, 2048), (40, 70, 1000)])
 def test_gemm_f32_split_k_and_strided(gpu, M, N, K):
-    """Few output tiles + long K takes the split-K path (float atomics); also the transposed-operand form
-    gW = gy^T x used by the backward."""
+    """Few output tiles + long K takes the split-K path (tcavt_gemm_f32: at most 2 splits meeting in the zeroed C;
+    tcavt_gemm_f32_strided: partial sums in a workspace, added in slice order); also the transposed-operand form
+    gW = gy^T x used by the backward.  tests/test_backward_kernels_gpu.py covers the split forms in detail."""
     from tcavt_amd import ops
 
     dev = gpu["device"]

@@ -122,7 +122,7 @@ __global__ void add_inplace_kernel(float* __restrict__ a, const float* __restric
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm backward (one wave per row, D <= 2048, D % 4 == 0):
+// LayerNorm backward (one wave per row, any D <= 2048: scalar loads, so no alignment or multiple-of-4 requirement):
 //   xhat = (x - mean) * rstd;  gx = rstd * (gy*gamma - mean(gy*gamma) - xhat * mean(gy*gamma*xhat))
 //   ggamma += sum_rows gy * xhat;  gbeta += sum_rows gy
 // x is the LayerNorm INPUT (residual already added).  One block per kLnRows rows, wave w takes rows w, w + 4, ...; every
