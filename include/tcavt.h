@@ -572,6 +572,12 @@ int tcavt_softmax_bwd_rows(const void* P_f16, int64_t ldp, const float* dP, int6
 /* d loss / d decoded for loss = MSE_x + MSE_y in pixel space (train.py:945-961) */
 int tcavt_mse_grad(const float* pred, const float* gt, const float* norm_stat, float* g, int B, int To,
                    tcavt_stream_t stream);
+/* seeded form (autograd): g = g_loss[0] * (d loss / d decoded) + g_pred.  g_loss: device fp32 [1], read on the device
+   (no host synchronisation), or NULL; g_pred: fp32 [B][2][To] or NULL; a NULL term is absent, both NULL is an argument
+   error (nothing launched).  pred, gt, norm_stat may be NULL when g_loss is.  g_loss = 1, g_pred = NULL: the bits of
+   tcavt_mse_grad */
+int tcavt_mse_grad_seeded(const float* pred, const float* gt, const float* norm_stat, const float* g_loss,
+                          const float* g_pred, float* g, int B, int To, tcavt_stream_t stream);
 /* backward of tcavt_out_head: gf [B][To][C], gw [F][C], gb [F] */
 int tcavt_out_head_bwd(const float* g, const float* fused, const float* w, float* gf, float* gw, float* gb,
                        int B, int To, int C, int F, tcavt_stream_t stream);

@@ -32,7 +32,9 @@ class GradBook:
     parameter vector), ordered by the time the gradient becomes ready in the backward so that
     contiguous buckets can be all-reduced while the rest of the backward is still running."""
 
-    def __init__(self, named_params, device):
+    def __init__(self, named_params, device, bind=True):
+        """bind=False: gradients only -- the parameters keep their own storage (autograd.py hands the views to
+        AccumulateGrad; the user's optimizer and DDP hold the Parameter objects), `params` is None."""
         self.names = [n for n, _ in named_params]
         sizes = [p.numel() for _, p in named_params]
         self.offsets = {}
@@ -41,15 +43,19 @@ class GradBook:
             self.offsets[n] = (off, sz, tuple(p.shape))
             off += _rup(sz, 4)  # keep every view 16-byte aligned
         self.total = off
-        self.params = torch.zeros(off, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(off, dtype=torch.float32, device=device)
-        self.g = {}
-        for n, p in named_params:
-            o, sz, shape = self.offsets[n]
-            view = self.params[o:o + sz].view(shape)
-            view.copy_(p.data)
-            p.data = view  # the nn.Parameter now aliases the flat vector (state_dict() is unchanged)
-            self.g[n] = self.grads[o:o + sz].view(shape)
+        self.params = torch.zeros(off, dtype=torch.float32, device=device) if bind else None
+        self.set_grads(torch.zeros(off, dtype=torch.float32, device=device))
+        if bind:
+            for n, p in named_params:
+                o, sz, shape = self.offsets[n]
+                view = self.params[o:o + sz].view(shape)
+                view.copy_(p.data)
+                p.data = view  # the nn.Parameter now aliases the flat vector (state_dict() is unchanged)
+
+    def set_grads(self, flat):
+        """Point the book (grads and the per-parameter views g) at the flat fp32 vector `flat`."""
+        self.grads = flat
+        self.g = {n: flat[o:o + sz].view(shape) for n, (o, sz, shape) in self.offsets.items()}
 
     def end_of(self, name):
         o, sz, _ = self.offsets[name]
@@ -777,14 +783,19 @@ class Backward:
         return True
 
     # ---- entry ------------------------------------------------------------------------------
-    def run(self, decoded, y, norm_stat, x_in, poly_emb, fh_b, L, after_ltsf=None):
+    def run(self, decoded, y, norm_stat, x_in, poly_emb, fh_b, L, after_ltsf=None, seed=None):
         """Fills book.grads (must be zeroed by the caller) from the retained forward activations.
-        `after_ltsf` (callable) is invoked once the LTSF gradients are complete (bucket hand-off)."""
+        `after_ltsf` (callable) is invoked once the LTSF gradients are complete (bucket hand-off).
+        `seed` = (g_loss, g_pred): autograd's gradients of the loss (device fp32 [1]) and of `decoded`, either may be None
+        (ops.mse_grad_seeded); None: d loss = 1 and nothing else reads `decoded` (ops.mse_grad)."""
         B, F, To = decoded.shape
         self._poly_emb, self._fh_b, self._L = poly_emb, fh_b, L
         self._ensure_streams()
         g_out = self._buf("g_out", (B, F, To))
-        ops.mse_grad(decoded, y, norm_stat, g_out, B, To)
+        if seed is None:
+            ops.mse_grad(decoded, y, norm_stat, g_out, B, To)
+        else:
+            ops.mse_grad_seeded(decoded, y, norm_stat, g_out, B, To, g_loss=seed[0], g_pred=seed[1])
         if not self._multi():
             g_poly = self.ltsf(g_out, x_in)
             if after_ltsf is not None:

@@ -292,6 +292,7 @@ _SIGNATURES = {
     "tcavt_softmax_bwd_rows": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_int, c_int, c_int,
                                c_void_p],
     "tcavt_mse_grad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "tcavt_mse_grad_seeded": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tcavt_out_head_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                            c_void_p],
     "tcavt_nlinear_bwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int,

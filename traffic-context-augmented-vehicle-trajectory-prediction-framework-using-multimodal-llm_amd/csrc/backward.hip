@@ -398,16 +398,27 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const unsigned sh
 // ---------------------------------------------------------------------------
 // Loss gradient (train.py:945-961): loss = mean_{b,t}(dx^2) + mean_{b,t}(dy^2) in pixels,
 // dx = (pred_x - gt_x) * rx  =>  dL/dpred_x = 2 * dx * rx / (B*To)
+// Seeded forms (autograd): g = g_loss[0] * dL/dpred + g_pred.  LOSS: the MSE term is scaled by the device scalar
+// g_loss; PRED: g_pred is added.  <false, false> is the unit seed of tcavt_mse_grad; <false, true> has no MSE term.
 // ---------------------------------------------------------------------------
+template <bool LOSS, bool PRED>
 __global__ void mse_grad_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                const float* __restrict__ ns, float* __restrict__ g, int B, int To) {
+                                const float* __restrict__ ns, const float* __restrict__ g_loss,
+                                const float* __restrict__ g_pred, float* __restrict__ g, int B, int To) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * 2 * To) return;
+  if (PRED && !LOSS) {
+    g[idx] = g_pred[idx];
+    return;
+  }
   const int b = idx / (2 * To), f = (idx / To) & 1;
   const float mn = ns[b * 4 + 2 * f], mx = ns[b * 4 + 2 * f + 1];
   const float r = mx - mn;
   const float d = (pred[idx] * r + mn) - (gt[idx] * r + mn);
-  g[idx] = 2.f * d * r / (float)(B * To);
+  float v = 2.f * d * r / (float)(B * To);
+  if (LOSS) v *= g_loss[0];
+  if (PRED) v += g_pred[idx];
+  g[idx] = v;
 }
 
 // out_head backward: out[b][f][s] = w[f].fused[b][s] + bias[f] (+x_last)
@@ -764,8 +775,28 @@ extern "C" int tcavt_mse_grad(const float* pred, const float* gt, const float* n
                               tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(pred && gt && norm_stat && g && B > 0 && To > 0, "mse_grad: bad args");
   const int n = B * 2 * To;
-  hipLaunchKernelGGL(mse_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, S_(stream), pred, gt, norm_stat, g, B, To);
+  hipLaunchKernelGGL((mse_grad_kernel<false, false>), dim3((n + 255) / 256), dim3(256), 0, S_(stream), pred, gt,
+                     norm_stat, nullptr, nullptr, g, B, To);
   TCAVT_CHECK_LAUNCH("mse_grad");
+  return TCAVT_OK;
+}
+
+extern "C" int tcavt_mse_grad_seeded(const float* pred, const float* gt, const float* norm_stat, const float* g_loss,
+                                     const float* g_pred, float* g, int B, int To, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(g && B > 0 && To > 0 && (g_loss || g_pred), "mse_grad_seeded: bad args (g_loss and g_pred both NULL?)");
+  TCAVT_CHECK_ARG(!g_loss || (pred && gt && norm_stat), "mse_grad_seeded: g_loss needs pred, gt and norm_stat");
+  const int n = B * 2 * To;
+  const dim3 grid((n + 255) / 256);
+  if (g_loss && g_pred)
+    hipLaunchKernelGGL((mse_grad_kernel<true, true>), grid, dim3(256), 0, S_(stream), pred, gt, norm_stat, g_loss,
+                       g_pred, g, B, To);
+  else if (g_loss)
+    hipLaunchKernelGGL((mse_grad_kernel<true, false>), grid, dim3(256), 0, S_(stream), pred, gt, norm_stat, g_loss,
+                       nullptr, g, B, To);
+  else
+    hipLaunchKernelGGL((mse_grad_kernel<false, true>), grid, dim3(256), 0, S_(stream), nullptr, nullptr, nullptr,
+                       nullptr, g_pred, g, B, To);
+  TCAVT_CHECK_LAUNCH("mse_grad_seeded");
   return TCAVT_OK;
 }
 

@@ -1613,6 +1613,9 @@ class MultiModalTrajectoryModel(nn.Module):
         # is in .train() mode; every forward uses seed dropout_seed + number of forwards so far.
         self.dropout_seed, self._fwd_count = 0x5EED, 0
         self._auto_range, self.range_contract = None, None  # set_storage("auto")
+        # loss.backward() (autograd.py): forwards so far, in any mode -- each one overwrites the tapes a pending backward reads;
+        # a training.Trainer drives its model itself and keeps it off the bridge
+        self._n_forward, self.driven_by_trainer, self._bridge = 0, False, None
 
     @classmethod
     def from_config(cls, cfg: ModelConfig):
@@ -1721,7 +1724,26 @@ class MultiModalTrajectoryModel(nn.Module):
         when the MLLM inputs of THIS call (vision_embs, input_ids, attention_mask) are ready on the device: a
         torch.cuda.Event (e.g. of the copy stream that uploaded the batch), True (already resident, nobody is writing them),
         or None: ready once the work queued on the current stream so far is done (always correct; the decoder then cannot
-        start before the previous step's optimizer has finished).  It is consumed by the call (reset to None)."""
+        start before the previous step's optimizer has finished).  It is consumed by the call (reset to None).
+
+        In grad mode with a supported trainable set (autograd.trainable_set: train.py's frozen MLLM, or that plus the LoRA
+        adapters) the outputs carry an autograd graph and loss.backward() runs the hand-written backward (autograd.py);
+        in every other state they are plain tensors."""
+        if torch.is_grad_enabled():
+            from . import autograd as _ag
+
+            kind = _ag.trainable_set(self)
+            if kind is not None:
+                return _ag.bridge_forward(self, kind, x, vision_embs, context_str, lane_polygon_batch, lane_polygon_len, y,
+                                          norm_stat, input_ids, attention_mask, labels)
+        return self._forward(x, vision_embs, context_str, lane_polygon_batch, lane_polygon_len, y=y, norm_stat=norm_stat,
+                             input_ids=input_ids, attention_mask=attention_mask, labels=labels)
+
+    def _forward(self, x, vision_embs, context_str, lane_polygon_batch, lane_polygon_len, y=None, norm_stat=None,
+                 input_ids=None, attention_mask=None, labels=None):
+        self._n_forward += 1
+        if self._bridge is not None and not self.driven_by_trainer:
+            self._bridge.refresh()  # (a model that has trained through loss.backward(): rebuild stale packed weights first)
         inputs_ready, self.inputs_ready = self.inputs_ready, None
         B = x.size(0)
         dev = x.device

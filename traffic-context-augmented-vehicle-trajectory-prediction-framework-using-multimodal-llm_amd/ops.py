@@ -778,6 +778,23 @@ def mse_grad(pred, gt, norm_stat, g, B, To):
     check(lib().tcavt_mse_grad(ptr(pred), ptr(gt), ptr(norm_stat), ptr(g), B, To, stream_ptr()), "tcavt_mse_grad")
 
 
+def mse_grad_seeded(pred, gt, norm_stat, g, B, To, g_loss=None, g_pred=None):
+    """g = g_loss[0] * mse_grad(pred, gt, norm_stat) + g_pred (autograd's seeds: g_loss a device fp32 scalar, read on the
+    device; g_pred [B, 2, To]).  A None term is absent; both None is refused.  g_loss = 1, g_pred None: mse_grad's bits."""
+    if g_loss is None and g_pred is None:
+        raise capi.TcavtError("mse_grad_seeded: g_loss and g_pred are both None")
+    checks = [(g, B * 2 * To, "g"), (g_loss, 1, "g_loss"), (g_pred, B * 2 * To, "g_pred")]
+    if g_loss is not None:
+        checks += [(pred, B * 2 * To, "pred"), (gt, B * 2 * To, "gt"), (norm_stat, B * 4, "norm_stat")]
+    for t, n, nm in checks:
+        _req(t, torch.float32, "mse_grad_seeded." + nm)
+        _need(t, n, "mse_grad_seeded." + nm)
+    if g_loss is None:
+        pred = gt = norm_stat = None
+    check(lib().tcavt_mse_grad_seeded(ptr(pred), ptr(gt), ptr(norm_stat), ptr(g_loss), ptr(g_pred), ptr(g), B, To,
+                                      stream_ptr()), "tcavt_mse_grad_seeded")
+
+
 def out_head_bwd(g, fused, w, gf, gw, gb, B, To, C, F):
     for t, n, nm in ((g, B * F * To, "g"), (fused, B * To * C, "fused"), (w, F * C, "w"), (gf, B * To * C, "gf"),
                      (gw, F * C, "gw"), (gb, F, "gb")):

@@ -29,6 +29,72 @@ def trainable_named_parameters(model):
     return ltsf + poly
 
 
+def backward_flags(model, lora_trainable, train_mllm_front=False):
+    """[(object, attribute, value)]: the model flags under which the forward keeps what the hand-written backward of a
+    trainable set reads.  Shared by Trainer (set once, for good) and the autograd bridge (set around its own calls)."""
+    dev = next(model.parameters()).device
+    flags = []
+    if lora_trainable:
+        flags += [(model.mllm.llama_wrapper, "save_for_backward", True),
+                  (model.ltsf, "absorb_kv", False)]  # the LoRA backward starts from dL/dk, dL/dv of the un-absorbed cross-attention
+    if train_mllm_front:
+        flags.append((model.mllm.qformer, "save_for_backward", True))
+    flags += [(model.lane_polygon_encoder, "save_for_backward", True), (model.ltsf, "save_for_backward", True),
+              # train.py's frozen MLLM: its pass reads nothing this step's backward / optimizer writes, so it runs on a stream
+              # of its own and the next step's decoder overlaps this step's head, backward and AdamW (model.pipeline_decoder)
+              (model, "pipeline_decoder", not lora_trainable and dev.type == "cuda"),
+              (model.mllm, "skip_f32_hidden", not lora_trainable)]  # the head consumes the 16-bit final hidden states only
+    return flags
+
+
+def make_backward(model, book, lora_trainable, train_mllm_front=False):
+    """(Backward, LoraBackward or None, QFormerBackward or None) of a trainable set, writing into `book`."""
+    bw, lbw, qbw = Backward(model, book), None, None
+    if lora_trainable:
+        bw.poly_after_chain = True  # (the decoder's backward follows on the caller's stream: backward.Backward._ltsf_stage)
+        lbw = LoraBackward(model, book)
+    if train_mllm_front:
+        qbw = QFormerBackward(model, book, bw)
+        lbw.input_grad = True
+    return bw, lbw, qbw
+
+
+def run_backward(model, bw, lbw, qbw, decoded, y, ns, x, B, L, exchange=None, bounds=None, seed=None):
+    """The backward of the last forward into the stages' book (zeroed by the caller): head and LTSF, the lane-polygon
+    encoder beside them, then the decoder (lbw) and the Q-Former (qbw) when they train.  exchange(lo, hi) with bounds =
+    (end of the LTSF, end of the train.py set, end of the book): the gradient hand-off of each bucket as it completes.
+    seed = (g_loss, g_pred) (autograd): Backward.run's seeded loss gradient; None = d loss = 1."""
+    after_ltsf = (lambda: exchange(0, bounds[0])) if exchange is not None else None
+    bw.run(decoded, y, ns, x, model.last.poly_emb, model.last.final_hidden_bf16, L, after_ltsf=after_ltsf, seed=seed)
+    if lbw is not None:
+        lora_backward(model, bw, lbw, qbw, B, L)  # (the caller's chain continues; the lane-polygon encoder's backward runs beside it)
+        bw.join()
+        if exchange is not None:
+            exchange(bounds[0], bounds[1])
+            exchange(bounds[1], bounds[2])
+    elif exchange is not None:
+        exchange(bounds[0], bounds[1])
+
+
+def lora_backward(model, bw, lbw, qbw, B, L):
+    """Gradient of the decoder's final hidden states = what flows back through the cross-attention's key and value
+    in-projections (k = fh W_k^T + b_k, v = fh W_v^T + b_v; the LTSF backward left dL/dk, dL/dv behind), then the
+    walk through the frozen layers."""
+    H = model.llama_hidden_size
+    ca = model.ltsf.decoder.cross_attn
+    g_k = bw._buf("xa.g_k", (B * L + 64, H), torch.bfloat16)
+    g_v = bw._buf("xa.g_v", (B * L + 64, H), torch.bfloat16)
+    gfa = bw._buf("lora.gfa", (B * L, H), torch.bfloat16)
+    gfb = bw._buf("lora.gfb", (B * L, H), torch.bfloat16)
+    for W, g, out, tag in ((ca.in_proj_weight[H:2 * H], g_k, gfa, "k"), (ca.in_proj_weight[2 * H:], g_v, gfb, "v")):
+        WT = bw._buf(f"lora.WT{tag}", (H, H), torch.bfloat16)
+        ops.transpose_f32_bf16(W.detach(), WT, H, H, H)
+        ops.gemm_bf16(g[: B * L], WT, out=out)
+    g_h0 = lbw.run(gfa, gfb)
+    if qbw is not None:
+        qbw.run(g_h0, B, L)
+
+
 class Trainer:
     """lora_trainable=False: scripts/train.py (whole MLLM frozen, :1140-1145).
 
@@ -89,25 +155,12 @@ class Trainer:
         self.v = torch.zeros_like(self.book.params)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.step_count = 0
-        self.bw = Backward(model, self.book)
-        self.lbw = None
+        self.bw, self.lbw, self.qbw = make_backward(model, self.book, self.lora_trainable, self.train_mllm_front)
         if self.lora_trainable:
-            self.bw.poly_after_chain = True  # (the decoder's backward follows on the caller's stream: backward.Backward._ltsf_stage)
-            self.lbw = LoraBackward(model, self.book)
-            model.mllm.llama_wrapper.save_for_backward = True
-            model.ltsf.absorb_kv = False  # _lora_backward starts from dL/dk, dL/dv of the un-absorbed cross-attention
             self._lora_stacked = self._stacked_lora_views(lora)
-        self.qbw = None
-        if self.train_mllm_front:
-            self.qbw = QFormerBackward(model, self.book, self.bw)
-            self.lbw.input_grad = True
-            model.mllm.qformer.save_for_backward = True
-        model.lane_polygon_encoder.save_for_backward = True
-        model.ltsf.save_for_backward = True
-        # train.py's frozen MLLM: its pass reads nothing this step's backward / optimizer writes, so it runs on a stream
-        # of its own and the next step's decoder overlaps this step's head, backward and AdamW (model.pipeline_decoder)
-        model.pipeline_decoder = not self.lora_trainable and dev.type == "cuda"
-        model.mllm.skip_f32_hidden = not self.lora_trainable  # the head consumes the 16-bit final hidden states only
+        for obj, attr, value in backward_flags(model, self.lora_trainable, self.train_mllm_front):
+            setattr(obj, attr, value)
+        model.driven_by_trainer = True  # (its forward stays off the autograd bridge in grad mode as well: autograd.py)
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         # Stream budget.  The pipelined step (model.pipeline_decoder) keeps its overlap only while at most FIVE HIP streams are
@@ -226,16 +279,8 @@ class Trainer:
             if next_vision_embs is not None and not self.train_mllm_front:
                 m.prefetch(next_vision_embs, ready=next_ready)  # before the backward: its leaf work shares the prefetch stream's queue
             B, L = input_ids.shape[0], m.mllm.qformer.num_query_tokens + input_ids.shape[1]
-            fh_b = m.last.final_hidden_bf16  # [B * L + 64 zeroed pad rows, H]
-            self.bw.run(decoded, y.contiguous(), ns, x.contiguous(), m.last.poly_emb, fh_b, L,
-                        after_ltsf=lambda: self._allreduce_bucket(0, self.n_ltsf))
-            if self.lbw is not None:
-                self._lora_backward(B, L)   # (the caller's chain continues; the lane-polygon encoder's backward runs beside it)
-                self.bw.join()
-                self._allreduce_bucket(self.n_ltsf, self.n_base)
-                self._allreduce_bucket(self.n_base, self.book.total)
-            else:
-                self._allreduce_bucket(self.n_ltsf, self.n_base)
+            run_backward(m, self.bw, self.lbw, self.qbw, decoded, y.contiguous(), ns, x.contiguous(), B, L,
+                         exchange=self._allreduce_bucket, bounds=(self.n_ltsf, self.n_base, self.book.total))
         self._last_loss = loss
         return loss, decoded
 
@@ -255,25 +300,6 @@ class Trainer:
             off, _, shape = offs[k]
             views.append(self.book.params.as_strided((nL,) + tuple(shape), (stride, shape[1], 1), off))
         return tuple(views)
-
-    def _lora_backward(self, B, L):
-        """Gradient of the decoder's final hidden states = what flows back through the cross-attention's key and value
-        in-projections (k = fh W_k^T + b_k, v = fh W_v^T + b_v; the LTSF backward left dL/dk, dL/dv behind), then the
-        walk through the frozen layers."""
-        m, bw = self.model, self.bw
-        H = m.llama_hidden_size
-        ca = m.ltsf.decoder.cross_attn
-        g_k = bw._buf("xa.g_k", (B * L + 64, H), torch.bfloat16)
-        g_v = bw._buf("xa.g_v", (B * L + 64, H), torch.bfloat16)
-        gfa = bw._buf("lora.gfa", (B * L, H), torch.bfloat16)
-        gfb = bw._buf("lora.gfb", (B * L, H), torch.bfloat16)
-        for W, g, out, tag in ((ca.in_proj_weight[H:2 * H], g_k, gfa, "k"), (ca.in_proj_weight[2 * H:], g_v, gfb, "v")):
-            WT = bw._buf(f"lora.WT{tag}", (H, H), torch.bfloat16)
-            ops.transpose_f32_bf16(W.detach(), WT, H, H, H)
-            ops.gemm_bf16(g[: B * L], WT, out=out)
-        g_h0 = self.lbw.run(gfa, gfb)
-        if self.qbw is not None:
-            self.qbw.run(g_h0, B, L)
 
     def clip_grad_norm_(self, max_norm, grad_scale=1.0):
         """torch.nn.utils.clip_grad_norm_(trainable, max_norm) (modify_train.py:1192) on the flat gradient vector,
