@@ -406,8 +406,8 @@ def test_gemm_w4_persistent_stream(gpu):
             # look-ahead reaches two K-tiles ahead) -- except with the generic epilogue, which stays one workgroup per tile
             r4d = ops.gemm_bf16(a, w, out_dtype=dt, tile=272, **kw)
             assert torch.equal(r8, r4d), (K, sorted(kw), "deep")
-        # fp16 operands, the decoder's forms: SiLU * up with the fused row scale stays covered by the model-level tests; here
-        # the in-place 16-bit residual epilogue through the persistent deep form against the one-barrier form
+        # fp16 operands, the decoder's forms: SiLU * up with the fused row scale against float64 is in tests/test_gemm_forms_gpu.py;
+        # here the SiLU epilogue through the persistent deep form against the one-barrier form
         a16, w16 = a.float().half(), w.float().half()
         r_a = ops.gemm_bf16(a16, w16, out_dtype=torch.float16, tile=257, silu_mul=True)
         r_b = ops.gemm_bf16(a16, w16, out_dtype=torch.float16, tile=272, silu_mul=True)
