@@ -1138,6 +1138,56 @@ int tcavt_adamw_gated(float* p, const float* g, float* m, float* v, int64_t n, f
                       float eps, float weight_decay, float grad_scale, const float* loss, const float* grad_norm,
                       int32_t* ctl, tcavt_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * LM loss on labels: lm_head + cross-entropy fused, forward and backward -- `outputs.loss` of
+ * LlamaWithCrossAttnPEFT.forward(..., labels=fused_labels) (scripts/train.py:445-453, 536-552; HF LlamaForCausalLM with
+ * `labels`), the objective of the stage-1 (MLLM text) fine-tune.  The [B * L][V] logits are never stored.
+ *
+ * Rows: fused_labels[b][p] = -100 for p < Nq and labels[b][p - Nq] otherwise; row (b, p), p < L - 1, is LABELLED when
+ * t = fused_labels[b][p + 1] != -100 (the last image row predicts the first text label; the last position predicts nothing).
+ * A label outside [0, V) other than -100, or a labelled position p + 1 >= kv_len[b], leaves the row unlabelled and stores 1
+ * to *flag (kernels only ever set it; the host reads and clears it).  Rows are selected on the device: no host sync.
+ *
+ *   z       = h16[b][p] . table^T                 fp32 accumulation of the 16-bit operands; nothing after it is rounded below fp32
+ *   lse     = logsumexp(z)                        per (row, 128-column tile) maximum and sum of exponentials, merged in tile order
+ *   loss    = (1 / N) sum_labelled (lse - z[t])   N = *count labelled rows; N == 0: NaN (as torch), and an all-zero gradient
+ *   g_out   = round16((g_loss / N) * (P . table)) on labelled rows, bit zero on every other row,
+ *             P = round16(exp(z - lse) - onehot(t)): the only 16-bit rounding of the backward besides the output.  With fp16
+ *             operands P is held times 2^14 (a probability down to 2^-28 stays a normal fp16 number) and the factor is undone
+ *             exactly in fp32 together with g_loss / N.  The sum over the vocabulary runs in chunks of 16384 columns, fp32, in
+ *             chunk order, without float atomics: results are bit-reproducible.  The table gets no gradient.
+ *
+ * tcavt_lm_loss_forward writes loss, count, lse and (optional) row_loss; lse and row_loss are indexed by row b * L + p and read 0
+ * on unlabelled rows.  tcavt_lm_loss_backward takes the same arguments plus lse (as the forward left it), table_t, g_loss and
+ * g_out; it selects the rows again (and rewrites *count with the same value), so it needs nothing else from the forward's
+ * workspace.  workspace: tcavt_lm_loss_workspace_bytes(B * L, V, H) bytes, 256-byte aligned, contents undefined between calls;
+ * it holds the row list, the per-tile statistics, ONE chunk of P and the fp32 accumulator -- never a [rows][V] array
+ * (rows 8192, V 128256, H 2048: 383 MiB against 4.2 GB of fp32 logits).  V % 16 == 0, H % 256 == 0. */
+typedef struct tcavt_lm_loss_args {
+  const void* h16; int64_t ldh;       /* 16-bit [B * L][ldh]: post-final-norm hidden states (tcavt_llama_stack_args.out16) */
+  const void* table;                  /* 16-bit [V][H]: the tied embedding table */
+  const void* table_t; int64_t ldt;   /* backward only: 16-bit [H][ldt] transpose of the table, ldt >= V rounded up to 64 and
+                                         % 8 == 0, columns >= V zero.  Made once per checkpoint; not part of the workspace */
+  const int64_t* labels;              /* [B][L - Nq] */
+  const int32_t* kv_len;              /* optional [B]: valid length of each sample (image + text tokens) */
+  int32_t B, L, V, H, Nq;
+  int32_t dtype16;                    /* TCAVT_F16 | TCAVT_BF16: type of h16, table, table_t (and of P) */
+  int32_t grad_dtype;                 /* backward: type of g_out, TCAVT_BF16 | TCAVT_F16 */
+  int32_t reserved0;
+  float* loss;                        /* fp32 [1] (forward) */
+  int32_t* count;                     /* int32 [1] */
+  float* lse;                         /* fp32 [B * L]: written by the forward, read by the backward */
+  float* row_loss;                    /* optional fp32 [B * L] (forward) */
+  int32_t* flag;                      /* optional int32 [1]: bad-label flag */
+  const float* g_loss;                /* backward, optional device fp32 scalar: d objective / d loss; NULL means 1 */
+  void* g_out; int64_t ldg;           /* backward: grad_dtype [B * L][ldg], ldg >= H and % 4 == 0 */
+  void* workspace; int64_t workspace_bytes;
+} tcavt_lm_loss_args;
+
+int64_t tcavt_lm_loss_workspace_bytes(int64_t rows, int V, int H);
+int tcavt_lm_loss_forward(const tcavt_lm_loss_args* args, tcavt_stream_t stream);
+int tcavt_lm_loss_backward(const tcavt_lm_loss_args* args, tcavt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

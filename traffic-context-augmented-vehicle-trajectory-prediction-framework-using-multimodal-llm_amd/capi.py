@@ -216,6 +216,16 @@ class DecodeArgs(ctypes.Structure):
         ("w_layout", ctypes.c_int32), ("act_layout", ctypes.c_int32), ("table_packed", c_void_p)]
 
 
+class LmLossArgs(ctypes.Structure):
+    """Mirror of ``tcavt_lm_loss_args`` (include/tcavt.h)."""
+
+    _fields_ = [("h16", c_void_p), ("ldh", c_int64), ("table", c_void_p), ("table_t", c_void_p), ("ldt", c_int64),
+                ("labels", c_void_p), ("kv_len", c_void_p)] + [(n, ctypes.c_int32) for n in (
+                    "B", "L", "V", "H", "Nq", "dtype16", "grad_dtype", "reserved0")] + [(n, c_void_p) for n in (
+                        "loss", "count", "lse", "row_loss", "flag", "g_loss", "g_out")] + [
+        ("ldg", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
 # name -> argtypes (return type is always int unless listed in _RESTYPES)
 _SIGNATURES = {
     "tcavt_abi_version": [],
@@ -327,8 +337,12 @@ _SIGNATURES = {
     "tcavt_event_elapsed_ms": [c_void_p, c_void_p, ctypes.POINTER(c_float)],
     "tcavt_adamw_gated": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                           c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tcavt_lm_loss_workspace_bytes": [c_int64, c_int, c_int],
+    "tcavt_lm_loss_forward": [ctypes.POINTER(LmLossArgs), c_void_p],
+    "tcavt_lm_loss_backward": [ctypes.POINTER(LmLossArgs), c_void_p],
 }
-_RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64}
+_RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64,
+             "tcavt_lm_loss_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -9,9 +9,11 @@ so that train.py-style callers drop in.  Every module holds its parameters as fp
 
 Differences from the reference that are deliberate and documented in DESIGN.md:
   * ``from_pretrained`` fetches are replaced by an explicit ``LlamaShape`` (no network);
-  * ``lm_head`` + cross-entropy of the reference's LLM call are dead work (its caller keeps
-    only ``hidden_states[-1]``, train.py:553) and are not computed: ``outputs.loss`` and
-    ``outputs.logits`` are ``None``;
+  * ``lm_head`` + cross-entropy of the reference's LLM call are not computed by the trajectory
+    path (its caller keeps only ``hidden_states[-1]``, train.py:553).  The LM loss is opt-in:
+    ``LlamaWithCrossAttnPEFT.forward(..., labels=...)`` and ``LlamaMultiModal.lm_forward`` fill
+    ``outputs.loss`` from the fused kernel (csrc/lm_loss.hip); ``outputs.logits`` stays ``None``
+    (the [B * L, V] logits are never stored);
   * the tokenizer branch of ``LlamaMultiModal.forward`` (train.py:556-575) runs when a tokenizer
     object is attached (``model.mllm.tokenizer``; none can be fetched offline) and raises
     ``NotImplementedError`` otherwise;
@@ -681,7 +683,48 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
     def _invalidate(self):
         self._prep_T = None
         self._prep_dec = None
+        self._prep_tableT = None
         _Prepared._invalidate(self)
+
+    # ---- LM loss on labels (opt-in: csrc/lm_loss.hip) ---------------------------------
+    def table_T(self):
+        """16-bit [H, V rounded up to 64] transpose of the tied table (zero beyond V): the LM loss backward's second
+        operand.  A second copy of the table (525 MB at the Llama-3.2-1B shape), made on the first LM-loss backward and
+        dropped with the packed weights it was made from, like the other transposed copies."""
+        P = self._prepared()
+        if getattr(self, "_prep_tableT", None) is None or self._prep_tableT[0] is not P:
+            with torch.no_grad():
+                self._prep_tableT = (P, ops.lm_table_t(P.table))
+        return self._prep_tableT[1]
+
+    def lm_loss(self, final16, labels, Nq, B, L, kv_len=None, flag=None):
+        """Mean cross-entropy of the labelled rows (HF LlamaForCausalLM with ``labels``: row p predicts fused label p + 1,
+        ignore_index -100, plain mean) from the 16-bit post-final-norm hidden states `final16` [>= B * L, H] and the tied
+        16-bit table; labels int64 [B, L - Nq] (the image positions are unlabelled).  One fused pass: the logits are
+        never stored.  Returns the state lm_loss_backward needs; .loss fp32 [1] and .count int32 [1] stay on the device
+        (no host sync).  flag: int32 [1], set by the kernel on a label outside [0, V) or beyond kv_len."""
+        P, ws, dev = self._prepared(), self._ws, final16.device
+        V, H = P.table.shape
+        wsb = ws.get("ll.lmloss.ws", (ops.lm_loss_workspace_bytes(B * L, V, H),), torch.uint8, dev)
+        lse = ws.get("ll.lmloss.lse", (B * L,), torch.float32, dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        ops.lm_loss_forward(final16, P.table, labels, Nq, B, L, loss=loss, count=count, lse=lse, workspace=wsb, kv_len=kv_len,
+                            flag=flag)
+        return SimpleNamespace(loss=loss, count=count, lse=lse, h16=final16, labels=labels, Nq=Nq, B=B, L=L, kv_len=kv_len,
+                               flag=flag, workspace=wsb)
+
+    def lm_loss_backward(self, st, g_loss=None, out=None):
+        """d loss / d (post-final-norm hidden states) as one bf16 [B * L, H] tensor -- what LoraBackward.run takes as
+        g_final_a: (g_loss / N) (softmax(z) - onehot) table on labelled rows, zeros elsewhere.  g_loss: optional device
+        fp32 [1] (absent: 1)."""
+        P, dev = self._prepared(), st.h16.device
+        H = P.table.shape[1]
+        if out is None:
+            out = self._ws.get("ll.lmloss.g_final", (st.B * st.L, H), torch.bfloat16, dev)
+        return ops.lm_loss_backward(st.h16, P.table, self.table_T(), st.labels, st.Nq, st.B, st.L, lse=st.lse, count=st.count,
+                                    g_out=out, workspace=st.workspace, g_loss=g_loss, kv_len=st.kv_len, flag=st.flag)
 
     def decode_weights(self):
         """Fragment-major copies of the frozen projection weights and of the tied embedding table for the decode step of
@@ -889,7 +932,10 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         del keep
 
     def forward(self, inputs_embeds, attention_mask, labels=None, output_hidden_states=False):
-        """HF-call-shaped entry (train.py:445-453).  Only ``hidden_states[-1]`` is produced."""
+        """HF-call-shaped entry (train.py:445-453).  ``hidden_states[-1]`` is produced; with ``labels`` (the FUSED labels
+        [B, L], -100 on the image positions: train.py:536-552) ``.loss`` is the LM loss as a device fp32 scalar, from the
+        fused lm_head + cross-entropy kernel (no host sync beyond the one this call already has).  ``.logits`` stays
+        ``None``: the [B * L, V] logits are never stored."""
         B, L, H = inputs_embeds.shape
         dev = inputs_embeds.device
         if self.stream16:
@@ -901,14 +947,26 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
             h.copy_(inputs_embeds.reshape(B * L, H))
             ops.rownorm_prep(h, *self.norm_inputs(B * L, dev), npart=self.norm_npart(B * L), stream_scale=self.stream_scale)
         kv_len = torch.empty(B, dtype=torch.int32, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        ops.mask_to_kvlen(attention_mask.to(torch.int64).contiguous(), 0, kv_len, flag)
+        flag = torch.zeros(2 if labels is not None else 1, dtype=torch.int32, device=dev)
+        ops.mask_to_kvlen(attention_mask.to(torch.int64).contiguous(), 0, kv_len, flag[0:1])
         out = torch.empty((B * L, H), dtype=torch.float32, device=dev)
-        self.decoder_stack(h, kv_len, B, L, out_f32=out)
-        if flag.item():
+        loss = None
+        if labels is None:
+            self.decoder_stack(h, kv_len, B, L, out_f32=out)
+        else:
+            if tuple(labels.shape) != (B, L):
+                raise ValueError(f"labels must be the fused labels [B, L] = {(B, L)} (-100 on the image positions)")
+            out16 = self._ws.get("ll.lmloss.h16", (B * L, H), self.storage, dev)
+            self.decoder_stack(h, kv_len, B, L, out_f32=out, out_bf16=out16)
+            self.lm_state = self.lm_loss(out16, labels, 0, B, L, kv_len=kv_len, flag=flag[1:2])
+            loss = self.lm_state.loss.reshape(())
+        f = flag.tolist()
+        if f[0]:
             raise ValueError("attention_mask must be right-padded (a prefix of ones per row)")
+        if len(f) > 1 and f[1]:
+            raise ValueError("labels contain ids outside [0, vocab) other than -100, or a label at or beyond a sample's valid length")
         hs = (None,) * self.shape.layers + (out.view(B, L, H),)
-        return SimpleNamespace(loss=None, logits=None, hidden_states=hs if output_hidden_states else None,
+        return SimpleNamespace(loss=loss, logits=None, hidden_states=hs if output_hidden_states else None,
                                last_hidden_state=out.view(B, L, H))
 
 
@@ -1052,8 +1110,29 @@ class LlamaMultiModal(nn.Module, _Prepared):
             return final, Nq, final_b
         return final, Nq
 
+    def lm_forward(self, vision_embs, context_str, input_ids=None, attention_mask=None, labels=None):
+        """The MLLM pass with the LM loss on `labels` [B, Lt] (what train.py:536-552 hands to the LLM as fused labels: the
+        image positions are unlabelled, the last image token predicts the first text label).  Opt-in: forward() keeps
+        ignoring labels.  Returns .loss (device fp32 scalar; NaN when no row is labelled, as torch), .n_tokens (device
+        int32 [1]: labelled rows), .final_hidden [B, L, H], .final_hidden_bf16 and .num_image_tokens; .state is what
+        llama_wrapper.lm_loss_backward takes.  A bad label sets a device flag that check_flags() reports."""
+        if labels is None:
+            raise ValueError("lm_forward needs labels (the LM loss is defined on them)")
+        final, Nq, final_b = self.forward(vision_embs, context_str, input_ids=input_ids, attention_mask=attention_mask,
+                                          return_bf16=True)
+        B, L = final.shape[0], final.shape[1]
+        dev = final_b.device
+        self._lm_flag = self._ws.get("mm.lmflag", (1,), torch.int32, dev, zero=True)
+        st = self.llama_wrapper.lm_loss(final_b[: B * L], labels, Nq, B, L, kv_len=self._ws.get("mm.kvlen", (B,), torch.int32, dev),
+                                        flag=self._lm_flag)
+        return SimpleNamespace(loss=st.loss.reshape(()), n_tokens=st.count, final_hidden=final, final_hidden_bf16=final_b,
+                               num_image_tokens=Nq, state=st)
+
     def check_flags(self):
         """Host-side check of the device error flags accumulated since the last check (one sync); clears them."""
+        if getattr(self, "_lm_flag", None) is not None and self._lm_flag.item():
+            self._lm_flag.zero_()
+            raise ValueError("labels contain ids outside [0, vocab) other than -100, or a label at or beyond a sample's valid length")
         if getattr(self, "_last_flags", None) is None:
             return
         f = self._last_flags.tolist()

@@ -1112,3 +1112,78 @@ class StackEvents:
         if self.arr is not None:
             lib().tcavt_events_destroy(self.arr, self.n)
             self.arr = None
+
+
+# ---- LM loss on labels (csrc/lm_loss.hip): fused lm_head + cross-entropy, forward and backward ----------------------------
+def lm_loss_workspace_bytes(rows, V, H):
+    """Transient device memory of lm_loss_forward / lm_loss_backward for `rows` = B * L hidden-state rows."""
+    return int(lib().tcavt_lm_loss_workspace_bytes(int(rows), int(V), int(H)))
+
+
+def lm_table_t(table):
+    """The backward's second operand: 16-bit [H, V rounded up to 64] transpose of the tied table, zero beyond V.  A layout of
+    the frozen weights made once per checkpoint (LlamaWithCrossAttnPEFT.table_T caches it), not part of the workspace."""
+    _req16(table, "lm_table_t.table")
+    V, H = table.shape
+    out = torch.zeros(H, (V + 63) // 64 * 64, dtype=table.dtype, device=table.device)
+    out[:, :V].copy_(table.t())
+    return out
+
+
+def _lm_loss_args(h16, table, labels, Nq, B, L, kv_len, flag, workspace, who):
+    _req16(h16, who + ".h16", rows_ok=True)
+    _req16(table, who + ".table", like=h16)
+    _req(labels, torch.int64, who + ".labels")
+    _req(kv_len, torch.int32, who + ".kv_len")
+    _req(flag, torch.int32, who + ".flag")
+    _req(workspace, torch.uint8, who + ".workspace")
+    if h16.dim() != 2 or table.dim() != 2 or h16.shape[1] != table.shape[1]:
+        raise capi.TcavtError(f"{who}: h16 [rows, H] and table [V, H] required")
+    V, H = table.shape
+    if h16.shape[0] < B * L or labels.numel() != B * (L - Nq) or (kv_len is not None and kv_len.numel() < B):
+        raise capi.TcavtError(f"{who}: h16 needs B * L rows, labels B * (L - Nq) elements, kv_len B")
+    a = capi.LmLossArgs()
+    a.h16, a.ldh, a.table = h16.data_ptr(), h16.stride(0), table.data_ptr()
+    a.labels = labels.data_ptr()
+    a.kv_len = None if kv_len is None else kv_len.data_ptr()
+    a.B, a.L, a.V, a.H, a.Nq = B, L, V, H, Nq
+    a.dtype16 = _DT[h16.dtype]
+    a.flag = None if flag is None else flag.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return a
+
+
+def lm_loss_forward(h16, table, labels, Nq, B, L, *, loss, count, lse, workspace, row_loss=None, kv_len=None, flag=None):
+    """Mean cross-entropy of the labelled rows (include/tcavt.h: tcavt_lm_loss_forward).  h16: 16-bit [>= B * L, H]
+    post-final-norm hidden states; table 16-bit [V, H]; labels int64 [B, L - Nq].  Writes loss fp32 [1], count int32 [1],
+    lse (and row_loss) fp32 [B * L]; no host sync."""
+    a = _lm_loss_args(h16, table, labels, Nq, B, L, kv_len, flag, workspace, "lm_loss_forward")
+    for t, n, nm in ((loss, 1, "loss"), (lse, B * L, "lse"), (row_loss, B * L, "row_loss")):
+        _req(t, torch.float32, "lm_loss_forward." + nm)
+        _need(t, n, "lm_loss_forward." + nm)
+    _req(count, torch.int32, "lm_loss_forward.count")
+    a.loss, a.count, a.lse = loss.data_ptr(), count.data_ptr(), lse.data_ptr()
+    a.row_loss = None if row_loss is None else row_loss.data_ptr()
+    check(lib().tcavt_lm_loss_forward(ctypes.byref(a), stream_ptr()), "tcavt_lm_loss_forward")
+    return loss
+
+
+def lm_loss_backward(h16, table, table_t, labels, Nq, B, L, *, lse, count, g_out, workspace, g_loss=None, kv_len=None, flag=None):
+    """g_out [B * L, H] (16-bit, its own dtype: bf16 for LoraBackward.run) = (g_loss / N) (softmax(z) - onehot) . table on the
+    labelled rows, zeros elsewhere (tcavt_lm_loss_backward).  lse / count: as lm_loss_forward left them; table_t: lm_table_t."""
+    a = _lm_loss_args(h16, table, labels, Nq, B, L, kv_len, flag, workspace, "lm_loss_backward")
+    _req16(table_t, "lm_loss_backward.table_t", like=table)
+    _req16(g_out, "lm_loss_backward.g_out", rows_ok=True)
+    _req(lse, torch.float32, "lm_loss_backward.lse")
+    _req(count, torch.int32, "lm_loss_backward.count")
+    _req(g_loss, torch.float32, "lm_loss_backward.g_loss")
+    _need(lse, B * L, "lm_loss_backward.lse")
+    V, H = table.shape
+    if table_t.dim() != 2 or table_t.shape[0] != H or g_out.dim() != 2 or g_out.shape[0] < B * L or g_out.shape[1] != H:
+        raise capi.TcavtError("lm_loss_backward: table_t [H, >= V rounded up to 64] and g_out [>= B * L, H] required")
+    a.table_t, a.ldt = table_t.data_ptr(), table_t.stride(0)
+    a.lse, a.count = lse.data_ptr(), count.data_ptr()
+    a.g_loss = None if g_loss is None else g_loss.data_ptr()
+    a.g_out, a.ldg, a.grad_dtype = g_out.data_ptr(), g_out.stride(0), _DT[g_out.dtype]
+    check(lib().tcavt_lm_loss_backward(ctypes.byref(a), stream_ptr()), "tcavt_lm_loss_backward")
+    return g_out

@@ -438,3 +438,111 @@ class Trainer:
         if self.check_flags_every > 0 and self.step_count % self.check_flags_every == 0:
             self.check_flags()
         return out
+
+
+class MllmTrainer:
+    """Stage-1 (MLLM text) fine-tune step: the LM loss on `labels` trains the LoRA adapters of q_proj / v_proj -- the
+    objective behind the reference's `outputs.loss` (scripts/train.py:445-453, 536-552) and the `mllm_ckpt` its scripts load.
+
+        taped decoder forward -> LM loss (fused lm_head + cross-entropy) -> its backward into g_final ->
+        LoraBackward.run(g_final) -> [QFormerBackward] -> clip -> tcavt_adamw_gated
+
+    The trajectory head is neither run nor trained.  train_mllm_front=True adds the Q-Former, mllm.q_proj and the two modality
+    embeddings to the trainable set (the backward continues below decoder layer 0).  The pieces are Trainer's: backward_flags /
+    make_backward, GradBook, the device-chosen gradient scale with its back-off, the norm clip and the gated AdamW (a non-finite
+    loss -- no labelled row gives NaN -- or gradient norm skips the update, decided on the device).
+    Single process: a process group of more than one rank is refused (the LM-loss step has no gradient exchange)."""
+
+    def __init__(self, model, lr=5e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
+                 train_mllm_front=False, process_group=None):
+        world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        if world > 1:
+            raise RuntimeError(f"MllmTrainer is single process: the process group has {world} ranks and the LM-loss step has no "
+                               "gradient exchange (data parallel for the stage-1 trainer is not implemented)")
+        lw = model.mllm.llama_wrapper
+        if not lw.use_lora:
+            raise ValueError("MllmTrainer: the model has no LoRA adapters (use_lora=False)")
+        self.model = model
+        dev = next(model.parameters()).device
+        for p in model.parameters():
+            p.requires_grad_(False)
+        lora = lora_named_parameters(model)
+        named = list(lora)
+        self.train_mllm_front = bool(train_mllm_front)
+        if self.train_mllm_front:
+            named += [(n, p) for n, p in model.named_parameters()
+                      if n.startswith(("mllm.q_proj.", "mllm.qformer.")) or n in ("mllm.vision_modality_embedding",
+                                                                                   "mllm.text_modality_embedding")]
+        for _, p in named:
+            p.requires_grad_(True)
+        self.book = GradBook(named, dev)
+        self.m = torch.zeros_like(self.book.params)
+        self.v = torch.zeros_like(self.book.params)
+        self.lr, self.wd, self.betas, self.eps, self.max_grad_norm = lr, weight_decay, betas, eps, max_grad_norm
+        self.bw, self.lbw, self.qbw = make_backward(model, self.book, True, self.train_mllm_front)
+        self._lora_stacked = Trainer._stacked_lora_views(self, lora)
+        for obj, attr, value in backward_flags(model, True, self.train_mllm_front):
+            if obj is model.mllm or obj is lw or obj is model.mllm.qformer:  # (the head's flags stay: it is not run here)
+                setattr(obj, attr, value)
+        model.driven_by_trainer = True
+        self._ctl = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.lbw.scale_backoff = self._ctl[6:7]
+        self._clip_scratch = None
+        self.step_count = 0
+        self.last = None
+        model.invalidate_prepared()
+
+    clip_grad_norm_ = Trainer.clip_grad_norm_
+
+    def forward_backward(self, vision_embs, input_ids, attention_mask, labels):
+        """zero_grad + taped forward + LM loss + backward; gradients end up in ``self.book.g``.  Returns the loss (device scalar)."""
+        from .model import DropoutCtx
+
+        m = self.model
+        mm, lw = m.mllm, m.mllm.llama_wrapper
+        with torch.no_grad():
+            self.book.grads.zero_()
+            dctx = None
+            if m.training:
+                dctx = DropoutCtx(m.dropout_seed + m._fwd_count)
+                m._fwd_count += 1
+            mm.qformer.dctx, lw.dctx = (dctx.sub(1), dctx.sub(2)) if dctx is not None else (None, None)
+            out = mm.lm_forward(vision_embs, None, input_ids=input_ids, attention_mask=attention_mask, labels=labels)
+            g_final = lw.lm_loss_backward(out.state)
+            B, L = out.state.B, out.state.L
+            g_h0 = self.lbw.run(g_final)
+            if self.qbw is not None:
+                self.qbw.run(g_h0, B, L)
+                cur = torch.cuda.current_stream()
+                for ls in (self.bw._leaf_streams or []):  # the Q-Former's weight gradients are leaf work on side streams
+                    cur.wait_stream(ls)
+        self.last = out
+        return out.loss
+
+    def optimizer_step(self):
+        m = self.model
+        with torch.no_grad():
+            norm = None
+            if self.max_grad_norm is not None:
+                norm = self.clip_grad_norm_(self.max_grad_norm)
+            self.step_count += 1
+            ops.adamw_gated(self.book.params, self.book.grads, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                            self.wd, self.last.loss.reshape(1), self._ctl, grad_scale=1.0, grad_norm=norm)
+            m.mllm.llama_wrapper.refresh_lora(self._lora_stacked)
+            if self.train_mllm_front:
+                m.mllm.qformer._invalidate()
+                m.mllm._invalidate()
+
+    def step(self, vision_embs, input_ids, attention_mask, labels):
+        loss = self.forward_backward(vision_embs, input_ids, attention_mask, labels)
+        self.optimizer_step()
+        return loss
+
+    def optimizer_counters(self):
+        """(applied, skipped) updates of the gated optimizer (one host sync)."""
+        c = self._ctl.tolist()
+        return c[0], c[1]
+
+    def check_flags(self):
+        """Raise on bad input ids, masks, labels or a 16-bit overflow seen since the last check (one host sync)."""
+        self.model.mllm.check_flags()
