@@ -517,6 +517,18 @@ int tcavt_attn_bwd_resident_ok(int T, int nq, int nkv);
 int tcavt_attn_bwd_resident(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16,
                             float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T,
                             int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream);
+/* The same backward for longer sequences, in chunks of 256 (tcavt_attn_bwd_long_ok: 256 < T <= 544, 16 % (nq / nkv) == 0 --
+   where the dispatch takes it; the entry point itself computes any 1 <= T <= 544, so that it can be cross-checked against
+   the resident form).  Arguments, outputs and `stats` exactly as tcavt_attn_bwd_resident.  dQ: a workgroup per (sample,
+   key/value head, query chunk) walks the key chunks up to its own with the dQ accumulators in registers; dK, dV: a workgroup
+   per (sample, key/value head, key chunk) walks the query heads of the group and the query chunks from its own upward.  One
+   chunk's LDS image per workgroup (107 KB / 140 KB), no fp32 gradient buffer, no atomics: two launches on the same inputs
+   give the same bits.  TCAVT_ERR_ARG before any launch on T > 544, head_dim != 64, an unsupported group, a null or
+   misaligned pointer. */
+int tcavt_attn_bwd_long_ok(int T, int nq, int nkv);
+int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16, float* stats,
+                        const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T, int nq, int nkv,
+                        int head_dim, float scale, int dtype16, tcavt_stream_t stream);
 /* dK, dV of the attention backward, key-major on the matrix cores (one workgroup per sample, key/value head and 64 keys;
    P^T, dS^T rebuilt from `stats`, the query heads of the group summed in registers): writes the k and v columns of
    g32 [B*T, (nq+2nkv)*64] fp32 (every row; no zero-initialisation needed) */
@@ -693,11 +705,12 @@ int tcavt_llama_stack_forward(const tcavt_llama_stack_args* args, tcavt_stream_t
  * adapters' .grad, and -- input_grad -- the decoder's input embeddings).  Per layer, last to first:
  *   dgrad of down_proj with d(silu(gate) * up) in its epilogue (TCAVT_EPI_SILU_BWD, in place on the taped pre-activations)
  *   -> dgrad of gate|up -> RMSNorm backward (post-attention norm; accumulates into the fp32 residual gradient g_h)
- *   -> dgrad of o_proj -> attention backward (tcavt_attn_bwd_resident) -> g_t = s * g_qkv . B_ext
+ *   -> dgrad of o_proj -> attention backward (tcavt_attn_bwd_resident at L <= 256, tcavt_attn_bwd_long at 256 < L <= 544)
+ *   -> g_t = s * g_qkv . B_ext
  *   -> [leaf stream] adapter weight gradients (tcavt_lora_wgrad_a, row-scaled tcavt_wgrad_tn), written into the caller's
  *      gradient tensors times scale[1]
  *   -> adapters' input gradient (tcavt_lora_dgrad) -> dgrad of q|k|v -> RMSNorm backward (input norm).
- * Requires the forward's tape with 16-bit streams, tape_att / tape_lse / tape_part (tcavt_llama_layer), L <= 256,
+ * Requires the forward's tape with 16-bit streams, tape_att / tape_lse / tape_part (tcavt_llama_layer), L <= 544,
  * 16 % (nq / nkv) == 0, M % 256 == 0, I % 256 == 0, H % 128 == 0, adapters of rank <= 16, head_dim 64.  dtype16 must be
  * TCAVT_F16 (16-bit stream tapes exist for fp16 storage only; anything else is refused): the incoming gradients g_final_a / b
  * are bf16 and the walk runs under the power-of-two scale picked here (tcavt_grad_scale_pick into scale[0..1]).  Every layer's

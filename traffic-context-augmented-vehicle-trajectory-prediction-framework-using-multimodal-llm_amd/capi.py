@@ -286,6 +286,9 @@ _SIGNATURES = {
     "tcavt_attn_bwd_resident_ok": [c_int, c_int, c_int],
     "tcavt_attn_bwd_resident": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    "tcavt_attn_bwd_long_ok": [c_int, c_int, c_int],
+    "tcavt_attn_bwd_long": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                            c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "tcavt_attn_bwd_dkv": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                            c_int, c_void_p],
     "tcavt_gqa_rope_bwd_pack": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],

@@ -1190,6 +1190,304 @@ __global__ __launch_bounds__(1024) void attn_bwd_dkv_res_kernel(const bf16_t* __
     }
 }
 
+// ---------------------------------------------------------------------------
+// The two resident kernels above in chunks of 256, for 256 < T <= 544 (tcavt_attn_bwd_long; any T <= 544 is computed
+// correctly).  The LDS images are those of ONE chunk, so a workgroup stays below 160 KB whatever T is.
+//
+// dQ: a workgroup owns (sample, key/value head, chunk of QC queries) and walks the key chunks 0 .. its own; K, V and K^T
+// of a key chunk are staged behind a barrier pair (107 KB).  A wave keeps the dQ accumulators of its U (query head, strip)
+// units in registers across the key chunks; q, dO, lse and dO . O of a unit are re-read per chunk (L2 hits) so that only the
+// accumulators stay live.  U = min(group, 2) and QC = 256 U / group: 16 U units of 16 queries per workgroup, U per wave,
+// whatever the group is (group 4 -> chunks of 128 queries, group 8 -> 64, group 16 -> 32; U = 4 at group 4 needed more
+// than the 128 registers a wave of a 1024-thread workgroup has and spilled).  Strips are dealt in (short, long) pairs of
+// the chunk as in the resident kernel: on the diagonal key chunk every wave sees the same number of keys.
+// Workgroups of the LAST query chunks (most key chunks) come first in the grid.
+// ---------------------------------------------------------------------------
+constexpr int ABL_CHUNK = 256;
+constexpr int ABL_KTS = ABL_CHUNK + 4;
+constexpr int ABL_MAX_T = 544;
+
+template <bool F16, int U>
+__global__ __launch_bounds__(ABQ_WAVES * 64) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
+                                                                          const bf16_t* __restrict__ att, const float* __restrict__ lse,
+                                                                          float* __restrict__ stats, const int* __restrict__ kv_len,
+                                                                          int T, int nq, int nkv, int nqc, int nbj, float scale,
+                                                                          bf16_t* __restrict__ g16, const float* __restrict__ cosT,
+                                                                          const float* __restrict__ sinT) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);  // [256][72]
+  bf16_t* Vs = Ks + ABL_CHUNK * 72;              // [256][72]
+  bf16_t* KT = Vs + ABL_CHUNK * 72;              // [64][260]
+  const int group = nq / nkv;
+  const int QC = ABL_CHUNK * U / group, nS = QC >> 4, NG = ABQ_WAVES / group;
+  const int bj = blockIdx.x % nbj, qc = nqc - 1 - blockIdx.x / nbj;
+  const int b = bj / nkv, j = bj % nkv;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const long nqkv = (long)(nq + 2 * nkv) * 64;
+  const long row0 = (long)b * T;
+  const int klen = min(kv_len[b], T);
+  const int q_lo = qc * QC, q_hi = min(T, q_lo + QC);
+  const int nkeys_wg = min(q_hi, klen);  // keys any query of this chunk attends
+  const int h = j * group + wave % group;
+  const int g0w = wave / group;
+  const float c2 = scale * 1.4426950408889634f;
+  f32x4 dq[U][4];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dq[u][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bf16_t* kbase = qkv + (nq + j) * 64;
+  const bf16_t* vbase = qkv + (nq + nkv + j) * 64;
+  for (int c = 0; c == 0 || c * ABL_CHUNK < nkeys_wg; ++c) {  // (uniform; chunk 0 always: it writes stats)
+    const int kb0 = c * ABL_CHUNK;
+    if (c > 0) __syncthreads();  // everyone is done with the previous chunk
+    {
+      // thread (key pair kp, 16-byte chunk ch): local rows 2 kp, 2 kp + 1; rows >= T as zeros (their loads clamped)
+      const int nrow = max(0, min(ABL_CHUNK, (nkeys_wg - kb0 + 31) & ~31));
+      const u32x4 zero4 = {0u, 0u, 0u, 0u};
+      for (int idx = threadIdx.x; idx < (nrow >> 1) * 8; idx += ABQ_WAVES * 64) {
+        const int kp = idx >> 3, ch = idx & 7;
+        const int r0 = 2 * kp, r1 = r0 + 1;
+        const long g0 = (row0 + min(kb0 + r0, T - 1)) * nqkv + ch * 8, g1 = (row0 + min(kb0 + r1, T - 1)) * nqkv + ch * 8;
+        u32x4 ka = *reinterpret_cast<const u32x4*>(kbase + g0), kb = *reinterpret_cast<const u32x4*>(kbase + g1);
+        u32x4 va = *reinterpret_cast<const u32x4*>(vbase + g0), vb = *reinterpret_cast<const u32x4*>(vbase + g1);
+        if (kb0 + r0 >= T) { ka = zero4; va = zero4; }
+        if (kb0 + r1 >= T) { kb = zero4; vb = zero4; }
+        *reinterpret_cast<u32x4*>(Ks + r0 * 72 + ch * 8) = ka;
+        *reinterpret_cast<u32x4*>(Ks + r1 * 72 + ch * 8) = kb;
+        *reinterpret_cast<u32x4*>(Vs + r0 * 72 + ch * 8) = va;
+        *reinterpret_cast<u32x4*>(Vs + r1 * 72 + ch * 8) = vb;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {  // two keys of one dimension per dword
+          *reinterpret_cast<unsigned int*>(KT + (ch * 8 + 2 * e) * ABL_KTS + r0) = (ka[e] & 0xffffu) | (kb[e] << 16);
+          *reinterpret_cast<unsigned int*>(KT + (ch * 8 + 2 * e + 1) * ABL_KTS + r0) = (ka[e] >> 16) | (kb[e] & 0xffff0000u);
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int pr = g0w + NG * (u >> 1);
+      const int strip = U == 1 ? g0w : (u & 1) ? nS - 1 - pr : pr;
+      const int s0 = q_lo + strip * 16;  // first query of the unit
+      if (s0 >= T) continue;             // (uniform)
+      const int nkl = min(ABL_CHUNK, min(s0 + 16, klen) - kb0);  // keys of this chunk any query of the strip attends
+      if (c > 0 && nkl <= 0) continue;                           // (uniform)
+      const int qi = s0 + l15;  // this lane's query (B-fragment column / D column)
+      const long ar = row0 + min(qi, T - 1);
+      bf16x8 qf[2], gf[2];
+      float delta = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        qf[kk] = *reinterpret_cast<const bf16x8*>(qkv + ar * nqkv + h * 64 + kk * 32 + l4 * 8);
+        gf[kk] = *reinterpret_cast<const bf16x8*>(dO + ar * (long)(nq * 64) + h * 64 + kk * 32 + l4 * 8);
+        const u32x4 ov = *reinterpret_cast<const u32x4*>(att + ar * (long)(nq * 64) + h * 64 + kk * 32 + l4 * 8);
+        const u32x4 gv = __builtin_bit_cast(u32x4, gf[kk]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          delta = fmaf(from16_lo<F16>(ov[e]), from16_lo<F16>(gv[e]), delta);
+          delta = fmaf(from16_hi<F16>(ov[e]), from16_hi<F16>(gv[e]), delta);
+        }
+      }
+      delta += __shfl_xor(delta, 16, 64);
+      delta += __shfl_xor(delta, 32, 64);
+      const long srow = ((long)b * nq + h) * T + min(qi, T - 1);
+      const float l_nat = lse[srow];
+      const float l2 = l_nat * 1.4426950408889634f;
+      const int nv = qi < T ? min(qi + 1, klen) : 0;
+      if (c == 0 && l4 == 0 && qi < T) *reinterpret_cast<f32x4*>(stats + srow * 4) = f32x4{l_nat, 1.f, delta, 0.f};
+      for (int k0 = 0; k0 < nkl; k0 += 32) {
+        f32x4 sa[2], da[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
+          const int krow = k0 + t * 16 + l15;
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + krow * 72 + kk * 32 + l4 * 8);
+            const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + krow * 72 + kk * 32 + l4 * 8);
+            sacc = mfma16b<F16>(kf, qf[kk], sacc);
+            dacc = mfma16b<F16>(vf, gf[kk], dacc);
+          }
+          sa[t] = sacc;
+          da[t] = dacc;
+        }
+        u32x4 af;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          float ds[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int key = kb0 + k0 + t * 16 + 4 * l4 + e;
+            const float pv = key < nv ? __builtin_amdgcn_exp2f(fmaf(sa[t][e], c2, -l2)) : 0.f;
+            ds[e] = scale * pv * (da[t][e] - delta);
+          }
+          af[2 * t] = pack16x2<F16>(ds[0], ds[1]);
+          af[2 * t + 1] = pack16x2<F16>(ds[2], ds[3]);
+        }
+        const bf16x8 afr = __builtin_bit_cast(bf16x8, af);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const bf16_t* kt = KT + (dt * 16 + l15) * ABL_KTS + k0 + 4 * l4;
+          const u32x2 b0 = *reinterpret_cast<const u32x2*>(kt), b1 = *reinterpret_cast<const u32x2*>(kt + 16);
+          const u32x4 bv = {b0[0], b0[1], b1[0], b1[1]};
+          dq[u][dt] = mfma16b<F16>(afr, __builtin_bit_cast(bf16x8, bv), dq[u][dt]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int pr = g0w + NG * (u >> 1);
+    const int strip = U == 1 ? g0w : (u & 1) ? nS - 1 - pr : pr;
+    const int s0 = q_lo + strip * 16;
+    if (s0 < T) store_grad16<F16>(dq[u], g16, nqkv, row0, s0, T, h * 64, true, cosT, sinT, lane);
+  }
+}
+
+// dK, dV: a workgroup owns (sample, key/value head, chunk of 256 keys), sixteen waves of 16 keys (K / V rows in registers,
+// dK / dV accumulators in registers for the whole kernel, as in attn_bwd_dkv_res_kernel) and walks the query heads of the
+// group and, per head, the query chunks from its own upward; q, dO, their transposes and the row statistics of a query
+// chunk are staged behind a barrier pair (140 KB).  Workgroups of key chunk 0 (most query chunks) come first in the grid;
+// a chunk that starts at or beyond kv_len writes its zeros and leaves.
+template <bool F16>
+__global__ __launch_bounds__(1024) void attn_bwd_dkv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
+                                                                 const float* __restrict__ stats, const int* __restrict__ kv_len,
+                                                                 int T, int nq, int nkv, int nbj, float scale,
+                                                                 bf16_t* __restrict__ g16, const float* __restrict__ cosT,
+                                                                 const float* __restrict__ sinT) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* Qs = reinterpret_cast<bf16_t*>(smem);  // [256][72]
+  bf16_t* Gs = Qs + ABL_CHUNK * 72;              // [256][72]
+  bf16_t* QT = Gs + ABL_CHUNK * 72;              // [64][260]
+  bf16_t* GT = QT + 64 * ABL_KTS;                // [64][260]
+  float* st = reinterpret_cast<float*>(GT + 64 * ABL_KTS);  // [3][256]: lse * log2(e), 1 / sum, dO . O
+  const int Tp = (T + 63) & ~63;
+  const int grp = nq / nkv;
+  const int bj = blockIdx.x % nbj, kc = blockIdx.x / nbj;
+  const int b = bj / nkv, j = bj % nkv;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const long nqkv = (long)(nq + 2 * nkv) * 64;
+  const long row0 = (long)b * T;
+  const int klen = min(kv_len[b], T);
+  // key strip of this wave: (s, 7 - s, 8 + s, 15 - s) for the four waves of SIMD s -- equal numbers of query tiles per SIMD
+  const int sd = wave & 3, rr = wave >> 2;
+  const int strip = rr == 0 ? sd : rr == 1 ? 7 - sd : rr == 2 ? 8 + sd : 15 - sd;
+  const int kl0 = strip * 16, key0 = kc * ABL_CHUNK + kl0;
+  const bool active = key0 < T;            // (uniform) this wave has rows to write
+  const bool work = key0 < klen;           // (uniform) ... and they are not all zero
+  bf16x8 kf[2], vf[2];
+  {
+    const long ar = row0 + min(key0 + l15, T - 1);  // keys >= T: clamped load; masked (>= klen)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      kf[kk] = *reinterpret_cast<const bf16x8*>(qkv + ar * nqkv + (nq + j) * 64 + kk * 32 + l4 * 8);
+      vf[kk] = *reinterpret_cast<const bf16x8*>(qkv + ar * nqkv + (nq + nkv + j) * 64 + kk * 32 + l4 * 8);
+    }
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int qp = threadIdx.x >> 3, ch = threadIdx.x & 7;  // staging: query pair qp, 16-byte chunk ch
+  const float c2 = scale * 1.4426950408889634f;
+  const int nqc = kc * ABL_CHUNK < klen ? (Tp + ABL_CHUNK - 1) / ABL_CHUNK : kc;  // (uniform; no key < kv_len: no walk)
+  bool first = true;
+  for (int hh = 0; hh < grp; ++hh) {
+    const int h = j * grp + hh;
+    for (int qcx = kc; qcx < nqc; ++qcx) {
+      const int qb0 = qcx * ABL_CHUNK;
+      const int nrow = min(ABL_CHUNK, Tp - qb0);  // (a multiple of 64)
+      if (!first) __syncthreads();                // everyone is done with the previous blocks
+      first = false;
+      if ((int)threadIdx.x < (nrow >> 1) * 8) {
+        const int r0 = 2 * qp, r1 = r0 + 1;
+        const long g0 = row0 + min(qb0 + r0, T - 1), g1 = row0 + min(qb0 + r1, T - 1);
+        u32x4 qa = *reinterpret_cast<const u32x4*>(qkv + g0 * nqkv + h * 64 + ch * 8);
+        u32x4 qb = *reinterpret_cast<const u32x4*>(qkv + g1 * nqkv + h * 64 + ch * 8);
+        u32x4 ga = *reinterpret_cast<const u32x4*>(dO + g0 * (long)(nq * 64) + h * 64 + ch * 8);
+        u32x4 gb = *reinterpret_cast<const u32x4*>(dO + g1 * (long)(nq * 64) + h * 64 + ch * 8);
+        const u32x4 zero4 = {0u, 0u, 0u, 0u};
+        if (qb0 + r0 >= T) { qa = zero4; ga = zero4; }
+        if (qb0 + r1 >= T) { qb = zero4; gb = zero4; }
+        *reinterpret_cast<u32x4*>(Qs + r0 * 72 + ch * 8) = qa;
+        *reinterpret_cast<u32x4*>(Qs + r1 * 72 + ch * 8) = qb;
+        *reinterpret_cast<u32x4*>(Gs + r0 * 72 + ch * 8) = ga;
+        *reinterpret_cast<u32x4*>(Gs + r1 * 72 + ch * 8) = gb;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          *reinterpret_cast<unsigned int*>(QT + (ch * 8 + 2 * e) * ABL_KTS + r0) = (qa[e] & 0xffffu) | (qb[e] << 16);
+          *reinterpret_cast<unsigned int*>(QT + (ch * 8 + 2 * e + 1) * ABL_KTS + r0) = (qa[e] >> 16) | (qb[e] & 0xffff0000u);
+          *reinterpret_cast<unsigned int*>(GT + (ch * 8 + 2 * e) * ABL_KTS + r0) = (ga[e] & 0xffffu) | (gb[e] << 16);
+          *reinterpret_cast<unsigned int*>(GT + (ch * 8 + 2 * e + 1) * ABL_KTS + r0) = (ga[e] >> 16) | (gb[e] & 0xffff0000u);
+        }
+      }
+      if ((int)threadIdx.x < nrow) {
+        const int il = threadIdx.x, i = qb0 + il;
+        f32x4 sv = {0.f, 0.f, 0.f, 0.f};
+        if (i < T) sv = *reinterpret_cast<const f32x4*>(stats + (((long)b * nq + h) * T + i) * 4);
+        st[il] = sv[0] * 1.4426950408889634f;
+        st[ABL_CHUNK + il] = i < T ? sv[1] : 0.f;  // (queries >= T: P = 0)
+        st[2 * ABL_CHUNK + il] = sv[2];
+      }
+      __syncthreads();
+      if (!work) continue;
+      // queries at or below the diagonal of this wave's keys: the whole chunk when it lies below the key chunk
+      for (int q0 = qcx == kc ? (kl0 & ~31) : 0; q0 < nrow; q0 += 32) {
+        f32x4 sa[2], da[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
+          const int qrow = q0 + t * 16 + l15;
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            const bf16x8 qf = *reinterpret_cast<const bf16x8*>(Qs + qrow * 72 + kk * 32 + l4 * 8);
+            const bf16x8 gf = *reinterpret_cast<const bf16x8*>(Gs + qrow * 72 + kk * 32 + l4 * 8);
+            sacc = mfma16b<F16>(qf, kf[kk], sacc);
+            dacc = mfma16b<F16>(gf, vf[kk], dacc);
+          }
+          sa[t] = sacc;
+          da[t] = dacc;
+        }
+        u32x4 pfr, dfr;
+        const int key = key0 + l15;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int ql = q0 + t * 16 + 4 * l4, qi = qb0 + ql;
+          const f32x4 m2 = *reinterpret_cast<const f32x4*>(st + ql), iv = *reinterpret_cast<const f32x4*>(st + ABL_CHUNK + ql),
+                      dt_ = *reinterpret_cast<const f32x4*>(st + 2 * ABL_CHUNK + ql);
+          float pv[4], ds[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool ok = key <= qi + e && key < klen;  // (queries >= T have 1 / sum = 0)
+            pv[e] = ok ? __builtin_amdgcn_exp2f(fmaf(sa[t][e], c2, -m2[e])) * iv[e] : 0.f;
+            ds[e] = scale * pv[e] * (da[t][e] - dt_[e]);
+          }
+          pfr[2 * t] = pack16x2<F16>(pv[0], pv[1]);
+          pfr[2 * t + 1] = pack16x2<F16>(pv[2], pv[3]);
+          dfr[2 * t] = pack16x2<F16>(ds[0], ds[1]);
+          dfr[2 * t + 1] = pack16x2<F16>(ds[2], ds[3]);
+        }
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, pfr), df = __builtin_bit_cast(bf16x8, dfr);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const bf16_t* gt = GT + (dt * 16 + l15) * ABL_KTS + q0 + 4 * l4;
+          const bf16_t* qt = QT + (dt * 16 + l15) * ABL_KTS + q0 + 4 * l4;
+          const u32x2 g0 = *reinterpret_cast<const u32x2*>(gt), g1 = *reinterpret_cast<const u32x2*>(gt + 16);
+          const u32x2 q0v = *reinterpret_cast<const u32x2*>(qt), q1v = *reinterpret_cast<const u32x2*>(qt + 16);
+          const u32x4 gv = {g0[0], g0[1], g1[0], g1[1]}, qv = {q0v[0], q0v[1], q1v[0], q1v[1]};
+          dv[dt] = mfma16b<F16>(pf, __builtin_bit_cast(bf16x8, gv), dv[dt]);
+          dk[dt] = mfma16b<F16>(df, __builtin_bit_cast(bf16x8, qv), dk[dt]);
+        }
+      }
+    }
+  }
+  if (!active) return;
+  store_grad16<F16>(dk, g16, nqkv, row0, key0, T, (nq + j) * 64, true, cosT, sinT, lane);
+  store_grad16<F16>(dv, g16, nqkv, row0, key0, T, (nq + nkv + j) * 64, false, cosT, sinT, lane);
+}
+
 // G3 fp32 [M, 3 * nq * 64] = dQ | dK per QUERY head | dV per QUERY head  ->  bf16 [M, (nq + 2 nkv) * 64]: the query heads of
 // a group are summed into their key / value head, q and k get the transposed RoPE rotation (rope_bwd_pack_kernel).
 __global__ __launch_bounds__(256) void gqa_rope_bwd_pack_kernel(const float* __restrict__ G3, bf16_t* __restrict__ out,
@@ -1815,6 +2113,57 @@ extern "C" int tcavt_attn_bwd_resident_ok(int T, int nq, int nkv) {
   return T > 0 && T <= 256 && nkv > 0 && nq % nkv == 0 && ABQ_WAVES % (nq / nkv) == 0;
 }
 
+// The same backward in chunks of 256 keys / queries (attn_bwd_dq_long_kernel, attn_bwd_dkv_long_kernel): any T <= 544
+extern "C" int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16,
+                                   float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T,
+                                   int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(qkv16 && dO16 && att16 && lse && g_qkv16 && stats && rope_cos && rope_sin && kv_len && B > 0 && T > 0 && is16(dtype16),
+                  "attn_bwd_long: bad args");
+  TCAVT_CHECK_ARG(head_dim == 64 && nkv > 0 && nq > 0 && nq % nkv == 0, "attn_bwd_long: head_dim 64 and nq %% nkv == 0 required");
+  TCAVT_CHECK_ARG(T <= ABL_MAX_T && ABQ_WAVES % (nq / nkv) == 0,
+                  "attn_bwd_long: T=%d, nq / nkv = %d outside the chunked form (T <= %d, 16 %% (nq / nkv) == 0)", T, nq / nkv, ABL_MAX_T);
+  TCAVT_CHECK_ARG(aligned16(qkv16) && aligned16(dO16) && aligned16(att16) && aligned16(stats) && aligned16(g_qkv16),
+                  "attn_bwd_long: 16-byte alignment required");
+  const bool f16 = dtype16 == TCAVT_F16;
+  const int group = nq / nkv, U = group < 2 ? group : 2;
+  typedef void (*dq_fn)(const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, const int*, int, int, int, int, int, float,
+                        bf16_t*, const float*, const float*);
+  static const dq_fn kqs[2][2] = {{attn_bwd_dq_long_kernel<false, 1>, attn_bwd_dq_long_kernel<false, 2>},
+                                  {attn_bwd_dq_long_kernel<true, 1>, attn_bwd_dq_long_kernel<true, 2>}};
+  const int ui = U - 1;
+  const dq_fn kq = kqs[f16][ui];
+  auto kr = f16 ? attn_bwd_dkv_long_kernel<true> : attn_bwd_dkv_long_kernel<false>;
+  const int lds_q = (2 * ABL_CHUNK * 72 + 64 * ABL_KTS) * 2;                       // 107,008 B
+  const int lds_kv = (2 * ABL_CHUNK * 72 + 2 * 64 * ABL_KTS) * 2 + 3 * ABL_CHUNK * 4;  // 143,360 B
+  static bool attr_set[2][2] = {{false, false}, {false, false}};
+  if (!attr_set[f16][ui]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
+    if (e != hipSuccess) {
+      tcavt::set_error("attn_bwd_long: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      return TCAVT_ERR_HIP;
+    }
+    attr_set[f16][ui] = true;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bf16_t* q_ = static_cast<const bf16_t*>(qkv16);
+  const bf16_t* g_ = static_cast<const bf16_t*>(dO16);
+  const int QC = ABL_CHUNK * U / group;
+  const int nqc = (T + QC - 1) / QC, nkc = (T + ABL_CHUNK - 1) / ABL_CHUNK, nbj = B * nkv;
+  hipLaunchKernelGGL(kq, dim3((unsigned)(nbj * nqc)), dim3(ABQ_WAVES * 64), lds_q, st, q_, g_, static_cast<const bf16_t*>(att16), lse,
+                     stats, kv_len, T, nq, nkv, nqc, nbj, scale, static_cast<bf16_t*>(g_qkv16), rope_cos, rope_sin);
+  TCAVT_CHECK_LAUNCH("attn_bwd_long(dq)");
+  hipLaunchKernelGGL(kr, dim3((unsigned)(nbj * nkc)), dim3(1024), lds_kv, st, q_, g_, static_cast<const float*>(stats), kv_len, T, nq,
+                     nkv, nbj, scale, static_cast<bf16_t*>(g_qkv16), rope_cos, rope_sin);
+  TCAVT_CHECK_LAUNCH("attn_bwd_long(dkv)");
+  return TCAVT_OK;
+}
+
+// where the dispatch (llm_backward.attn_bwd_composed, tcavt_llama_stack_backward) takes the chunked form
+extern "C" int tcavt_attn_bwd_long_ok(int T, int nq, int nkv) {
+  return T > 256 && T <= ABL_MAX_T && nkv > 0 && nq > 0 && nq % nkv == 0 && ABQ_WAVES % (nq / nkv) == 0;
+}
+
 #define TCAVT_TRY(call)            \
   do {                             \
     const int rc_ = (call);        \
@@ -1833,8 +2182,9 @@ extern "C" int tcavt_llama_stack_backward(const tcavt_llama_backward_args* a, tc
   // streams, whose backward is the per-launch composition of llm_backward.py); head_dim 64, adapters in 16-column groups
   TCAVT_CHECK_ARG(dt == TCAVT_F16, "llama_stack_backward: dtype16 must be TCAVT_F16 (16-bit stream tapes exist for fp16 storage only)");
   const int M = B * L, nqkv = (nq + 2 * nkv) * 64;
-  TCAVT_CHECK_ARG(tcavt_attn_bwd_resident_ok(L, nq, nkv) && M % 256 == 0 && I % 256 == 0 && H % 128 == 0,
-                  "llama_stack_backward: outside the fused forms (L <= 256, 16 %% (nq / nkv) == 0, M %% 256 == 0, I %% 256 == 0, H %% 128 == 0)");
+  const bool att_long = !tcavt_attn_bwd_resident_ok(L, nq, nkv);  // 256 < L <= 544: the chunked attention backward
+  TCAVT_CHECK_ARG((!att_long || tcavt_attn_bwd_long_ok(L, nq, nkv)) && M % 256 == 0 && I % 256 == 0 && H % 128 == 0,
+                  "llama_stack_backward: outside the fused forms (L <= 544, 16 %% (nq / nkv) == 0, M %% 256 == 0, I %% 256 == 0, H %% 128 == 0)");
   TCAVT_CHECK_ARG(!a->leaf_stream || a->events, "llama_stack_backward: a leaf stream needs the four events");
   // every layer's pointers are checked BEFORE anything is launched: an argument error must not leave half a walk enqueued
   // (adapter gradients half-written, the leaf stream forked and never joined -- under a hipGraph capture an unjoined stream)
@@ -1889,8 +2239,8 @@ extern "C" int tcavt_llama_stack_backward(const tcavt_llama_backward_args* a, tc
     const int par = li & 1;
     if (two && leaf_used[par])  // the leaf of layer li + 2 has read g_qkv / g_t of this parity
       TCAVT_TRY(hip_ok(hipStreamWaitEvent(st, static_cast<hipEvent_t>(a->events[2 + par]), 0), "wait(done)"));
-    TCAVT_TRY(tcavt_attn_bwd_resident(w.qkv, a->g_att, w.att, w.lse, g_qkv2[par], a->stats, a->rope_cos, a->rope_sin, a->kv_len, B, L,
-                                      nq, nkv, 64, 0.125f, dt, stream));
+    TCAVT_TRY((att_long ? tcavt_attn_bwd_long : tcavt_attn_bwd_resident)(w.qkv, a->g_att, w.att, w.lse, g_qkv2[par], a->stats, a->rope_cos,
+                                                                         a->rope_sin, a->kv_len, B, L, nq, nkv, 64, 0.125f, dt, stream));
     TCAVT_TRY(gemm(g_qkv2[par], nqkv, w.b_extT, nqkv, g_t2[par], 64, a->lora_scale));
     // ---- leaf: the adapters' weight gradients (nothing downstream reads them)
     if (two) {

@@ -234,11 +234,29 @@ class MultiModalTrajectoryDataset(torch.utils.data.Dataset):
         return out
 
 
-def custom_collate_fn(batch):
+def custom_collate_fn(batch, pad_to_multiple_of=None):
     """train.py:301-347: (B,2,T) trajectories, stacked vision/polygons, right-padded ids (0), mask (0),
-    labels (-100); python lists for lengths / norm_stat / strings."""
+    labels (-100); python lists for lengths / norm_stat / strings.
+
+    pad_to_multiple_of=m (an integer; None, the default, is the reference's collate unchanged): the text is padded on to the
+    next multiple of m with the same pad values, so that B * L meets the GEMM forms of the one-call decoder backward on
+    ragged data (B = 32, m = 8: B * L a multiple of 256).  The extra padded rows feed the head's unmasked cross-attention
+    like every padded row does, so results differ from the unpadded batch -- as any padding does in the reference."""
     from torch.nn.utils.rnn import pad_sequence
 
+    out = _collate(batch, pad_sequence)
+    if pad_to_multiple_of is not None:
+        m = int(pad_to_multiple_of)
+        if m <= 0:
+            raise ValueError("custom_collate_fn: pad_to_multiple_of must be a positive integer or None")
+        extra = -out["input_ids"].shape[1] % m
+        if extra:
+            for k, v in (("input_ids", 0), ("attention_mask", 0), ("labels", -100)):
+                out[k] = torch.nn.functional.pad(out[k], (0, extra), value=v)
+    return out
+
+
+def _collate(batch, pad_sequence):
     return {
         "traj_emb": torch.stack([b["traj_emb"].transpose(0, 1) for b in batch], dim=0),
         "target_traj": torch.stack([b["target_traj"].transpose(0, 1) for b in batch], dim=0),

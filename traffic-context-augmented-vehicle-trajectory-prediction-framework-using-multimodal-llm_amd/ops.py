@@ -709,20 +709,34 @@ def attn_bwd_resident_ok(T, nq, nkv):
 def attn_bwd_resident(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale):
     """The whole causal GQA attention backward in two launches (tcavt_attn_bwd_resident): g_qkv 16-bit [B*T, (nq+2nkv)*64]
     = gradient of the projections' outputs, RoPE undone; att / lse from attn_causal_gqa(..., lse=...)."""
+    return _attn_bwd_two_launch("attn_bwd_resident", qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
+
+
+def _attn_bwd_two_launch(name, qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale):
     ncols = (nq + 2 * nkv) * 64
     for t, n, nm in ((qkv, B * T * ncols, "qkv"), (dO, B * T * nq * 64, "dO"), (att, B * T * nq * 64, "att"),
                      (g_qkv, B * T * ncols, "g_qkv")):
         if t.dtype != qkv.dtype or t.dtype not in _H16 or not t.is_contiguous() or (not t.is_cuda and not _ALLOW_CPU):
-            raise capi.TcavtError(f"attn_bwd_resident.{nm}: contiguous 16-bit GPU tensor of the type of qkv required")
+            raise capi.TcavtError(f"{name}.{nm}: contiguous 16-bit GPU tensor of the type of qkv required")
         if _avail(t) < n:
-            raise capi.TcavtError(f"attn_bwd_resident.{nm}: buffer too small")
+            raise capi.TcavtError(f"{name}.{nm}: buffer too small")
     for t, n, nm in ((lse, B * nq * T, "lse"), (stats, B * nq * T * 4, "stats"), (cos, T * 32, "cos"), (sin, T * 32, "sin")):
-        _req(t, torch.float32, f"attn_bwd_resident.{nm}")
-        _need(t, n, f"attn_bwd_resident.{nm}")
-    _need(kv_len, B, "attn_bwd_resident.kv_len")
-    check(lib().tcavt_attn_bwd_resident(ptr(qkv), ptr(dO), ptr(att), ptr(lse), ptr(g_qkv), ptr(stats), ptr(cos), ptr(sin),
-                                        ptr(kv_len), B, T, nq, nkv, 64, scale, _DT16(qkv), stream_ptr()), "tcavt_attn_bwd_resident")
+        _req(t, torch.float32, f"{name}.{nm}")
+        _need(t, n, f"{name}.{nm}")
+    _need(kv_len, B, f"{name}.kv_len")
+    check(getattr(lib(), "tcavt_" + name)(ptr(qkv), ptr(dO), ptr(att), ptr(lse), ptr(g_qkv), ptr(stats), ptr(cos), ptr(sin),
+                                          ptr(kv_len), B, T, nq, nkv, 64, scale, _DT16(qkv), stream_ptr()), "tcavt_" + name)
     return g_qkv
+
+
+def attn_bwd_long_ok(T, nq, nkv):
+    """Shapes the dispatch hands to the chunked form of the attention backward (256 < T <= 544, 16 % (nq / nkv) == 0)."""
+    return bool(lib().tcavt_attn_bwd_long_ok(T, nq, nkv))
+
+
+def attn_bwd_long(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale):
+    """attn_bwd_resident in chunks of 256 keys / queries (tcavt_attn_bwd_long): same arguments and outputs, any T <= 544."""
+    return _attn_bwd_two_launch("attn_bwd_long", qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
 
 
 def gqa_rope_bwd_pack(G3, out, cos, sin, nq, nkv, L):
