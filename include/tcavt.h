@@ -1201,6 +1201,42 @@ int64_t tcavt_lm_loss_workspace_bytes(int64_t rows, int V, int H);
 int tcavt_lm_loss_forward(const tcavt_lm_loss_args* args, tcavt_stream_t stream);
 int tcavt_lm_loss_backward(const tcavt_lm_loss_args* args, tcavt_stream_t stream);
 
+/* Teacher-forced evaluation pass of the same fused kernel: everything tcavt_lm_loss_forward writes (loss, count, lse, row_loss:
+ * bit-identical to that call on the same inputs) plus the arg-max of every labelled row's logits, still without storing a logit.
+ * Row and label contract as above (shift, -100, Nq, kv_len; a bad label sets *flag and drops the row; V % 16 == 0,
+ * H % 256 == 0).  Per (row, 128-column tile) the kernel keeps the tile's arg-max column next to (max, sum exp), taken after the
+ * ragged-tile mask (a masked column is -inf and never wins); among equal values the lowest column wins, inside a tile and --
+ * the merge walks the tiles in order and only a strictly greater maximum replaces the winner -- across tiles.
+ *   pred[b * L + p]   = argmax_v z[v] in [0, V) on labelled rows, -1 on every other row
+ *   correct           = number of labelled rows with pred == target
+ *   sample_tokens[b]  = labelled rows of sample b;  sample_correct[b] = those with pred == target
+ *   sample_nll[b]     = sum of row_loss over sample b (fixed order, fp64 partial sums; 0 without labels)
+ * No float atomics, no host sync: two launches give identical bits in every output.  workspace:
+ * tcavt_lm_eval_workspace_bytes(B * L, V, H) bytes, 256-byte aligned: the row arrays and 12 bytes per (row rounded up to 256,
+ * tile) -- no P chunk, no [rows][H] accumulator (rows 8192, V 128256, H 2048: 94 MiB). */
+typedef struct tcavt_lm_eval_args {
+  const void* h16; int64_t ldh;       /* 16-bit [B * L][ldh] */
+  const void* table;                  /* 16-bit [V][H] */
+  const int64_t* labels;              /* [B][L - Nq] */
+  const int32_t* kv_len;              /* optional [B] */
+  int32_t B, L, V, H, Nq;
+  int32_t dtype16;                    /* TCAVT_F16 | TCAVT_BF16 */
+  float* loss;                        /* fp32 [1] */
+  int32_t* count;                     /* int32 [1] */
+  float* lse;                         /* fp32 [B * L] */
+  float* row_loss;                    /* optional fp32 [B * L] */
+  int32_t* flag;                      /* optional int32 [1]: bad-label flag */
+  int32_t* pred;                      /* int32 [B * L] */
+  int32_t* correct;                   /* optional int32 [1] */
+  int32_t* sample_tokens;             /* optional int32 [B] */
+  int32_t* sample_correct;            /* optional int32 [B] */
+  float* sample_nll;                  /* optional fp32 [B] */
+  void* workspace; int64_t workspace_bytes;
+} tcavt_lm_eval_args;
+
+int64_t tcavt_lm_eval_workspace_bytes(int64_t rows, int V, int H);
+int tcavt_lm_eval(const tcavt_lm_eval_args* args, tcavt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

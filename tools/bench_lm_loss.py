@@ -7,8 +7,11 @@ gradient to bf16 (the scaled gradient leaves fp16's normal range), ops.gemm_bf16
 Two label sets: tcavt_amd.synth's (full rows: 7680 labelled rows of 8192) and one with 1/8 of the rows labelled.
 Per set: time of each path (HIP events after a warm-up; median and spread over the repetitions), peak allocated memory of
 each path, model FLOP/s of the fused forward and backward over their own time (2 N V H and 4 N V H for N labelled rows).
---trainer adds the MllmTrainer step at the Llama-3.2-1B shape.  Usage:
+--trainer adds the MllmTrainer step at the Llama-3.2-1B shape.
+--eval runs the evaluation leg INSTEAD: ops.lm_eval (loss + arg-max + per-sample sums) and ops.lm_loss_forward alternate with
+the composed evaluation (ops.gemm_bf16 -> fp32 logits -> torch.argmax + cross-entropy); time and peak memory of each.  Usage:
     python tools/bench_lm_loss.py [--reps 10] [--warmup 3] [--trainer] [--out profiles/lm_loss.txt]
+    python tools/bench_lm_loss.py --eval [--out profiles/lm_eval.txt]
 """
 import argparse
 import os
@@ -133,6 +136,62 @@ def run_label_set(name, h16, table, table_t_bf16, labels, Nq, B, L, reps, warmup
     return {"N": N, "ms": ms}
 
 
+def composed_eval(h16, table, targets):
+    """-> (loss, pred [rows], correct) through the stored fp32 logits"""
+    from tcavt_amd import ops
+
+    logits = ops.gemm_bf16(h16, table, out_dtype=F32)
+    pred = logits.argmax(dim=1)
+    loss = torch.nn.functional.cross_entropy(logits, targets, ignore_index=-100)
+    return loss, pred, ((pred == targets) & (targets != -100)).sum()
+
+
+def run_eval(name, h16, table, labels, Nq, B, L, reps, warmup, log):
+    from tcavt_amd import ops
+
+    dev = h16.device
+    V, H = table.shape
+    fused = Fused(h16, table, labels, Nq, B, L)
+    targets = row_targets(labels, Nq)
+    N = int((targets != -100).sum())
+    ws = torch.empty(ops.lm_eval_workspace_bytes(B * L, V, H), dtype=torch.uint8, device=dev)
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    loss, count, correct, pred, lse = torch.empty(1, dtype=F32, device=dev), i32(1), i32(1), i32(B * L), torch.empty(B * L, dtype=F32, device=dev)
+    row_loss, nll, stok, scor = torch.empty(B * L, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev), i32(B), i32(B)
+
+    def ev():
+        return ops.lm_eval(h16, table, labels, Nq, B, L, loss=loss, count=count, lse=lse, pred=pred, workspace=ws, row_loss=row_loss,
+                           correct=correct, sample_tokens=stok, sample_correct=scor, sample_nll=nll)
+
+    for _ in range(warmup):
+        ev(), fused.forward(), composed_eval(h16, table, targets)
+    torch.cuda.synchronize()
+    evs = {"eval": [], "forward": [], "composed": []}
+    for _ in range(reps):  # alternate the paths inside one process
+        evs["eval"].append(_timed(ev)[:2])
+        evs["forward"].append(_timed(fused.forward)[:2])
+        evs["composed"].append(_timed(lambda: composed_eval(h16, table, targets))[:2])
+    torch.cuda.synchronize()
+    ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in evs.items()}
+    loss_c, pred_c, cor_c = composed_eval(h16, table, targets)
+    ev(), fused.forward()
+    torch.cuda.synchronize()
+    lab = targets != -100
+    agree = int((pred.long()[lab] == pred_c[lab]).sum())
+    peak_c = _peak(lambda: composed_eval(h16, table, targets))
+    peak_e = _peak(ev)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    log(f"--- eval, labels: {name}: {N} labelled rows of {B * L} (B {B}, L {L}, H {H}, V {V}, operands {str(h16.dtype)[6:]})")
+    log(f"tcavt_lm_eval            {_stats(ms['eval'])}   {2.0 * N * V * H / med['eval'] / 1e9:7.1f} model TFLOP/s")
+    log(f"tcavt_lm_loss_forward    {_stats(ms['forward'])}   {2.0 * N * V * H / med['forward'] / 1e9:7.1f} model TFLOP/s")
+    log(f"composed (fp32 logits)   {_stats(ms['composed'])}")
+    log(f"eval / forward time      {med['eval'] / med['forward']:.3f}     eval / composed time {med['eval'] / med['composed']:.3f}")
+    log(f"memory: eval workspace {ws.numel() / 2 ** 20:.1f} MiB (loss workspace {fused.ws.numel() / 2 ** 20:.1f} MiB; the call allocates "
+        f"{peak_e / 2 ** 20:.1f} MiB more); composed path peaks at {peak_c / 2 ** 20:.1f} MiB")
+    log(f"agreement: loss bits equal to the forward's: {bool(torch.equal(loss, fused.loss))}; loss vs composed rel "
+        f"{abs(float(loss) - float(loss_c)) / abs(float(loss_c)):.2e}; arg-max equal on {agree} of {N} rows; correct {int(correct)} vs {int(cor_c)}")
+
+
 def run_trainer(reps, warmup, log, B=32, text_len=240):
     from tcavt_amd import config, model, synth, training
     from tcavt_amd.weights import make_weights
@@ -163,6 +222,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trainer", action="store_true")
+    ap.add_argument("--eval", action="store_true", help="the evaluation leg: lm_eval against lm_loss_forward and the composed arg-max")
     ap.add_argument("--dtype", default="float16", choices=["float16", "bfloat16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -185,7 +245,13 @@ def main():
     h16 = torch.randn(B * L, H, generator=g, device=dev).to(dt)
     table_t_bf16 = table.t().contiguous().to(BF16)
     labels = torch.from_numpy(synth.make_batch(cfg, B, text_len=Lt, seed=100, ragged=False)["labels"]).to(dev)  # every text row labelled
-    log(f"tools/bench_lm_loss.py --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}")
+    log(f"tools/bench_lm_loss.py{' --eval' if a.eval else ''} --reps {a.reps} --warmup {a.warmup}: {torch.cuda.get_device_name(0)}")
+    if a.eval:
+        run_eval("synth", h16, table, labels, Nq, B, L, a.reps, a.warmup, log)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     run_label_set("synth", h16, table, table_t_bf16, labels, Nq, B, L, a.reps, a.warmup, log)
     sparse = labels.clone()
     keep = torch.zeros_like(sparse, dtype=torch.bool)

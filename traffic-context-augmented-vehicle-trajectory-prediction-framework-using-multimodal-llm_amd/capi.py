@@ -226,6 +226,15 @@ class LmLossArgs(ctypes.Structure):
         ("ldg", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
 
 
+class LmEvalArgs(ctypes.Structure):
+    """Mirror of ``tcavt_lm_eval_args`` (include/tcavt.h)."""
+
+    _fields_ = [("h16", c_void_p), ("ldh", c_int64), ("table", c_void_p), ("labels", c_void_p), ("kv_len", c_void_p)] + [
+        (n, ctypes.c_int32) for n in ("B", "L", "V", "H", "Nq", "dtype16")] + [(n, c_void_p) for n in (
+            "loss", "count", "lse", "row_loss", "flag", "pred", "correct", "sample_tokens", "sample_correct", "sample_nll")] + [
+        ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
 # name -> argtypes (return type is always int unless listed in _RESTYPES)
 _SIGNATURES = {
     "tcavt_abi_version": [],
@@ -343,9 +352,11 @@ _SIGNATURES = {
     "tcavt_lm_loss_workspace_bytes": [c_int64, c_int, c_int],
     "tcavt_lm_loss_forward": [ctypes.POINTER(LmLossArgs), c_void_p],
     "tcavt_lm_loss_backward": [ctypes.POINTER(LmLossArgs), c_void_p],
+    "tcavt_lm_eval_workspace_bytes": [c_int64, c_int, c_int],
+    "tcavt_lm_eval": [ctypes.POINTER(LmEvalArgs), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64,
-             "tcavt_lm_loss_workspace_bytes": c_int64}
+             "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -46,6 +46,29 @@ LmLayout lm_layout(long rows, int V, int H) {
   return l;
 }
 
+// the eval pass: the row arrays, the per-tile statistics and the per-tile arg-max (12 bytes per row and tile); no P chunk, no accumulator
+struct LmEvalLayout {
+  long rowidx, tgt, slot, zt, rowloss, scor, part, amax, total;
+  int mcap, ntiles;
+};
+
+LmEvalLayout lm_eval_layout(long rows, int V) {
+  LmEvalLayout l;
+  l.mcap = (int)align_up(rows, 256);
+  l.ntiles = (V + LM_TN - 1) / LM_TN;
+  long o = 0;
+  l.rowidx = o; o += align_up((long)l.mcap * 4, 256);
+  l.tgt = o; o += align_up((long)l.mcap * 4, 256);
+  l.slot = o; o += align_up((long)l.mcap * 4, 256);
+  l.zt = o; o += align_up((long)l.mcap * 4, 256);
+  l.rowloss = o; o += align_up((long)l.mcap * 4, 256);
+  l.scor = o; o += align_up((long)l.mcap * 4, 256);  // sample_correct when the caller passes none (B <= rows)
+  l.part = o; o += align_up((long)l.ntiles * l.mcap * 8, 256);
+  l.amax = o; o += align_up((long)l.ntiles * l.mcap * 4, 256);
+  l.total = o;
+  return l;
+}
+
 // ---- labelled-row selection: one workgroup, rows compacted in row order -------------------------------------------------------
 __global__ __launch_bounds__(1024) void lm_select_kernel(const int64_t* __restrict__ labels, const int32_t* __restrict__ kv_len, int B, int L,
                                                          int Nq, int V, int mcap, int* __restrict__ rowidx, int* __restrict__ tgt,
@@ -95,12 +118,14 @@ struct LogitsP {
   int v0;            // first vocabulary column of this launch (P mode: the chunk's)
   // stats mode
   float2* part; float* zt;
+  int* amax;         // MODE 2: [ntiles][mcap] arg-max column of the tile
   // P mode
   const float* lse;  // [B * L], by original row
   bf16_t* P; long ldp;
 };
 
 // MODE 0: per-(row, tile) softmax statistics + the target logit.  MODE 1: P = exp(z - lse) - onehot as 16-bit, chunk-local columns.
+// MODE 2: MODE 0 plus the tile's arg-max column (after the ragged-tile mask; among equal values the lowest column).
 // 4 waves; wave w owns rows 32 w .. 32 w + 31 and all 128 columns.  The table fragment is the MFMA's A operand, so a lane holds
 // 4 consecutive vocabulary columns of ONE row: D row (vocab) = 4 (lane >> 4) + reg, D column (row of h) = lane & 15.
 template <bool F16, int MODE>
@@ -185,8 +210,10 @@ __global__ __launch_bounds__(256) void lm_logits_kernel(LogitsP p) {
     const int r = m_base + 32 * w + 16 * i + fr;
     const bool live = r < n;
     const int t = p.tgt[r];  // -1 beyond the count
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == 0 || MODE == 2) {
       float mx = -INFINITY;
+      [[maybe_unused]] float bv = -INFINITY;  // MODE 2: greatest value so far and its column; columns are visited in rising order,
+      [[maybe_unused]] int bi = 0x7fffffff;     // so a strict > keeps the lowest column among equal values
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -194,10 +221,22 @@ __global__ __launch_bounds__(256) void lm_logits_kernel(LogitsP p) {
           const int v = vt + 16 * j + 4 * fq + e;
           if (v >= p.V) acc[i][j][e] = -INFINITY;  // ragged last tile: masked, never padded with zeros
           mx = fmaxf(mx, acc[i][j][e]);
+          if constexpr (MODE == 2) {
+            if (acc[i][j][e] > bv) { bv = acc[i][j][e]; bi = v; }
+          }
           if (live && v == t) p.zt[r] = acc[i][j][e];  // exactly one lane of one tile owns column t
         }
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      if constexpr (MODE == 2) {  // the index travels with the value: greater value first, lower column on equality
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+          const float ov = __shfl_xor(bv, o, 64);
+          const int oi = __shfl_xor(bi, o, 64);
+          if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (live && fq == 0) p.amax[(long)tile * p.mcap + r] = bi;
+      }
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j)
@@ -227,13 +266,25 @@ __global__ __launch_bounds__(256) void lm_logits_kernel(LogitsP p) {
 }
 
 // ---- merge of the per-tile statistics, in tile order ----------------------------------------------------------------------------
+// EVAL: also the row's arg-max -- that of the tile with the greatest maximum, the lowest tile among equal maxima.  The
+// (max, sum exp) arithmetic is the same code in both instantiations.
+template <bool EVAL>
 __global__ __launch_bounds__(256) void lm_merge_kernel(const float2* __restrict__ part, const float* __restrict__ zt, const int* __restrict__ rowidx,
                                                        const int* __restrict__ count, int ntiles, int mcap, float* __restrict__ lse,
-                                                       float* __restrict__ row_loss, float* __restrict__ rowloss_c) {
+                                                       float* __restrict__ row_loss, float* __restrict__ rowloss_c,
+                                                       const int* __restrict__ amax, int* __restrict__ pred) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= *count) return;
   float mx = -INFINITY;
-  for (int t = 0; t < ntiles; ++t) mx = fmaxf(mx, part[(long)t * mcap + r].x);
+  [[maybe_unused]] int bt = 0;
+  for (int t = 0; t < ntiles; ++t) {
+    const float x = part[(long)t * mcap + r].x;
+    if constexpr (EVAL) {
+      if (x > mx) bt = t;  // strict: the lowest tile keeps an equal maximum
+    }
+    mx = fmaxf(mx, x);
+  }
+  if constexpr (EVAL) pred[rowidx[r]] = amax[(long)bt * mcap + r];
   float s = 0.f;
   for (int t = 0; t < ntiles; ++t) {
     const float2 q = part[(long)t * mcap + r];
@@ -255,6 +306,60 @@ __global__ __launch_bounds__(256) void lm_clear_rows_kernel(const int* __restric
     lse[r] = 0.f;
     if (row_loss) row_loss[r] = 0.f;
   }
+}
+
+// unlabelled rows of pred read -1
+__global__ __launch_bounds__(256) void lm_clear_pred_kernel(const int* __restrict__ slot, int R, int* __restrict__ pred) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r < R && slot[r] < 0) pred[r] = -1;
+}
+
+// per-sample sums: workgroup b walks the rows of sample b, thread t rows t, t + 256, ...; LDS tree.  Fixed order, fp64 partial sums.
+__global__ __launch_bounds__(256) void lm_sample_kernel(const int* __restrict__ slot, const int* __restrict__ tgt, const float* __restrict__ rowloss_c,
+                                                        const int* __restrict__ pred, int L, int* __restrict__ sample_tokens,
+                                                        int* __restrict__ sample_correct, float* __restrict__ sample_nll) {
+  __shared__ double s_sum[256];
+  __shared__ int s_tok[256], s_cor[256];
+  const int b = blockIdx.x;
+  double a = 0.0;
+  int nt = 0, nc = 0;
+  for (int p = threadIdx.x; p < L; p += 256) {
+    const int r = b * L + p, s = slot[r];
+    if (s >= 0) {
+      a += (double)rowloss_c[s];
+      ++nt;
+      nc += pred[r] == tgt[s];
+    }
+  }
+  s_sum[threadIdx.x] = a; s_tok[threadIdx.x] = nt; s_cor[threadIdx.x] = nc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+      s_tok[threadIdx.x] += s_tok[threadIdx.x + o];
+      s_cor[threadIdx.x] += s_cor[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (sample_tokens) sample_tokens[b] = s_tok[0];
+    sample_correct[b] = s_cor[0];
+    if (sample_nll) sample_nll[b] = (float)s_sum[0];
+  }
+}
+
+// correct = sum of sample_correct: one workgroup
+__global__ __launch_bounds__(256) void lm_correct_kernel(const int* __restrict__ sample_correct, int B, int* __restrict__ correct) {
+  __shared__ int s_cor[256];
+  int n = 0;
+  for (int b = threadIdx.x; b < B; b += 256) n += sample_correct[b];
+  s_cor[threadIdx.x] = n;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_cor[threadIdx.x] += s_cor[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *correct = s_cor[0];
 }
 
 // mean over the labelled rows: one workgroup, fixed order, fp64 partial sums.  N = 0: 0 / 0 = NaN, as torch gives.
@@ -327,6 +432,7 @@ LogitsP lm_logits_params(const tcavt_lm_loss_args* a, const LmLayout& lay) {
   p.V = a->V; p.H = a->H; p.mcap = lay.mcap; p.v0 = 0;
   p.part = reinterpret_cast<float2*>(ws + lay.part);
   p.zt = reinterpret_cast<float*>(ws + lay.zt);
+  p.amax = nullptr;
   p.lse = a->lse;
   p.P = reinterpret_cast<bf16_t*>(ws + lay.P); p.ldp = lay.chunk;
   return p;
@@ -356,8 +462,8 @@ extern "C" int tcavt_lm_loss_forward(const tcavt_lm_loss_args* a, tcavt_stream_t
   else hipLaunchKernelGGL((lm_logits_kernel<false, 0>), grid, dim3(256), 0, s, p);
   TCAVT_CHECK_LAUNCH("lm_loss_forward(logits)");
   hipLaunchKernelGGL(lm_clear_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, reinterpret_cast<const int*>(ws + lay.slot), R, a->lse, a->row_loss);
-  hipLaunchKernelGGL(lm_merge_kernel, dim3(lay.mcap / 256), dim3(256), 0, s, p.part, p.zt, p.rowidx, a->count, lay.ntiles, lay.mcap, a->lse, a->row_loss,
-                     reinterpret_cast<float*>(ws + lay.rowloss));
+  hipLaunchKernelGGL(lm_merge_kernel<false>, dim3(lay.mcap / 256), dim3(256), 0, s, p.part, p.zt, p.rowidx, a->count, lay.ntiles, lay.mcap, a->lse,
+                     a->row_loss, reinterpret_cast<float*>(ws + lay.rowloss), nullptr, nullptr);
   hipLaunchKernelGGL(lm_mean_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const float*>(ws + lay.rowloss), a->count, a->loss);
   TCAVT_CHECK_LAUNCH("lm_loss_forward(merge)");
   return TCAVT_OK;
@@ -404,5 +510,62 @@ extern "C" int tcavt_lm_loss_backward(const tcavt_lm_loss_args* a, tcavt_stream_
   else
     hipLaunchKernelGGL(lm_scatter_kernel<false>, sg, dim3(256), 0, s, G, slot, a->count, a->g_loss, unscale, R, a->H, static_cast<bf16_t*>(a->g_out), (long)a->ldg);
   TCAVT_CHECK_LAUNCH("lm_loss_backward(scatter)");
+  return TCAVT_OK;
+}
+
+extern "C" int64_t tcavt_lm_eval_workspace_bytes(int64_t rows, int V, int H) {
+  if (rows <= 0 || V <= 0 || H <= 0) return 0;
+  return lm_eval_layout(rows, V).total;
+}
+
+extern "C" int tcavt_lm_eval(const tcavt_lm_eval_args* a, tcavt_stream_t stream) {
+  const char* who = "lm_eval";
+  TCAVT_CHECK_ARG(a != nullptr, "%s: null args", who);
+  TCAVT_CHECK_ARG(a->h16 && a->table && a->labels && a->count && a->lse && a->workspace, "%s: null h16 / table / labels / count / lse / workspace", who);
+  TCAVT_CHECK_ARG(a->loss != nullptr, "%s: null loss", who);
+  TCAVT_CHECK_ARG(a->pred != nullptr, "%s: null pred", who);
+  TCAVT_CHECK_ARG(a->B > 0 && a->L > 1 && a->Nq >= 0 && a->Nq < a->L, "%s: bad B / L / Nq %d / %d / %d", who, a->B, a->L, a->Nq);
+  TCAVT_CHECK_ARG((long)a->B * a->L < (1 << 24), "%s: B * L too large", who);
+  TCAVT_CHECK_ARG(a->V > 0 && a->V % 16 == 0, "%s: V=%d must be a multiple of 16", who, a->V);
+  TCAVT_CHECK_ARG(a->H > 0 && a->H % 256 == 0, "%s: H=%d must be a multiple of 256", who, a->H);
+  TCAVT_CHECK_ARG(a->dtype16 == TCAVT_BF16 || a->dtype16 == TCAVT_F16, "%s: dtype16 must be TCAVT_BF16 or TCAVT_F16", who);
+  TCAVT_CHECK_ARG(a->ldh >= a->H && a->ldh % 8 == 0 && aligned16(a->h16) && aligned16(a->table), "%s: h16 / table need 16-byte alignment, ldh >= H and %% 8 == 0", who);
+  const LmEvalLayout lay = lm_eval_layout((long)a->B * a->L, a->V);
+  TCAVT_CHECK_ARG(a->workspace_bytes >= lay.total, "%s: workspace too small: %ld bytes, need %ld (tcavt_lm_eval_workspace_bytes)", who,
+                  (long)a->workspace_bytes, lay.total);
+  TCAVT_CHECK_ARG(((uintptr_t)a->workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(a->workspace);
+  const int R = a->B * a->L;
+  int* rowidx = reinterpret_cast<int*>(ws + lay.rowidx);
+  int* tgt = reinterpret_cast<int*>(ws + lay.tgt);
+  int* slot = reinterpret_cast<int*>(ws + lay.slot);
+  float* rowloss_c = reinterpret_cast<float*>(ws + lay.rowloss);
+  int* scor = a->sample_correct ? a->sample_correct : reinterpret_cast<int*>(ws + lay.scor);
+  hipLaunchKernelGGL(lm_select_kernel, dim3(1), dim3(1024), 0, s, a->labels, a->kv_len, a->B, a->L, a->Nq, a->V, lay.mcap, rowidx, tgt, slot, a->count,
+                     a->flag);
+  TCAVT_CHECK_LAUNCH("lm_eval(select)");
+  LogitsP p;
+  p.h = static_cast<const bf16_t*>(a->h16); p.ldh = a->ldh;
+  p.table = static_cast<const bf16_t*>(a->table);
+  p.rowidx = rowidx; p.tgt = tgt; p.count = a->count;
+  p.V = a->V; p.H = a->H; p.mcap = lay.mcap; p.v0 = 0;
+  p.part = reinterpret_cast<float2*>(ws + lay.part);
+  p.zt = reinterpret_cast<float*>(ws + lay.zt);
+  p.amax = reinterpret_cast<int*>(ws + lay.amax);
+  p.lse = nullptr; p.P = nullptr; p.ldp = 0;
+  const dim3 grid(lay.mcap / LM_TM, lay.ntiles);
+  if (a->dtype16 == TCAVT_F16) hipLaunchKernelGGL((lm_logits_kernel<true, 2>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((lm_logits_kernel<false, 2>), grid, dim3(256), 0, s, p);
+  TCAVT_CHECK_LAUNCH("lm_eval(logits)");
+  hipLaunchKernelGGL(lm_clear_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, slot, R, a->lse, a->row_loss);
+  hipLaunchKernelGGL(lm_clear_pred_kernel, dim3((R + 255) / 256), dim3(256), 0, s, slot, R, a->pred);
+  hipLaunchKernelGGL(lm_merge_kernel<true>, dim3(lay.mcap / 256), dim3(256), 0, s, p.part, p.zt, p.rowidx, a->count, lay.ntiles, lay.mcap, a->lse,
+                     a->row_loss, rowloss_c, p.amax, a->pred);
+  hipLaunchKernelGGL(lm_mean_kernel, dim3(1), dim3(256), 0, s, rowloss_c, a->count, a->loss);
+  TCAVT_CHECK_LAUNCH("lm_eval(merge)");
+  hipLaunchKernelGGL(lm_sample_kernel, dim3(a->B), dim3(256), 0, s, slot, tgt, rowloss_c, a->pred, a->L, a->sample_tokens, scor, a->sample_nll);
+  if (a->correct) hipLaunchKernelGGL(lm_correct_kernel, dim3(1), dim3(256), 0, s, scor, a->B, a->correct);
+  TCAVT_CHECK_LAUNCH("lm_eval(samples)");
   return TCAVT_OK;
 }

@@ -8,7 +8,11 @@
   through ``tcavt_traj_metrics`` (de-normalise, errors, min/argmin over K on the GPU), per-batch sums stay
   on the device, ranks exchange 4 scalars at the end (the reference evaluates on rank 0 only and so sees
   1/W of the test set, train.py:1255,1271 -- SURVEY.md 2c).
+* ``evaluate_mllm`` -- the stage-1 (MLLM text fine-tune) validation / test loop: token-weighted LM loss, perplexity,
+  token and sequence accuracy over a whole loader, from the fused eval pass (``tcavt_lm_eval``).
 """
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -140,3 +144,39 @@ def evaluate_model(model, batches, num_candidates=1, process_group=None, mc_drop
     model.mllm.check_flags()  # ids outside the vocabulary / masks that are not right-padded in ANY batch of the loop
     tot = max(tot, 1.0)
     return {"ADE": ade / tot, "FDE": fde / tot, "RMSE": rmse / tot, "n": int(tot)}
+
+
+def evaluate_mllm(model, batches, process_group=None):
+    """Stage-1 validation / test loop on the HIP path.  `model`: the MultiModalTrajectoryModel (its ``.mllm`` is used) or
+    the LlamaMultiModal itself; `batches` yields dicts with vision_emb, input_ids, attention_mask, labels on the GPU.
+    Eval mode, no_grad, no decoder tape; mode and tape flag are restored also on errors.  The sums stay on the device; ranks
+    exchange them once at the end, in float64.  Returns dict(loss, perplexity, token_accuracy, sequence_accuracy, n_tokens,
+    n_samples): loss = sum of row losses / labelled tokens over ALL batches and ranks (not a mean of batch means),
+    sequence_accuracy = share of the samples with at least one label whose labels are all predicted right (n_samples counts
+    those).  Without any labelled token the ratios are NaN."""
+    mllm = getattr(model, "mllm", model)
+    was_training = model.training
+    lw = mllm.llama_wrapper
+    was_saving, lw.save_for_backward = lw.save_for_backward, False
+    model.train(False)
+    dev = next(model.parameters()).device
+    stats = torch.zeros(5, dtype=torch.float64, device=dev)  # nll, tokens, correct, samples with labels, samples all right
+    try:
+        with torch.no_grad():
+            for b in batches:
+                out = mllm.lm_evaluate(b["vision_emb"], None, input_ids=b["input_ids"], attention_mask=b["attention_mask"],
+                                       labels=b["labels"])
+                has = out.sample_tokens > 0
+                stats += torch.stack([out.sample_nll.double().sum(), out.n_tokens.double().sum(), out.n_correct.double().sum(),
+                                      has.double().sum(), (has & (out.sample_correct == out.sample_tokens)).double().sum()])
+    finally:
+        lw.save_for_backward = was_saving
+        model.train(was_training)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
+        dist.all_reduce(stats, group=process_group)
+    nll, ntok, ncor, nsmp, nall = stats.tolist()
+    mllm.check_flags()
+    nan = float("nan")
+    loss = nll / ntok if ntok > 0 else nan
+    return {"loss": loss, "perplexity": math.exp(loss) if ntok > 0 else nan, "token_accuracy": ncor / ntok if ntok > 0 else nan,
+            "sequence_accuracy": nall / nsmp if nsmp > 0 else nan, "n_tokens": int(ntok), "n_samples": int(nsmp)}

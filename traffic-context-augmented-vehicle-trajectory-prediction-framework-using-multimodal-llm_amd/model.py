@@ -726,6 +726,28 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         return ops.lm_loss_backward(st.h16, P.table, self.table_T(), st.labels, st.Nq, st.B, st.L, lse=st.lse, count=st.count,
                                     g_out=out, workspace=st.workspace, g_loss=g_loss, kv_len=st.kv_len, flag=st.flag)
 
+    def lm_eval(self, final16, labels, Nq, B, L, kv_len=None, flag=None):
+        """Teacher-forced evaluation of the labelled rows in one fused pass (tcavt_lm_eval): the loss of lm_loss, bit for
+        bit, plus the arg-max prediction of every labelled row and the per-sample sums -- the logits are never stored.
+        Same arguments as lm_loss.  Returns fresh device tensors (no host sync): .loss fp32 [1], .count / .correct int32
+        [1], .pred int32 [B * L] (-1 on unlabelled rows), .row_loss fp32 [B * L] (0 there), .sample_nll fp32 [B],
+        .sample_tokens / .sample_correct int32 [B]."""
+        P, ws, dev = self._prepared(), self._ws, final16.device
+        V, H = P.table.shape
+        wsb = ws.get("ll.lmeval.ws", (ops.lm_eval_workspace_bytes(B * L, V, H),), torch.uint8, dev)
+        lse = ws.get("ll.lmloss.lse", (B * L,), torch.float32, dev)
+        f32 = torch.empty(1 + B * L + B, dtype=torch.float32, device=dev)
+        i32 = torch.empty(2 + B * L + 2 * B, dtype=torch.int32, device=dev)
+        loss, row_loss, sample_nll = f32[:1], f32[1:1 + B * L], f32[1 + B * L:]
+        count, correct, pred = i32[:1], i32[1:2], i32[2:2 + B * L]
+        sample_tokens, sample_correct = i32[2 + B * L:2 + B * L + B], i32[2 + B * L + B:]
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        ops.lm_eval(final16, P.table, labels, Nq, B, L, loss=loss, count=count, lse=lse, pred=pred, workspace=wsb,
+                    row_loss=row_loss, correct=correct, sample_tokens=sample_tokens, sample_correct=sample_correct,
+                    sample_nll=sample_nll, kv_len=kv_len, flag=flag)
+        return SimpleNamespace(loss=loss, count=count, correct=correct, pred=pred, row_loss=row_loss, sample_nll=sample_nll,
+                               sample_tokens=sample_tokens, sample_correct=sample_correct)
+
     def decode_weights(self):
         """Fragment-major copies of the frozen projection weights and of the tied embedding table for the decode step of
         generate_batch (ops.pack_weight16; tcavt_decode_args.w_layout = W_FRAG16): one wave instruction of the weight stream
@@ -1127,6 +1149,34 @@ class LlamaMultiModal(nn.Module, _Prepared):
                                         flag=self._lm_flag)
         return SimpleNamespace(loss=st.loss.reshape(()), n_tokens=st.count, final_hidden=final, final_hidden_bf16=final_b,
                                num_image_tokens=Nq, state=st)
+
+    def lm_evaluate(self, vision_embs, context_str, input_ids=None, attention_mask=None, labels=None):
+        """Teacher-forced evaluation of the MLLM pass on `labels` [B, Lt]: lm_forward's loss (the same bits) plus the
+        model's predictions, from one fused pass that never stores the logits.  Returns .loss / .n_tokens / .n_correct
+        (device scalars), .pred int64 [B, Lt] aligned with `labels` (pred[b, j] is the arg-max of the row that predicts
+        labels[b, j], row Nq + j - 1; -1 where labels[b, j] == -100), .row_loss fp32 [B, Lt] in the same alignment,
+        .sample_nll fp32 [B], .sample_tokens / .sample_correct int32 [B], .final_hidden and .num_image_tokens.  Runs in
+        whatever mode the model is in and never keeps a decoder tape.  A bad label sets the flag check_flags() reports."""
+        if labels is None:
+            raise ValueError("lm_evaluate needs labels (the predictions are scored against them)")
+        LW = self.llama_wrapper
+        was_saving, LW.save_for_backward = LW.save_for_backward, False
+        try:
+            final, Nq, final_b = self.forward(vision_embs, context_str, input_ids=input_ids, attention_mask=attention_mask,
+                                              return_bf16=True)
+        finally:
+            LW.save_for_backward = was_saving
+        B, L = final.shape[0], final.shape[1]
+        dev = final_b.device
+        self._lm_flag = self._ws.get("mm.lmflag", (1,), torch.int32, dev, zero=True)
+        st = LW.lm_eval(final_b[: B * L], labels, Nq, B, L, kv_len=self._ws.get("mm.kvlen", (B,), torch.int32, dev),
+                        flag=self._lm_flag)
+        # labels[b, j] is predicted by row Nq + j - 1 (Nq >= 1: the last image row predicts the first text label)
+        pred = st.pred.view(B, L)[:, Nq - 1:L - 1].to(torch.int64)
+        row_loss = st.row_loss.view(B, L)[:, Nq - 1:L - 1].contiguous()
+        return SimpleNamespace(loss=st.loss.reshape(()), n_tokens=st.count, n_correct=st.correct, pred=pred, row_loss=row_loss,
+                               sample_nll=st.sample_nll, sample_tokens=st.sample_tokens, sample_correct=st.sample_correct,
+                               final_hidden=final, num_image_tokens=Nq)
 
     def check_flags(self):
         """Host-side check of the device error flags accumulated since the last check (one sync); clears them."""

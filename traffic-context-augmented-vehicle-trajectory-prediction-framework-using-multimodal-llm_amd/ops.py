@@ -1201,3 +1201,49 @@ def lm_loss_backward(h16, table, table_t, labels, Nq, B, L, *, lse, count, g_out
     a.g_out, a.ldg, a.grad_dtype = g_out.data_ptr(), g_out.stride(0), _DT[g_out.dtype]
     check(lib().tcavt_lm_loss_backward(ctypes.byref(a), stream_ptr()), "tcavt_lm_loss_backward")
     return g_out
+
+
+def lm_eval_workspace_bytes(rows, V, H):
+    """Transient device memory of lm_eval for `rows` = B * L hidden-state rows: row arrays and per-tile statistics only."""
+    return int(lib().tcavt_lm_eval_workspace_bytes(int(rows), int(V), int(H)))
+
+
+def lm_eval(h16, table, labels, Nq, B, L, *, loss, count, lse, pred, workspace, row_loss=None, correct=None, sample_tokens=None,
+            sample_correct=None, sample_nll=None, kv_len=None, flag=None):
+    """Teacher-forced evaluation pass (include/tcavt.h: tcavt_lm_eval): what lm_loss_forward writes, bit for bit, plus
+    pred int32 [B * L] (arg-max column of every labelled row's logits, -1 elsewhere), correct int32 [1], sample_tokens /
+    sample_correct int32 [B] and sample_nll fp32 [B].  Same operands and checks as lm_loss_forward; no host sync."""
+    who = "lm_eval"
+    _req16(h16, who + ".h16", rows_ok=True)
+    _req16(table, who + ".table", like=h16)
+    _req(labels, torch.int64, who + ".labels")
+    _req(kv_len, torch.int32, who + ".kv_len")
+    _req(flag, torch.int32, who + ".flag")
+    _req(workspace, torch.uint8, who + ".workspace")
+    if h16.dim() != 2 or table.dim() != 2 or h16.shape[1] != table.shape[1]:
+        raise capi.TcavtError(f"{who}: h16 [rows, H] and table [V, H] required")
+    V, H = table.shape
+    if h16.shape[0] < B * L or labels.numel() != B * (L - Nq) or (kv_len is not None and kv_len.numel() < B):
+        raise capi.TcavtError(f"{who}: h16 needs B * L rows, labels B * (L - Nq) elements, kv_len B")
+    for t, n, nm in ((loss, 1, "loss"), (lse, B * L, "lse"), (row_loss, B * L, "row_loss"), (sample_nll, B, "sample_nll")):
+        _req(t, torch.float32, who + "." + nm)
+        _need(t, n, who + "." + nm)
+    for t, n, nm in ((count, 1, "count"), (pred, B * L, "pred"), (correct, 1, "correct"), (sample_tokens, B, "sample_tokens"),
+                     (sample_correct, B, "sample_correct")):
+        _req(t, torch.int32, who + "." + nm)
+        _need(t, n, who + "." + nm)
+    if loss is None or count is None or lse is None or pred is None:
+        raise capi.TcavtError(f"{who}: loss, count, lse and pred are required")
+    a = capi.LmEvalArgs()
+    a.h16, a.ldh, a.table = h16.data_ptr(), h16.stride(0), table.data_ptr()
+    a.labels = labels.data_ptr()
+    a.kv_len = None if kv_len is None else kv_len.data_ptr()
+    a.B, a.L, a.V, a.H, a.Nq = B, L, V, H, Nq
+    a.dtype16 = _DT[h16.dtype]
+    a.loss, a.count, a.lse, a.pred = loss.data_ptr(), count.data_ptr(), lse.data_ptr(), pred.data_ptr()
+    for nm, t in (("row_loss", row_loss), ("flag", flag), ("correct", correct), ("sample_tokens", sample_tokens),
+                  ("sample_correct", sample_correct), ("sample_nll", sample_nll)):
+        setattr(a, nm, None if t is None else t.data_ptr())
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    check(lib().tcavt_lm_eval(ctypes.byref(a), stream_ptr()), "tcavt_lm_eval")
+    return pred

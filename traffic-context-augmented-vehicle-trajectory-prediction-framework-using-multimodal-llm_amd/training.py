@@ -451,14 +451,31 @@ class MllmTrainer:
     embeddings to the trainable set (the backward continues below decoder layer 0).  The pieces are Trainer's: backward_flags /
     make_backward, GradBook, the device-chosen gradient scale with its back-off, the norm clip and the gated AdamW (a non-finite
     loss -- no labelled row gives NaN -- or gradient norm skips the update, decided on the device).
-    Single process: a process group of more than one rank is refused (the LM-loss step has no gradient exchange)."""
+    Single process by default: without data_parallel=True a process group of more than one rank is refused.
+
+    data_parallel=True (the reference's stage 1 is a DDP job: `mllm_lora_ddp_finetuned.pt`): the constructor broadcasts rank
+    0's parameters and AdamW moments (Trainer.broadcast_state); the adapter gradients are SUM-all-reduced as one bucket after
+    LoraBackward.run and -- with train_mllm_front -- the front gradients as a second one after the Q-Former backward and its
+    leaf streams, each launched from the stream that completed the bucket (Trainer._allreduce_bucket; TCAVT_FORCE_DP=1 sends
+    a one-rank group down the same path); the mean is taken in the clip call (grad_scale = 1 / world).
+      loss_normalization="rank"  : what HF + DDP computes -- each rank's token mean, gradients averaged; the reported loss is
+                                   the mean of the ranks' losses.
+      loss_normalization="global": token mean over the global batch.  The ranks all-reduce their labelled-row counts on the
+                                   device between the LM forward and its backward (no host sync); rank r's backward runs with
+                                   g_loss = world N_r / N_total, so that the averaged gradient is the single-process gradient of
+                                   the concatenated batch; the reported loss is sum_r N_r loss_r / N_total.  A rank without a
+                                   labelled row contributes zero (its NaN mean never enters the sum).
+    The gated AdamW takes the EXCHANGED loss and the norm of the EXCHANGED gradient, so all ranks apply or skip together and the
+    fp16 scale back-off (ctl[6]) stays in step: a per-rank gate would let the replicas diverge silently."""
 
     def __init__(self, model, lr=5e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 train_mllm_front=False, process_group=None):
+                 train_mllm_front=False, process_group=None, data_parallel=False, loss_normalization="rank"):
         world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
-        if world > 1:
+        if world > 1 and not data_parallel:
             raise RuntimeError(f"MllmTrainer is single process: the process group has {world} ranks and the LM-loss step has no "
                                "gradient exchange (data parallel for the stage-1 trainer is not implemented)")
+        if loss_normalization not in ("rank", "global"):
+            raise ValueError(f"MllmTrainer: loss_normalization must be 'rank' or 'global', not {loss_normalization!r}")
         lw = model.mllm.llama_wrapper
         if not lw.use_lora:
             raise ValueError("MllmTrainer: the model has no LoRA adapters (use_lora=False)")
@@ -490,9 +507,33 @@ class MllmTrainer:
         self._clip_scratch = None
         self.step_count = 0
         self.last = None
+        self._gate_loss = None
+        # gradient exchange (Trainer._allreduce_bucket reads these)
+        self.pg, self.world = process_group, world
+        self.loss_normalization = loss_normalization
+        self._fake_dp, self._exchange, self.diag = None, True, None
+        self._force_dp = bool(data_parallel) and (world == 1 and os.environ.get("TCAVT_FORCE_DP", "0") == "1"
+                                                  and dist.is_available() and dist.is_initialized())
+        self.data_parallel = bool(data_parallel) and (world > 1 or self._force_dp)
+        self.n_lora = self.book.end_of(lora[-1][0])  # bucket 1: the adapters; bucket 2: the front, when it trains
+        if self.data_parallel and world > 1:
+            self.broadcast_state()
         model.invalidate_prepared()
 
     clip_grad_norm_ = Trainer.clip_grad_norm_
+    broadcast_state = Trainer.broadcast_state
+    _allreduce_bucket = Trainer._allreduce_bucket
+
+    def _exchange_loss(self, st):
+        """(loss every rank's gate sees, g_loss of this rank's LM backward or None) from the LM forward's state; device only."""
+        if self.loss_normalization == "rank":
+            loss = st.loss.clone()
+            dist.all_reduce(loss, group=self.pg)
+            return loss / self.world, None
+        n = st.count.double()
+        stats = torch.cat([n, torch.where(n > 0, n * st.loss.double(), torch.zeros_like(n))])  # N_r, N_r loss_r (0, not NaN, at N_r = 0)
+        dist.all_reduce(stats, group=self.pg)
+        return (stats[1:2] / stats[0:1]).float(), (self.world * n / stats[0:1]).float()  # N_total = 0: NaN, every rank skips
 
     def forward_backward(self, vision_embs, input_ids, attention_mask, labels):
         """zero_grad + taped forward + LM loss + backward; gradients end up in ``self.book.g``.  Returns the loss (device scalar)."""
@@ -508,26 +549,34 @@ class MllmTrainer:
                 m._fwd_count += 1
             mm.qformer.dctx, lw.dctx = (dctx.sub(1), dctx.sub(2)) if dctx is not None else (None, None)
             out = mm.lm_forward(vision_embs, None, input_ids=input_ids, attention_mask=attention_mask, labels=labels)
-            g_final = lw.lm_loss_backward(out.state)
+            loss, g_loss = out.loss.reshape(1), None
+            if self.data_parallel:
+                loss, g_loss = self._exchange_loss(out.state)
+            g_final = lw.lm_loss_backward(out.state, g_loss=g_loss)
             B, L = out.state.B, out.state.L
             g_h0 = self.lbw.run(g_final)
+            if self.data_parallel:
+                self._allreduce_bucket(0, self.n_lora)
             if self.qbw is not None:
                 self.qbw.run(g_h0, B, L)
-                cur = torch.cuda.current_stream()
                 for ls in (self.bw._leaf_streams or []):  # the Q-Former's weight gradients are leaf work on side streams
-                    cur.wait_stream(ls)
+                    torch.cuda.current_stream().wait_stream(ls)
+                if self.data_parallel:
+                    self._allreduce_bucket(self.n_lora, self.book.total)
         self.last = out
-        return out.loss
+        self._gate_loss = loss
+        return loss.reshape(())
 
     def optimizer_step(self):
         m = self.model
         with torch.no_grad():
-            norm = None
+            grad_scale, norm = (1.0 / self.world if self.data_parallel else 1.0), None
             if self.max_grad_norm is not None:
-                norm = self.clip_grad_norm_(self.max_grad_norm)
+                norm = self.clip_grad_norm_(self.max_grad_norm, grad_scale=grad_scale)  # mean first, then clip
+                grad_scale = 1.0
             self.step_count += 1
             ops.adamw_gated(self.book.params, self.book.grads, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
-                            self.wd, self.last.loss.reshape(1), self._ctl, grad_scale=1.0, grad_norm=norm)
+                            self.wd, self._gate_loss, self._ctl, grad_scale=grad_scale, grad_norm=norm)
             m.mllm.llama_wrapper.refresh_lora(self._lora_stacked)
             if self.train_mllm_front:
                 m.mllm.qformer._invalidate()
