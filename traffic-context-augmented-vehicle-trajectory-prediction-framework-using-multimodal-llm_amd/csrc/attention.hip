@@ -537,7 +537,8 @@ extern "C" int tcavt_attn_causal_gqa_lse(const void* qkv, void* out, float* lse,
   int lds = Lp * 128 + 64 * (Lp + 4) * 2;
   const int group = nq / nkv;
   const bool small = 2 * group * 64 <= 512;
-  // per-wave output tiles (32 x 144 bytes) behind K and V^T when the CU's LDS has room (L <= 384 for groups of 4)
+  // per-wave output tiles (32 x 144 bytes) behind K and V^T when the CU's LDS has room: L <= 480 for groups of 4, L <= 320
+  // for groups of 8, L <= 512 for groups of 3, every L <= 544 for groups of 1 and 2
   int ot_bytes = 2 * group * 32 * 144;
   if (((lds + 15) & ~15) + ot_bytes <= 160 * 1024 - 256) lds = ((lds + 15) & ~15) + ot_bytes;
   else ot_bytes = 0;
