@@ -124,9 +124,8 @@ typedef struct tcavt_gemm_args {
                                     257 = 4-wave 256x256 (whole tiles only), 271 = 4-wave 256x192 (N % 192 == 0),
                                     272 = 4-wave two-barrier deep-prefetch form (long K).  The 4-wave forms write their SILU_MUL / ROPE /
                                     in-place NORM_OUT results with 16-byte accesses: 16-bit output of the operand type and
-                                    ldc % 8 == 0 (refused otherwise; auto picks the 8-wave form).  Any other code is refused by
-                                    the product library (measured-and-rejected variants and timing experiments live in
-                                    the -DTCAVT_EXPERIMENTS build that tools/ makes for itself) */
+                                    ldc % 8 == 0 (refused otherwise; auto picks the 8-wave form).  The codes are 0, 64, 128, 256,
+                                    257, 271 and 272; nothing else exists, and any other value is refused */
   float acc_scale;               /* accumulator is multiplied by this first; 0 means 1 */
   int32_t in_dtype;              /* operand type of A/W/A2/W2: 0 or TCAVT_BF16, or TCAVT_F16 (every epilogue and kernel form) */
   /* Batched form (generic epilogue only): batch > 1 runs `batch` independent products; product i uses

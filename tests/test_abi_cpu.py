@@ -104,6 +104,28 @@ def test_argument_errors_are_reported_not_crashed():
     assert rc == 1 and b"skinny form" in capi.lib().tcavt_last_error()
 
 
+def test_gemm_refuses_every_tile_code_but_the_seven_forms():
+    """tcavt_gemm_args.tile: 0 (auto), 64, 128, 256, 257, 271 and 272 exist.  Every other value is an argument error whose
+    message names the accepted codes -- with otherwise valid arguments, and before anything touches a device."""
+    from tcavt_amd import capi
+
+    accepted = (64, 128, 256, 257, 271, 272)
+    args = capi.GemmArgs()
+    args.A = args.W = args.C = 64  # (fake, 16-byte aligned, never dereferenced)
+    args.M, args.N, args.K = 256, 256, 128
+    args.lda = args.ldw = 128
+    args.ldc = 256
+    args.out_dtype = capi.BF16
+    for tile in range(1, 301):
+        if tile in accepted:
+            continue
+        args.tile = tile
+        rc = capi.lib().tcavt_gemm_bf16(ctypes.byref(args), None)
+        msg = capi.lib().tcavt_last_error()
+        assert rc == 1, tile
+        assert b"tile must be" in msg and all(str(c).encode() in msg for c in accepted), (tile, msg)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from tcavt_amd import capi
 

@@ -417,18 +417,14 @@ def test_gemm_w4_persistent_stream(gpu):
 
 
 def test_gemm_timing_experiment_codes_are_refused(gpu):
-    """Tile codes 261-267 are timing-only elimination experiments that compute wrong results: refused by the C ABI
-    unless TCAVT_GEMM_TIMING_EXPERIMENTS is set in the environment."""
-    import os
-
+    """Every tile code that once selected a measured-and-rejected GEMM variant or a timing-only elimination experiment
+    (which computed wrong results) is refused by the C ABI: the library holds the production forms only."""
     from tcavt_amd import capi, ops
 
-    if os.environ.get("TCAVT_GEMM_TIMING_EXPERIMENTS"):
-        pytest.skip("experiments explicitly enabled in this environment")
     dev = gpu["device"]
     a = torch.zeros(256, 128, dtype=torch.bfloat16, device=dev)
     w = torch.zeros(256, 128, dtype=torch.bfloat16, device=dev)
-    for code in (261, 264, 267):
+    for code in (124, 125, 126, 127, 250, 252, 253, 255, 258, 259, *range(261, 271), 273, 274):
         with pytest.raises(capi.TcavtError):
             ops.gemm_bf16(a, w, out_dtype=torch.bfloat16, silu_mul=True, tile=code)
 

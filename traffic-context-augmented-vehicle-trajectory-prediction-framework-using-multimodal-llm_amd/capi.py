@@ -15,8 +15,6 @@ import torch  # noqa: F401  (must precede CDLL: see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtcavt_hip.so")
-if os.environ.get("TCAVT_LIB") == "exp":  # tools/ only: the -DTCAVT_EXPERIMENTS build (python -m tcavt_amd.build --experiments)
-    LIB_PATH = os.path.join(_HERE, "libtcavt_hip_exp.so")
 
 ABI_VERSION = 5  # TCAVT_ABI_VERSION of include/tcavt.h
 F32, BF16, F16 = 0, 1, 2

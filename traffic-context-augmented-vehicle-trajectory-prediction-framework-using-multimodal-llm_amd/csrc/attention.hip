@@ -57,25 +57,13 @@ __device__ __forceinline__ unsigned int bf16pair_to_f16pair(unsigned int k0_bits
 // lane -- with the 1024-thread bound (groups up to 8) the kernel is held to 128 and spills.
 // F16: q|k|v and the output are fp16 (the forward path's default storage): S^T = K . Q^T runs on the f16 MFMA and V needs
 // no conversion while it is transposed into LDS.
-// STAMP (experiments build, tools/attn_stamps.py): s_memtime at the phase boundaries of every wave, written to `stamps`
-// ([workgroup][wave][16] uint64) -- a buffer nothing else reads; the product instantiation has no such code.
-template <int MAXT, bool F16, bool STAMP = false>
+template <int MAXT, bool F16>
 __global__ __launch_bounds__(MAXT) void attn_causal_gqa_kernel(const bf16_t* __restrict__ qkv,
                                                               bf16_t* __restrict__ out,
                                                               const int* __restrict__ kv_len_p,
                                                               int L, int Lp, int nq, int nkv,
                                                               float scale_log2e, int ot_bytes,
-                                                              unsigned long long* __restrict__ stamps = nullptr,
                                                               float* __restrict__ lse = nullptr) {
-  int n_stamp = 0;
-  auto stamp = [&]() {
-    if constexpr (STAMP) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if ((threadIdx.x & 63) == 0 && n_stamp < 16) stamps[((long)blockIdx.x * (MAXT / 64) + (threadIdx.x >> 6)) * 16 + n_stamp] = t;
-      ++n_stamp;
-    }
-  };
-  stamp();  // 0: entry
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int group = nq / nkv;
   const int b = blockIdx.x / nkv, kvh = blockIdx.x % nkv;
@@ -187,9 +175,7 @@ __global__ __launch_bounds__(MAXT) void attn_causal_gqa_kernel(const bf16_t* __r
     stage_k(idx, krow_ok(idx) ? load_k(idx) : zero4);
   for (int idx = threadIdx.x + VIT * nthreads; idx < (Lp >> 1) * 8; idx += nthreads)
     stage_v(idx, vrow_ok(idx, 0) ? load_v(idx, 0) : zero4, vrow_ok(idx, 1) ? load_v(idx, 1) : zero4);
-  stamp();  // 1: staging stores issued
   __syncthreads();
-  stamp();  // 2: K / V visible
 
   const int kv_len = min(kv_len_p[b], L);
   const int kv_tiles = (kv_len + 31) >> 5;
@@ -313,7 +299,6 @@ __global__ __launch_bounds__(MAXT) void attn_causal_gqa_kernel(const bf16_t* __r
         const u32x4 v = *reinterpret_cast<const u32x4*>(ot + row * 144 + (lane & 7) * 16);
         if (q < L) *reinterpret_cast<u32x4*>(out + ((long)b * L + q) * (nq * 64) + head * 64 + (lane & 7) * 8) = v;
       }
-      stamp();
       return;
     }
     bf16_t* orow = out + ((long)b * L + min(qi, L - 1)) * (nq * 64) + head * 64;
@@ -330,7 +315,6 @@ __global__ __launch_bounds__(MAXT) void attn_causal_gqa_kernel(const bf16_t* __r
         if (qi < L) *reinterpret_cast<u32x4*>(orow + half * 32 + 8 * g + 8 * hh) = u32x4{s0[0], s1[0], s0[1], s1[1]};
       }
     }
-    stamp();  // 3 + block: block done (stores issued)
   };
 
 #pragma unroll
@@ -560,7 +544,7 @@ extern "C" int tcavt_attn_causal_gqa_lse(const void* qkv, void* out, float* lse,
 #define TCAVT_ATTN(MAXT, F)                                                                                       \
   hipLaunchKernelGGL((attn_causal_gqa_kernel<MAXT, F>), dim3(B * nkv), dim3(2 * group * 64), lds,                  \
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(out), \
-                     kv_len, L, Lp, nq, nkv, scale * 1.4426950408889634f, ot_bytes, nullptr, lse)
+                     kv_len, L, Lp, nq, nkv, scale * 1.4426950408889634f, ot_bytes, lse)
   if (which == 0) TCAVT_ATTN(1024, false);
   else if (which == 1) TCAVT_ATTN(512, false);
   else if (which == 2) TCAVT_ATTN(1024, true);
@@ -610,23 +594,3 @@ extern "C" int tcavt_mha(const void* q, int64_t ldq, const void* k, int64_t ldk,
   TCAVT_CHECK_LAUNCH("mha");
   return TCAVT_OK;
 }
-
-#ifdef TCAVT_EXPERIMENTS
-// tools/attn_stamps.py: the fp16, group-4 instantiation with s_memtime stamps (stamps: [B * nkv][8][16] uint64)
-extern "C" int tcavt_attn_causal_gqa_stamped(const void* qkv, void* out, const int32_t* kv_len, int B, int L, int nq, int nkv,
-                                             float scale, unsigned long long* stamps, tcavt_stream_t stream) {
-  TCAVT_CHECK_ARG(qkv && out && kv_len && stamps && nq / nkv == 4 && L <= 544, "attn_causal_gqa_stamped: bad args");
-  const int Lp = (L + 31) & ~31;
-  int lds = Lp * 128 + 64 * (Lp + 4) * 2;
-  int ot_bytes = 8 * 32 * 144;
-  if (((lds + 15) & ~15) + ot_bytes <= 160 * 1024 - 256) lds = ((lds + 15) & ~15) + ot_bytes;
-  else ot_bytes = 0;
-  auto kfn = attn_causal_gqa_kernel<512, true, true>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-  hipLaunchKernelGGL(kfn, dim3(B * nkv), dim3(512), lds, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<bf16_t*>(out), kv_len, L, Lp, nq, nkv, scale * 1.4426950408889634f, ot_bytes, stamps,
-                     static_cast<float*>(nullptr));
-  TCAVT_CHECK_LAUNCH("attn_causal_gqa_stamped");
-  return TCAVT_OK;
-}
-#endif
