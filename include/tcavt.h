@@ -310,8 +310,9 @@ int tcavt_mask_to_kvlen(const int64_t* mask, int B, int Lt, int Nq, int32_t* kv_
  *   out  same type [B*L][nq * 64]
  *   kv_len int32 [B]: keys j < kv_len[b] are valid (right padding); a query i
  *   attends keys j <= i with j < kv_len[b]; padded queries are still computed.
- * head_dim is 64; nq % nkv == 0; L <= 544.  softmax in fp32, scale given.
+ * head_dim is 64; nq % nkv == 0; L <= TCAVT_ATTN_RESIDENT_MAX_L.  softmax in fp32, scale given.
  * ---------------------------------------------------------------------- */
+#define TCAVT_ATTN_RESIDENT_MAX_L 544
 int tcavt_attn_causal_gqa(const void* qkv, void* out, const int32_t* kv_len, int B,
                           int L, int nq, int nkv, float scale, int dtype16, tcavt_stream_t stream);
 /* The same, also leaving lse fp32 [B][nq][L] (NULL: none) = log sum_j exp(scale * q_i . k_j) over the keys query i attends
@@ -319,6 +320,20 @@ int tcavt_attn_causal_gqa(const void* qkv, void* out, const int32_t* kv_len, int
  * (LoRA-trainable variant, modify_scripts/modify_train.py:512-528). */
 int tcavt_attn_causal_gqa_lse(const void* qkv, void* out, float* lse, const int32_t* kv_len, int B,
                               int L, int nq, int nkv, float scale, int dtype16, tcavt_stream_t stream);
+/* The same attention for sequences whose K and V^T do not fit in LDS: 1 <= L <= TCAVT_ATTN_STREAM_MAX_L.  A workgroup per
+ * (sample, kv head, chunk of 64 queries) walks the key chunks of 256 from 0 to its diagonal with
+ * the output accumulators, running maximum and running sum of its queries in registers; one key chunk's K and V^T (66,048
+ * bytes of LDS whatever L is) is staged at a time, chunks at or beyond kv_len are skipped.  Arguments, semantics and the
+ * lse convention are those of tcavt_attn_causal_gqa_lse (query i attends keys j <= i with j < kv_len[b]; padded queries
+ * are computed and attend every valid key; kv_len 0 gives zeros and lse 0; lse may be NULL); the arithmetic per key is
+ * the same, the bits of the result are not promised to be.  The kernel does not depend on L; the cap fences off what is
+ * not tested.  TCAVT_ERR_ARG before any launch (nothing is written) on a null or misaligned qkv / out / kv_len, a dtype
+ * other than fp16 / bf16, L outside [1, TCAVT_ATTN_STREAM_MAX_L], nq % nkv != 0 or nq / nkv > 8; messages start with
+ * "attn_causal_gqa_stream:".  tcavt_llama_stack_forward takes it for TCAVT_ATTN_RESIDENT_MAX_L < L <=
+ * TCAVT_ATTN_STREAM_MAX_L. */
+#define TCAVT_ATTN_STREAM_MAX_L 2048
+int tcavt_attn_causal_gqa_stream(const void* qkv, void* out, float* lse, const int32_t* kv_len, int B, int L, int nq, int nkv,
+                                 float scale, int dtype16, tcavt_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Row softmax for the batched cross-attention: P[r][c] = softmax_c(S[r][c]) over c < n_valid,
@@ -528,6 +543,16 @@ int tcavt_attn_bwd_long_ok(int T, int nq, int nkv);
 int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16, float* stats,
                         const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T, int nq, int nkv,
                         int head_dim, float scale, int dtype16, tcavt_stream_t stream);
+/* The chunked backward beyond 544 (tcavt_attn_bwd_stream_ok: 544 < T <= TCAVT_ATTN_STREAM_MAX_L, 16 % (nq / nkv) == 0 --
+   where the dispatch takes it; the entry point itself computes any 1 <= T <= TCAVT_ATTN_STREAM_MAX_L): the two launches of
+   tcavt_attn_bwd_long, whose kernels hold one chunk's image in LDS and loop over (T + 255) / 256 chunks, under the higher
+   cap.  Arguments, outputs, `stats` and the two-launch bit equality exactly as tcavt_attn_bwd_long; rope_cos / rope_sin
+   need T rows.  TCAVT_ERR_ARG before any launch on T outside [1, TCAVT_ATTN_STREAM_MAX_L], head_dim != 64, an unsupported
+   group, a null or misaligned pointer; messages start with "attn_bwd_stream:". */
+int tcavt_attn_bwd_stream_ok(int T, int nq, int nkv);
+int tcavt_attn_bwd_stream(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16, float* stats,
+                          const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T, int nq, int nkv,
+                          int head_dim, float scale, int dtype16, tcavt_stream_t stream);
 /* dK, dV of the attention backward, key-major on the matrix cores (one workgroup per sample, key/value head and 64 keys;
    P^T, dS^T rebuilt from `stats`, the query heads of the group summed in registers): writes the k and v columns of
    g32 [B*T, (nq+2nkv)*64] fp32 (every row; no zero-initialisation needed) */

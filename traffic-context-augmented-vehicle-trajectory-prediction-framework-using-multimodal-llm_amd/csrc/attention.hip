@@ -501,9 +501,260 @@ __global__ __launch_bounds__(256) void mha_lds_kernel(const TI* __restrict__ q, 
   }
 }
 
+// ---------------------------------------------------------------------------
+// (3) attn_causal_gqa_stream_kernel -- the decoder attention of (1) for sequences whose K and V^T do not fit in LDS
+//     (tcavt_attn_causal_gqa_stream: 544 < L <= 2048 through the decoder stack; any L >= 1 is computed correctly).
+//     A workgroup owns (sample, kv head, chunk of 64 queries) and walks the key chunks of 256 keys from 0 up to its
+//     diagonal -- chunks at or beyond kv_len are never visited -- staging K [256][64] and V^T [64][260] of ONE key chunk
+//     behind a barrier pair: 66,048 bytes whatever L is, one buffer, so that a CU holds two workgroups and one computes
+//     while the other restages.  The 2 * group waves are those of (1): wave w serves query head w % group, and the two
+//     32-query blocks of the chunk are the (short, long) pair of a head's two waves (one key tile apart on the diagonal
+//     chunk, none elsewhere).  A wave keeps the query fragments, the O^T accumulators, the running maximum and the running
+//     sum of its block in registers across the key chunks (50 VGPRs); only K and V are restaged.  110 / 111 VGPRs (fp16 / bf16): under
+//     the 128 a wave of a 1024-thread workgroup has (groups of 8), and two 512-thread workgroups (groups of 4) share a CU.
+//     (A variant with two blocks per wave, chunks of 128 queries, needed 165 VGPRs: one workgroup per CU at group 4.  It
+//     was measured slower while this kernel was written and is not in the tree; profiles/attention_stream.txt section 3.)
+//     Per key tile the arithmetic is that of (1), instruction for instruction.
+//     Workgroups of the LAST query chunks (most key chunks) come first in the grid.
+// ---------------------------------------------------------------------------
+constexpr int AS_KC = 256;             // keys per chunk
+constexpr int AS_VS = AS_KC + 4;       // V^T row stride (elements)
+constexpr int AS_LDS = AS_KC * 128 + 64 * AS_VS * 2;
+constexpr int AS_QC = 64;              // queries per chunk: one 32-query block per wave
+
+template <bool F16>
+__global__ __launch_bounds__(1024) void attn_causal_gqa_stream_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                                     const int* __restrict__ kv_len_p, int L, int nq, int nkv,
+                                                                     int nqc, int nbj, float scale_log2e, float* __restrict__ lse) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int group = nq / nkv;
+  const int bj = blockIdx.x % nbj, qc = nqc - 1 - blockIdx.x / nbj;
+  const int b = bj / nkv, kvh = bj % nkv;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ld = (nq + 2 * nkv) * 64;
+  const int koff = nq * 64 + kvh * 64, voff = (nq + nkv) * 64 + kvh * 64;
+  char* Ks = smem;
+  bf16_t* Vt = reinterpret_cast<bf16_t*>(smem + AS_KC * 128);
+  const bf16_t* base = qkv + (long)b * L * ld;
+  const int head = kvh * group + (wave % group);
+  const int par = wave / group;  // 0 or 1
+  const int r = lane & 31, hh = lane >> 5;
+  const int kswz = (r >> 1) & 7;
+  const int kv_len = min(kv_len_p[b], L);
+  const int kv_tiles = (kv_len + 31) >> 5;
+  const int nthreads = blockDim.x;
+
+  // this wave's query block (global 32-query block number), its query fragments and running state
+  const int qb = qc * 2 + par;
+  const bool has_block = qb * 32 < L;  // (uniform)
+  const int qi = qb * 32 + r;          // this lane's query row
+  bf16x8 qf[4];
+  {
+    const int qrow = min(qi, L - 1);  // (a block at or beyond L loads row L - 1 and is never used)
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      qf[s] = *reinterpret_cast<const bf16x8*>(base + (long)qrow * ld + head * 64 + s * 16 + hh * 8);
+  }
+  f32x16 o0, o1;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { o0[i] = 0.f; o1[i] = 0.f; }
+  float mrun = -1e30f, lrun = 0.f;
+
+  // key tiles any query of this chunk attends: up to the chunk's last query below L, and below kv_len
+  const int q_hi = min(qc * AS_QC + AS_QC, L);
+  const int tiles_wg = min((q_hi + 31) >> 5, kv_tiles);
+  const u32x4 zero4 = {0u, 0u, 0u, 0u};
+  for (int kc = 0; kc * (AS_KC / 32) < tiles_wg; ++kc) {  // (uniform)
+    const int k0 = kc * AS_KC;
+    const int nrow = min(AS_KC, tiles_wg * 32 - k0);  // rows of this chunk anyone reads (a multiple of 32)
+    if (kc > 0) __syncthreads();                       // everyone is done with the previous chunk
+    // ---- stage K (swizzled rows) and V^T; four K passes / two V passes of loads in flight together.  Rows >= L are
+    // staged as zeros, their loads clamped (as in (1))
+    for (int i0 = threadIdx.x; i0 < nrow * 8; i0 += 4 * nthreads) {
+      u32x4 kreg[4];
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int idx = i0 + it * nthreads;
+        const int row = min(k0 + (idx >> 3), L - 1), c = idx & 7;
+        kreg[it] = *reinterpret_cast<const u32x4*>(base + (long)row * ld + koff + c * 8);
+      }
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int idx = i0 + it * nthreads;
+        const int row = idx >> 3, c = idx & 7;
+        if (idx < nrow * 8)
+          *reinterpret_cast<u32x4*>(Ks + row * 128 + ((c ^ ((row >> 1) & 7)) << 4)) = (k0 + row < L) ? kreg[it] : zero4;
+      }
+    }
+    for (int i0 = threadIdx.x; i0 < (nrow >> 1) * 8; i0 += 2 * nthreads) {
+      u32x4 va[2], vb[2];
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int idx = i0 + it * nthreads;
+        const int r0 = k0 + 2 * (idx >> 3), c = idx & 7;
+        va[it] = *reinterpret_cast<const u32x4*>(base + (long)min(r0, L - 1) * ld + voff + c * 8);
+        vb[it] = *reinterpret_cast<const u32x4*>(base + (long)min(r0 + 1, L - 1) * ld + voff + c * 8);
+      }
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int idx = i0 + it * nthreads;
+        if (idx >= (nrow >> 1) * 8) continue;
+        const int kp = idx >> 3, c = idx & 7;
+        const int r0 = 2 * kp;
+        const u32x4 a = (k0 + r0 < L) ? va[it] : zero4, bb = (k0 + r0 + 1 < L) ? vb[it] : zero4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          unsigned int lo, hi;
+          if constexpr (F16) {
+            lo = (a[e] & 0xffffu) | (bb[e] << 16);
+            hi = (a[e] >> 16) | (bb[e] & 0xffff0000u);
+          } else {
+            lo = bf16pair_to_f16pair(a[e] & 0xffffu, bb[e] & 0xffffu);
+            hi = bf16pair_to_f16pair(a[e] >> 16, bb[e] >> 16);
+          }
+          *reinterpret_cast<unsigned int*>(Vt + (c * 8 + 2 * e) * AS_VS + r0) = lo;
+          *reinterpret_cast<unsigned int*>(Vt + (c * 8 + 2 * e + 1) * AS_VS + r0) = hi;
+        }
+      }
+    }
+    __syncthreads();
+
+    if (has_block) {
+      const int kt_end = min(min(qb + 1, kv_tiles), (kc + 1) * (AS_KC / 32));
+      for (int kt = kc * (AS_KC / 32); kt < kt_end; ++kt) {
+        const int ktl = kt - kc * (AS_KC / 32);  // tile within the staged chunk
+        f32x16 sacc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[i] = 0.f;
+        const char* krow = Ks + (ktl * 32 + r) * 128;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(krow + (((2 * s + hh) ^ kswz) << 4));
+          if constexpr (F16)
+            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kf), __builtin_bit_cast(f16x8, qf[s]), sacc, 0, 0, 0);
+          else
+            sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc, 0, 0, 0);
+        }
+        // scale + mask + tile max: per-element masks only on the diagonal tile and on a tile that straddles kv_len
+        float p[16];
+        const bool full = (kt < qb) && (kt * 32 + 32 <= kv_len);
+        if (full) {
+          float rmax = fmaxf(fmaxf(sacc[0], sacc[1]), sacc[2]);
+#pragma unroll
+          for (int i = 3; i + 1 < 16; i += 2) rmax = fmaxf(fmaxf(rmax, sacc[i]), sacc[i + 1]);
+          rmax = fmaxf(rmax, sacc[15]);
+          { float a, b2; halves(rmax, a, b2); rmax = fmaxf(a, b2); }
+          const float mnew = fmaxf(mrun, rmax * scale_log2e);
+          const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
+          float psum = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            p[i] = __builtin_amdgcn_exp2f(fmaf(sacc[i], scale_log2e, -mnew));
+            psum += p[i];
+          }
+          { float a, b2; halves(psum, a, b2); psum = a + b2; }
+          lrun = lrun * alpha + psum;
+          mrun = mnew;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
+        } else {
+          float tmax = -1e30f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int kk = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const bool ok = (kk <= qi) && (kk < kv_len);
+            p[i] = ok ? sacc[i] * scale_log2e : -1e30f;
+            tmax = fmaxf(tmax, p[i]);
+          }
+          { float a, b2; halves(tmax, a, b2); tmax = fmaxf(a, b2); }
+          const float mnew = fmaxf(mrun, tmax);
+          const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
+          float psum = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            p[i] = (p[i] > -1e29f) ? __builtin_amdgcn_exp2f(p[i] - mnew) : 0.f;
+            psum += p[i];
+          }
+          { float a, b2; halves(psum, a, b2); psum = a + b2; }
+          lrun = lrun * alpha + psum;
+          mrun = mnew;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
+        }
+        // O^T += V^T . P^T  (two 16-key k-steps; P registers 8*s2.. are the B operand)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const f16x8 pf = cvt8_f16(&p[8 * s2]);
+          const int kbase = ktl * 32 + 16 * s2 + 4 * hh;
+#pragma unroll
+          for (int dt = 0; dt < 2; ++dt) {
+            const bf16_t* vrow = Vt + (dt * 32 + r) * AS_VS + kbase;
+            const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
+            const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 8);
+            const u32x4 vv = {lo[0], lo[1], hi[0], hi[1]};
+            const f16x8 vf = __builtin_bit_cast(f16x8, vv);
+            if (dt == 0) o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o0, 0, 0, 0);
+            else o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o1, 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+
+  // ---- normalise + store (the register form of (1): v_permlane32_swap on the packed words of two neighbouring 8-dim
+  // groups leaves 16 consecutive bytes in every lane), once per query block after its whole key sweep
+  if (has_block) {
+    const float inv = lrun > 0.f ? 1.f / lrun : 0.f;
+    if (lse && hh == 0 && qi < L)
+      lse[((long)b * nq + head) * L + qi] = lrun > 0.f ? (mrun + __log2f(lrun)) * 0.6931471805599453f : 0.f;
+    bf16_t* orow = out + ((long)b * L + min(qi, L - 1)) * (nq * 64) + head * 64;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const f32x16& o = half ? o1 : o0;
+#pragma unroll
+      for (int g = 0; g < 4; g += 2) {
+        unsigned int a0 = pack16x2<F16>(o[4 * g] * inv, o[4 * g + 1] * inv), a1 = pack16x2<F16>(o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+        unsigned int b0 = pack16x2<F16>(o[4 * g + 4] * inv, o[4 * g + 5] * inv), b1 = pack16x2<F16>(o[4 * g + 6] * inv, o[4 * g + 7] * inv);
+        auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+        auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+        if (qi < L) *reinterpret_cast<u32x4*>(orow + half * 32 + 8 * g + 8 * hh) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+      }
+    }
+  }
+}
+
 }  // namespace tcavt
 
 using namespace tcavt;
+
+extern "C" int tcavt_attn_causal_gqa_stream(const void* qkv, void* out, float* lse, const int32_t* kv_len, int B, int L, int nq,
+                                            int nkv, float scale, int dtype16, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(qkv && out && kv_len, "attn_causal_gqa_stream: null pointer");
+  TCAVT_CHECK_ARG(is16(dtype16), "attn_causal_gqa_stream: dtype16 must be TCAVT_BF16 or TCAVT_F16");
+  TCAVT_CHECK_ARG(B > 0 && L > 0 && L <= TCAVT_ATTN_STREAM_MAX_L, "attn_causal_gqa_stream: L=%d must be in [1, %d]", L,
+                  TCAVT_ATTN_STREAM_MAX_L);
+  TCAVT_CHECK_ARG(nkv > 0 && nq > 0 && nq % nkv == 0 && nq / nkv <= 8, "attn_causal_gqa_stream: nq/nkv must be an integer <= 8");
+  TCAVT_CHECK_ARG(aligned16(qkv) && aligned16(out), "attn_causal_gqa_stream: unaligned pointer");
+  const int group = nq / nkv;
+  const bool f16 = dtype16 == TCAVT_F16;
+  auto fn = f16 ? attn_causal_gqa_stream_kernel<true> : attn_causal_gqa_stream_kernel<false>;
+  static bool attr_set[2] = {false, false};
+  if (!attr_set[f16]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, AS_LDS);
+    if (e != hipSuccess) {
+      set_error("attn_causal_gqa_stream: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      return TCAVT_ERR_HIP;
+    }
+    attr_set[f16] = true;
+  }
+  const int nqc = (L + AS_QC - 1) / AS_QC, nbj = B * nkv;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(nbj * nqc)), dim3(2 * group * 64), AS_LDS, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(out), kv_len, L, nq, nkv, nqc, nbj,
+                     scale * 1.4426950408889634f, lse);
+  TCAVT_CHECK_LAUNCH("attn_causal_gqa_stream");
+  return TCAVT_OK;
+}
 
 extern "C" int tcavt_attn_causal_gqa(const void* qkv, void* out, const int32_t* kv_len, int B, int L,
                                      int nq, int nkv, float scale, int dtype16, tcavt_stream_t stream) {

@@ -5,6 +5,8 @@
 // Attention backward: attn_bwd_scores_kernel (query-major: row statistics, dQ) + attn_bwd_dkv_kernel (key-major: dK, dV),
 // both on the matrix cores, nothing of S / P / dS stored; the GEMM-composed forms (llm_backward.attn_bwd_composed) and the
 // scalar-FMA attn_causal_gqa_bwd_kernel are cross-checks, not product paths.
+#include <string>
+
 #include "common.hpp"
 #include "philox.hpp"
 #include <stdlib.h>
@@ -2113,17 +2115,21 @@ extern "C" int tcavt_attn_bwd_resident_ok(int T, int nq, int nkv) {
   return T > 0 && T <= 256 && nkv > 0 && nq % nkv == 0 && ABQ_WAVES % (nq / nkv) == 0;
 }
 
-// The same backward in chunks of 256 keys / queries (attn_bwd_dq_long_kernel, attn_bwd_dkv_long_kernel): any T <= 544
-extern "C" int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16,
-                                   float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T,
-                                   int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream) {
+static std::string launch_name(const char* who, const char* part) { return std::string(who) + part; }
+
+// The same backward in chunks of 256 keys / queries (attn_bwd_dq_long_kernel, attn_bwd_dkv_long_kernel).  Neither kernel
+// depends on T: the LDS images are those of one chunk, both walk (T + 255) / 256 chunks, every row index is a long.
+// `who` names the entry point in the messages, `max_T` is its cap (tcavt_attn_bwd_long: 544, tcavt_attn_bwd_stream: 2048).
+static int attn_bwd_chunked(const char* who, int max_T, const void* qkv16, const void* dO16, const void* att16, const float* lse,
+                            void* g_qkv16, float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B,
+                            int T, int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(qkv16 && dO16 && att16 && lse && g_qkv16 && stats && rope_cos && rope_sin && kv_len && B > 0 && T > 0 && is16(dtype16),
-                  "attn_bwd_long: bad args");
-  TCAVT_CHECK_ARG(head_dim == 64 && nkv > 0 && nq > 0 && nq % nkv == 0, "attn_bwd_long: head_dim 64 and nq %% nkv == 0 required");
-  TCAVT_CHECK_ARG(T <= ABL_MAX_T && ABQ_WAVES % (nq / nkv) == 0,
-                  "attn_bwd_long: T=%d, nq / nkv = %d outside the chunked form (T <= %d, 16 %% (nq / nkv) == 0)", T, nq / nkv, ABL_MAX_T);
+                  "%s: bad args", who);
+  TCAVT_CHECK_ARG(head_dim == 64 && nkv > 0 && nq > 0 && nq % nkv == 0, "%s: head_dim 64 and nq %% nkv == 0 required", who);
+  TCAVT_CHECK_ARG(T <= max_T && ABQ_WAVES % (nq / nkv) == 0,
+                  "%s: T=%d, nq / nkv = %d outside the chunked form (T <= %d, 16 %% (nq / nkv) == 0)", who, T, nq / nkv, max_T);
   TCAVT_CHECK_ARG(aligned16(qkv16) && aligned16(dO16) && aligned16(att16) && aligned16(stats) && aligned16(g_qkv16),
-                  "attn_bwd_long: 16-byte alignment required");
+                  "%s: 16-byte alignment required", who);
   const bool f16 = dtype16 == TCAVT_F16;
   const int group = nq / nkv, U = group < 2 ? group : 2;
   typedef void (*dq_fn)(const bf16_t*, const bf16_t*, const bf16_t*, const float*, float*, const int*, int, int, int, int, int, float,
@@ -2140,7 +2146,7 @@ extern "C" int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const vo
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
     if (e != hipSuccess) {
-      tcavt::set_error("attn_bwd_long: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      tcavt::set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
       return TCAVT_ERR_HIP;
     }
     attr_set[f16][ui] = true;
@@ -2152,16 +2158,36 @@ extern "C" int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const vo
   const int nqc = (T + QC - 1) / QC, nkc = (T + ABL_CHUNK - 1) / ABL_CHUNK, nbj = B * nkv;
   hipLaunchKernelGGL(kq, dim3((unsigned)(nbj * nqc)), dim3(ABQ_WAVES * 64), lds_q, st, q_, g_, static_cast<const bf16_t*>(att16), lse,
                      stats, kv_len, T, nq, nkv, nqc, nbj, scale, static_cast<bf16_t*>(g_qkv16), rope_cos, rope_sin);
-  TCAVT_CHECK_LAUNCH("attn_bwd_long(dq)");
+  TCAVT_CHECK_LAUNCH(launch_name(who, "(dq)").c_str());
   hipLaunchKernelGGL(kr, dim3((unsigned)(nbj * nkc)), dim3(1024), lds_kv, st, q_, g_, static_cast<const float*>(stats), kv_len, T, nq,
                      nkv, nbj, scale, static_cast<bf16_t*>(g_qkv16), rope_cos, rope_sin);
-  TCAVT_CHECK_LAUNCH("attn_bwd_long(dkv)");
+  TCAVT_CHECK_LAUNCH(launch_name(who, "(dkv)").c_str());
   return TCAVT_OK;
+}
+
+extern "C" int tcavt_attn_bwd_long(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16,
+                                   float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T,
+                                   int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream) {
+  return attn_bwd_chunked("attn_bwd_long", ABL_MAX_T, qkv16, dO16, att16, lse, g_qkv16, stats, rope_cos, rope_sin, kv_len, B, T, nq,
+                          nkv, head_dim, scale, dtype16, stream);
 }
 
 // where the dispatch (llm_backward.attn_bwd_composed, tcavt_llama_stack_backward) takes the chunked form
 extern "C" int tcavt_attn_bwd_long_ok(int T, int nq, int nkv) {
   return T > 256 && T <= ABL_MAX_T && nkv > 0 && nq > 0 && nq % nkv == 0 && ABQ_WAVES % (nq / nkv) == 0;
+}
+
+// The chunked form beyond 544 (stage 1 truncates its text to 1024 tokens: L up to 1040): the same two launches under the
+// cap of the streaming forward, TCAVT_ATTN_STREAM_MAX_L
+extern "C" int tcavt_attn_bwd_stream(const void* qkv16, const void* dO16, const void* att16, const float* lse, void* g_qkv16,
+                                     float* stats, const float* rope_cos, const float* rope_sin, const int32_t* kv_len, int B, int T,
+                                     int nq, int nkv, int head_dim, float scale, int dtype16, tcavt_stream_t stream) {
+  return attn_bwd_chunked("attn_bwd_stream", TCAVT_ATTN_STREAM_MAX_L, qkv16, dO16, att16, lse, g_qkv16, stats, rope_cos, rope_sin,
+                          kv_len, B, T, nq, nkv, head_dim, scale, dtype16, stream);
+}
+
+extern "C" int tcavt_attn_bwd_stream_ok(int T, int nq, int nkv) {
+  return T > ABL_MAX_T && T <= TCAVT_ATTN_STREAM_MAX_L && nkv > 0 && nq > 0 && nq % nkv == 0 && ABQ_WAVES % (nq / nkv) == 0;
 }
 
 #define TCAVT_TRY(call)            \
@@ -2182,9 +2208,12 @@ extern "C" int tcavt_llama_stack_backward(const tcavt_llama_backward_args* a, tc
   // streams, whose backward is the per-launch composition of llm_backward.py); head_dim 64, adapters in 16-column groups
   TCAVT_CHECK_ARG(dt == TCAVT_F16, "llama_stack_backward: dtype16 must be TCAVT_F16 (16-bit stream tapes exist for fp16 storage only)");
   const int M = B * L, nqkv = (nq + 2 * nkv) * 64;
-  const bool att_long = !tcavt_attn_bwd_resident_ok(L, nq, nkv);  // 256 < L <= 544: the chunked attention backward
-  TCAVT_CHECK_ARG((!att_long || tcavt_attn_bwd_long_ok(L, nq, nkv)) && M % 256 == 0 && I % 256 == 0 && H % 128 == 0,
-                  "llama_stack_backward: outside the fused forms (L <= 544, 16 %% (nq / nkv) == 0, M %% 256 == 0, I %% 256 == 0, H %% 128 == 0)");
+  // L <= 256: resident; 256 < L <= 544: chunked (tcavt_attn_bwd_long); 544 < L <= 2048: chunked (tcavt_attn_bwd_stream)
+  const bool att_long = !tcavt_attn_bwd_resident_ok(L, nq, nkv);
+  const bool att_stream = att_long && !tcavt_attn_bwd_long_ok(L, nq, nkv);
+  TCAVT_CHECK_ARG((!att_long || tcavt_attn_bwd_long_ok(L, nq, nkv) || tcavt_attn_bwd_stream_ok(L, nq, nkv)) && M % 256 == 0 &&
+                      I % 256 == 0 && H % 128 == 0,
+                  "llama_stack_backward: outside the fused forms (L <= 2048, 16 %% (nq / nkv) == 0, M %% 256 == 0, I %% 256 == 0, H %% 128 == 0)");
   TCAVT_CHECK_ARG(!a->leaf_stream || a->events, "llama_stack_backward: a leaf stream needs the four events");
   // every layer's pointers are checked BEFORE anything is launched: an argument error must not leave half a walk enqueued
   // (adapter gradients half-written, the leaf stream forked and never joined -- under a hipGraph capture an unjoined stream)
@@ -2239,7 +2268,7 @@ extern "C" int tcavt_llama_stack_backward(const tcavt_llama_backward_args* a, tc
     const int par = li & 1;
     if (two && leaf_used[par])  // the leaf of layer li + 2 has read g_qkv / g_t of this parity
       TCAVT_TRY(hip_ok(hipStreamWaitEvent(st, static_cast<hipEvent_t>(a->events[2 + par]), 0), "wait(done)"));
-    TCAVT_TRY((att_long ? tcavt_attn_bwd_long : tcavt_attn_bwd_resident)(w.qkv, a->g_att, w.att, w.lse, g_qkv2[par], a->stats, a->rope_cos,
+    TCAVT_TRY((att_stream ? tcavt_attn_bwd_stream : att_long ? tcavt_attn_bwd_long : tcavt_attn_bwd_resident)(w.qkv, a->g_att, w.att, w.lse, g_qkv2[par], a->stats, a->rope_cos,
                                                                          a->rope_sin, a->kv_len, B, L, nq, nkv, 64, 0.125f, dt, stream));
     TCAVT_TRY(gemm(g_qkv2[par], nqkv, w.b_extT, nqkv, g_t2[par], 64, a->lora_scale));
     // ---- leaf: the adapters' weight gradients (nothing downstream reads them)

@@ -200,6 +200,11 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
   TCAVT_CHECK_ARG(a->lora_dropout_p >= 0.f && a->lora_dropout_p < 1.f, "llama_stack_forward: lora_dropout_p must be in [0, 1)");
   TCAVT_CHECK_ARG((a->k_cache == nullptr) == (a->v_cache == nullptr) && (!a->k_cache || a->kv_lmax >= a->L),
                   "llama_stack_forward: k_cache / v_cache go together, kv_lmax >= L");
+  // attention: K and V^T of a kv head resident in LDS up to TCAVT_ATTN_RESIDENT_MAX_L rows, streamed in key chunks beyond (refused before any launch
+  // past the streaming entry's cap)
+  TCAVT_CHECK_ARG(a->L <= TCAVT_ATTN_STREAM_MAX_L, "llama_stack_forward: L=%d exceeds the decoder attention's limit of %d", a->L,
+                  TCAVT_ATTN_STREAM_MAX_L);
+  const bool attn_stream = a->L > TCAVT_ATTN_RESIDENT_MAX_L;
   const int M = a->B * a->L, H = a->H, I = a->I, nq = a->nq, nkv = a->nkv;
   const int nqkv = (nq + 2 * nkv) * 64, dt = a->dtype16;
   // partial sums of squares per row: what the producer of each fused norm's input writes (embedding kernel and down_proj
@@ -272,7 +277,8 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
     ev.rec(2);
     TCAVT_CHECK_ARG((w.tape_att != nullptr) == (w.tape_lse != nullptr), "llama_stack_forward: layer %d: tape_att and tape_lse come together", li);
     void* att = tape && w.tape_att ? w.tape_att : a->att;
-    TCAVT_TRY(tcavt_attn_causal_gqa_lse(qkv, att, tape ? w.tape_lse : nullptr, a->kv_len, a->B, a->L, nq, nkv, scale, dt, stream));
+    TCAVT_TRY((attn_stream ? tcavt_attn_causal_gqa_stream : tcavt_attn_causal_gqa_lse)(qkv, att, tape ? w.tape_lse : nullptr, a->kv_len,
+                                                                                       a->B, a->L, nq, nkv, scale, dt, stream));
     ev.rec(3);
     // ---- h_mid = h + att . W_o^T; 16-bit copy + partial sums of squares for the post-attention norm
     {

@@ -77,6 +77,10 @@ def attn_bwd_composed(buf, qkv, dO, kv_len, B, T, nq, nkv, scale, cos, sin, g_qk
             # 256 < T <= 544: the same two launches over chunks of 256 keys / queries (the tiled kernels below stay as the
             # cross-check and the baseline behind the switch)
             return ops.attn_bwd_long(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
+        if (lse is not None and ops.attn_bwd_stream_ok(T, nq, nkv) and cos.shape[0] >= T
+                and os.environ.get("TCAVT_ATTN_BWD_NO_STREAM") is None):
+            # 544 < T <= 2048 (stage 1 at its own max_length): the chunked kernels under the higher cap
+            return ops.attn_bwd_stream(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
         g32 = buf("at.g32", (B * T, nqkv), f32)
         # (lse / att from the forward's tape: the scores kernel sweeps the keys once, not twice)
         ops.attn_bwd_scores(qkv, dO, None, None, None, kv_len, B, T, Tp, nq, nkv, scale, dQ=g32, stats=stats, lse=lse, att=att)
@@ -131,13 +135,14 @@ class LoraBackward:
         return self.ws.get(f"llbw.{name}.{str(dtype)[6:]}", shape, dtype, self.book.grads.device, zero=zero)
 
     def _stage_call_ok(self, tape, st, B, L, M, H, I, nq, nkv, r, fuse_silu, dev):
-        """Shapes / tapes the C++ stage call serves (everything the fp16-contract product path produces at L <= 544)."""
+        """Shapes / tapes the C++ stage call serves (everything the fp16-contract product path produces at L <= 2048)."""
         if dev.type != "cuda" or os.environ.get("TCAVT_PY_LLM_BACKWARD", "0") == "1" or not fuse_silu or H % 128 or r > 16:
             return False
         if any(os.environ.get(k) for k in ("TCAVT_ATTN_BWD_TWO_SWEEPS", "TCAVT_ATTN_BWD_NO_RESIDENT", "TCAVT_ATTN_BWD_NO_LONG",
-                                              "TCAVT_LORA_LEAF_UNFUSED")):
+                                              "TCAVT_ATTN_BWD_NO_STREAM", "TCAVT_LORA_LEAF_UNFUSED")):
             return False  # (A/B switches of the Python composition)
-        if (not (ops.attn_bwd_resident_ok(L, nq, nkv) or ops.attn_bwd_long_ok(L, nq, nkv)) or st != torch.float16
+        if (not (ops.attn_bwd_resident_ok(L, nq, nkv) or ops.attn_bwd_long_ok(L, nq, nkv) or ops.attn_bwd_stream_ok(L, nq, nkv))
+                or st != torch.float16
                 or self.lw.shape.head_dim != 64):
             return False  # (the stage call walks fp16 stream tapes with head_dim 64; anything else: the composition below)
         return all(sv.h_in.dtype == st and getattr(sv, "lse", None) is not None and getattr(sv, "part", None) is not None

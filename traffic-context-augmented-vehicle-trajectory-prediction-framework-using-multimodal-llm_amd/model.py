@@ -960,6 +960,10 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         ``None``: the [B * L, V] logits are never stored."""
         B, L, H = inputs_embeds.shape
         dev = inputs_embeds.device
+        if L > ops.ATTN_STREAM_MAX_L:  # (before anything is launched; tcavt_llama_stack_forward refuses it as well)
+            from . import capi
+
+            raise capi.TcavtError(f"LlamaWithCrossAttnPEFT: L={L} exceeds the decoder attention's limit of {ops.ATTN_STREAM_MAX_L}")
         if self.stream16:
             h = None
             ops.rownorm_prep(inputs_embeds.reshape(B * L, H).float().contiguous(), *self.norm_inputs(B * L, dev),
@@ -1079,14 +1083,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
         (MultiModalTrajectoryModel.pipeline_decoder) alternates them, the head of pass i still reads one while pass i + 1
         writes the other."""
         if input_ids is None or attention_mask is None:
-            # tokenizer branch (train.py:556-575): context_str alone, tokenised with padding + truncation, no labels
-            if self.tokenizer is None or context_str is None:
-                raise NotImplementedError(
-                    "the tokenizer branch (train.py:556-575) needs a tokenizer that cannot be fetched offline: attach one "
-                    "(model.tokenizer = ...) or pass input_ids/attention_mask as custom_collate_fn produces them")
-            enc = self.tokenizer(context_str, return_tensors="pt", padding=True, truncation=True)
-            input_ids = enc["input_ids"].to(vision_embs.device)
-            attention_mask = enc["attention_mask"].to(vision_embs.device)
+            input_ids, attention_mask = self.tokenize_context(context_str, vision_embs.device)
             labels = None
         B, Lt = input_ids.shape
         dev, H, ws = vision_embs.device, self.llama_hidden_size, self._ws
@@ -1094,6 +1091,9 @@ class LlamaMultiModal(nn.Module, _Prepared):
         LW = self.llama_wrapper
         Nq = self.qformer.num_query_tokens
         L = Nq + Lt
+        if L > ops.ATTN_STREAM_MAX_L:  # (before anything is launched; the decoder stack refuses it as well)
+            raise ValueError(f"LlamaMultiModal: {Nq} image tokens + {Lt} text tokens = {L} rows exceed the decoder attention's "
+                             f"limit of {ops.ATTN_STREAM_MAX_L}")
         pf, self._pf = self._pf, None
         want = self.qformer.dctx  # (train mode) the masks this forward must use; a prefetch made for them carries the same
         if pf is not None and pf[0] == self._pf_key(vision_embs) and \
@@ -1131,6 +1131,16 @@ class LlamaMultiModal(nn.Module, _Prepared):
         if return_bf16:
             return final, Nq, final_b
         return final, Nq
+
+    def tokenize_context(self, context_str, device):
+        """The tokenizer branch (train.py:556-575): context_str alone, tokenised with padding + truncation (host work only,
+        nothing is launched) -> (input_ids, attention_mask) on `device`."""
+        if self.tokenizer is None or context_str is None:
+            raise NotImplementedError(
+                "the tokenizer branch (train.py:556-575) needs a tokenizer that cannot be fetched offline: attach one "
+                "(model.tokenizer = ...) or pass input_ids/attention_mask as custom_collate_fn produces them")
+        enc = self.tokenizer(context_str, return_tensors="pt", padding=True, truncation=True)
+        return enc["input_ids"].to(device), enc["attention_mask"].to(device)
 
     def lm_forward(self, vision_embs, context_str, input_ids=None, attention_mask=None, labels=None):
         """The MLLM pass with the LM loss on `labels` [B, Lt] (what train.py:536-552 hands to the LLM as fused labels: the
@@ -1707,6 +1717,8 @@ class TransformerLTSF(nn.Module, _Prepared):
 # MultiModalTrajectoryModel (train.py:847-964)
 # --------------------------------------------------------------------------------------
 class MultiModalTrajectoryModel(nn.Module):
+    HEAD_MAX_L = 544  # decoder rows (image tokens + text) the trajectory head's cross-attention buffers are sized for
+
     def __init__(self, seq_len, out_len, individual, feature_size=2, d_model=64, lane_polygon_d_model=64,
                  lane_polygon_nhead=4, lane_polygon_layers=2, max_polygon_points=64, use_post_mlp=True,
                  post_mlp_hidden_dim=64, base_model_name="meta-llama/Llama-3.2-1B", use_lora=True, lora_r=8,
@@ -1868,8 +1880,25 @@ class MultiModalTrajectoryModel(nn.Module):
         return self._forward(x, vision_embs, context_str, lane_polygon_batch, lane_polygon_len, y=y, norm_stat=norm_stat,
                              input_ids=input_ids, attention_mask=attention_mask, labels=labels)
 
+    def _check_head_limit(self, input_ids):
+        """The trajectory path keeps L <= 544 (train.py truncates its text to 512; the head's cross-attention is sized for
+        that).  The decoder itself serves L <= 2048, so the refusal is made here, before anything is launched."""
+        if input_ids is None:  # (an MLLM pass cached by evaluate_model(reuse_prefix=True): checked when it was made)
+            return
+        L = self.mllm.qformer.num_query_tokens + input_ids.shape[1]
+        if L > self.HEAD_MAX_L:
+            raise ValueError(f"MultiModalTrajectoryModel: L = {L} decoder rows exceed the trajectory head's limit of "
+                             f"{self.HEAD_MAX_L}; longer text is served by the stage-1 entry points of the MLLM alone "
+                             "(mllm.lm_forward, mllm.lm_evaluate, mllm.generate_batch, training.MllmTrainer, "
+                             "evaluate.evaluate_mllm), up to 2048 rows")
+
     def _forward(self, x, vision_embs, context_str, lane_polygon_batch, lane_polygon_len, y=None, norm_stat=None,
                  input_ids=None, attention_mask=None, labels=None):
+        if (input_ids is None or attention_mask is None) and self._llm_cache is None:
+            # tokenizer branch: tokenised here (host work) so that the length is known before anything is launched
+            input_ids, attention_mask = self.mllm.tokenize_context(context_str, vision_embs.device)
+            labels = None
+        self._check_head_limit(input_ids)
         self._n_forward += 1
         if self._bridge is not None and not self.driven_by_trainer:
             self._bridge.refresh()  # (a model that has trained through loss.backward(): rebuild stale packed weights first)

@@ -385,6 +385,26 @@ def attn_causal_gqa(qkv, out, kv_len, B, L, nq, nkv, scale, lse=None):
                                           scale, _DT[qkv.dtype], stream_ptr()), "tcavt_attn_causal_gqa")
 
 
+ATTN_RESIDENT_MAX_L = 544  # tcavt_attn_causal_gqa(_lse): K and V^T of a (sample, kv head) resident in LDS
+ATTN_STREAM_MAX_L = 2048   # TCAVT_ATTN_STREAM_MAX_L: tcavt_attn_causal_gqa_stream, tcavt_attn_bwd_stream
+
+
+def attn_causal_gqa_stream(qkv, out, kv_len, B, L, nq, nkv, scale, lse=None):
+    """attn_causal_gqa with K and V^T streamed through LDS in chunks of 256 keys (tcavt_attn_causal_gqa_stream): the same
+    arguments, semantics and lse convention, 1 <= L <= ATTN_STREAM_MAX_L.  The decoder stack takes it for L > 544."""
+    _req16(qkv, "attn_stream.qkv")
+    _req16(out, "attn_stream.out", like=qkv)
+    _req(kv_len, torch.int32, "attn_stream.kv_len")
+    _need(qkv, B * L * (nq + 2 * nkv) * 64, "attn_stream.qkv")
+    _need(out, B * L * nq * 64, "attn_stream.out")
+    _need(kv_len, B, "attn_stream.kv_len")
+    if lse is not None:
+        _req(lse, torch.float32, "attn_stream.lse")
+        _need(lse, B * nq * L, "attn_stream.lse")
+    check(lib().tcavt_attn_causal_gqa_stream(ptr(qkv), ptr(out), ptr(lse) if lse is not None else None, ptr(kv_len), B, L, nq,
+                                             nkv, scale, _DT[qkv.dtype], stream_ptr()), "tcavt_attn_causal_gqa_stream")
+
+
 def mha(q, k, v, out, B, Lq, Lk, nh, dh, scale, key_len=None, ldq=None, ldk=None, ldv=None, ldo=None, dropout=None):
     """q/k/v may be column slices of wider row-major buffers: pass the slice's data_ptr tensor and ld."""
     in_dt, out_dt = _DT[q.dtype], _DT[out.dtype]
@@ -737,6 +757,16 @@ def attn_bwd_long_ok(T, nq, nkv):
 def attn_bwd_long(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale):
     """attn_bwd_resident in chunks of 256 keys / queries (tcavt_attn_bwd_long): same arguments and outputs, any T <= 544."""
     return _attn_bwd_two_launch("attn_bwd_long", qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
+
+
+def attn_bwd_stream_ok(T, nq, nkv):
+    """Shapes the dispatch hands to the chunked backward beyond 544 (544 < T <= 2048, 16 % (nq / nkv) == 0)."""
+    return bool(lib().tcavt_attn_bwd_stream_ok(T, nq, nkv))
+
+
+def attn_bwd_stream(qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale):
+    """attn_bwd_long under the cap of the streaming forward (tcavt_attn_bwd_stream): same arguments and outputs, any T <= 2048."""
+    return _attn_bwd_two_launch("attn_bwd_stream", qkv, dO, att, lse, g_qkv, stats, cos, sin, kv_len, B, T, nq, nkv, scale)
 
 
 def gqa_rope_bwd_pack(G3, out, cos, sin, nq, nkv, L):
