@@ -26,6 +26,7 @@
 #ifndef TCAVT_H
 #define TCAVT_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -150,7 +151,10 @@ typedef struct tcavt_gemm_args {
   /* Layout of W.  0: row-major [N][ldw].  TCAVT_W_FRAG16 (1): the fragment-major copy tcavt_pack_weight16 makes -- skinny form
    * only (M <= 32, tile 0: the decode step; refused elsewhere), ldw == K.  Same arithmetic in the same order: bit-identical
    * results; what changes is that one wave instruction reads 1 KiB of consecutive bytes instead of 16 rows x 64 bytes that are
-   * K * 2 bytes apart (decode step 1.09 -> 0.91 ms at B = 8: the weight stream was bound by its access pattern, not by HBM) */
+   * K * 2 bytes apart (decode step 1.09 -> 0.91 ms at B = 8: the weight stream was bound by its access pattern, not by HBM).
+   * TCAVT_W_FRAG8 (2): the FP8 copy tcavt_pack_weight8 makes (e4m3 codes in the same order + one power-of-two scale per row),
+   * accepted and refused exactly where TCAVT_W_FRAG16 is.  The codes are converted to the 16-bit operand type on the way into the
+   * same MFMAs and the fp32 partial sums multiplied by the row scales: bit-identical to TCAVT_W_FRAG16 on the dequantised matrix */
   int32_t w_layout;
   /* TCAVT_EPI_SILU_MUL only, optional: a bf16 copy of the gate|up pre-activations [M, N] (interleaved layout, leading
    * dimension ld_preact) next to the activated output -- what the backward of silu(gate)*up needs (tcavt_silu_mul_bwd) */
@@ -1136,7 +1140,8 @@ typedef struct tcavt_decode_args {
                                       per layer less); adapters of rank <= 8 only (lora_rank), B <= 32, NULL = a launch per layer */
   int32_t lora_rank;
   float stream_scale;              /* as tcavt_llama_stack_args.stream_scale (0 means 1) */
-  int32_t w_layout;                /* 0, or TCAVT_W_FRAG16: layers[].w_qkv / w_o / w_gu / w_d point to tcavt_pack_weight16 copies */
+  int32_t w_layout;                /* 0, or TCAVT_W_FRAG16: layers[].w_qkv / w_o / w_gu / w_d point to tcavt_pack_weight16 copies; or
+                                      TCAVT_W_FRAG8: they and table_packed (required then) point to tcavt_pack_weight8 copies */
   int32_t act_layout;              /* 0; 1: h16, att, act and x16 are kept in fragment-major order (tcavt_gemm_args.act_layout; each
                                       buffer then holds 16 (B <= 16) or 32 whole rows, B <= 32); 2: the same in ONE block of 8
                                       tokens (TCAVT_ACT_BLOCK8; buffers of 8 whole rows, B <= 8).  Needs h == NULL */
@@ -1157,6 +1162,23 @@ int tcavt_llama_decode_step(const tcavt_decode_args* args, tcavt_stream_t stream
 #define TCAVT_ACT_OUT_FRAG16 2
 #define TCAVT_ACT_BLOCK8 4
 int tcavt_pack_weight16(const void* W, int64_t ldw, void* out, int N, int K, tcavt_stream_t stream);
+
+/* FP8 copy of a 16-bit weight matrix W [N][ldw] (dtype16 = TCAVT_F16 / TCAVT_BF16; N % 16 == 0, K % 32 == 0, 16-byte alignment)
+ * for the skinny form (tcavt_gemm_args.w_layout = TCAVT_W_FRAG8): half the bytes of the decode step's weight stream, weight-only
+ * (activations, accumulation and the KV cache stay as they are).  out holds tcavt_pack_weight8_bytes(N, K) = N * K + 4 * N bytes:
+ *   codes   N * K bytes, the tcavt_pack_weight16 order at one byte per element: block b (rows 16 b .. 16 b + 15), k-step j
+ *           (columns 32 j .. 32 j + 31) is the 512-byte chunk (b * K / 32 + j), and lane l = 16 q + r of the consuming wave finds
+ *           its eight codes W[16 b + r][32 j + 8 q .. + 7] at byte 8 l of the chunk
+ *   scales  N fp32 values at byte offset N * K, in row order, each exactly 2^k: k is the smallest integer with
+ *           amax * 2^-k <= 448 (amax = the row's largest magnitude); an all-zero row has k = 0
+ * A code is the OCP e4m3fn value nearest to the exact product W[n][j] * 2^-k, ties to even.  A power-of-two scale costs no
+ * precision in a floating-point format: code * 2^k is an f16 and a bf16 value (short of their subnormal range), and so is
+ * the product with an fp32 accumulator.  A row with a non-finite element gets the NaN code (0x7f) everywhere and scale 1: the
+ * products it feeds come out as NaN and reach tcavt_gemm_args.nonfinite_flag like any other.
+ * The reference has no counterpart: a storage format of the frozen weights, made once per checkpoint. */
+#define TCAVT_W_FRAG8 2
+size_t tcavt_pack_weight8_bytes(int N, int K);
+int tcavt_pack_weight8(const void* W, int64_t ldw, int dtype16, void* out, int N, int K, tcavt_stream_t stream);
 
 /* hipEvent helpers for tcavt_llama_stack_args.events (timing enabled); elapsed time in milliseconds between two
  * recorded events after the stream has been synchronised by the caller */

@@ -22,6 +22,7 @@ EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_SILU_MUL, EPI_ROPE, EPI_BIAS_ROW, EPI_ACCU
 EPI_NORM_OUT, EPI_ROWSCALE, EPI_SILU_BWD = 128, 256, 512
 ACT_A_FRAG16, ACT_OUT_FRAG16, ACT_BLOCK8 = 1, 2, 4  # tcavt_gemm_args.act_layout
 W_FRAG16 = 1  # tcavt_gemm_args.w_layout / tcavt_decode_args.w_layout: tcavt_pack_weight16 copy
+W_FRAG8 = 2  # the same fields: tcavt_pack_weight8 copy (e4m3 codes + power-of-two row scales)
 
 c_void_p, c_int, c_int64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
@@ -334,6 +335,8 @@ _SIGNATURES = {
     "tcavt_llama_decode_step": [ctypes.POINTER(DecodeArgs), c_void_p],
     "tcavt_norm_npart": [c_int, c_int, c_int],
     "tcavt_pack_weight16": [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p],
+    "tcavt_pack_weight8_bytes": [c_int, c_int],
+    "tcavt_pack_weight8": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p],
     "tcavt_lora_down": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, ctypes.c_uint64, ctypes.c_uint32,
                         ctypes.c_uint32, c_int, c_void_p],
     "tcavt_rownorm_prep": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p],
@@ -357,7 +360,7 @@ _SIGNATURES = {
     "tcavt_lm_eval_workspace_bytes": [c_int64, c_int, c_int],
     "tcavt_lm_eval": [ctypes.POINTER(LmEvalArgs), c_void_p],
 }
-_RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64,
+_RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

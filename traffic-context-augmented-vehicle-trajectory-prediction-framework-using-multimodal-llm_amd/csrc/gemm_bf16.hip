@@ -96,6 +96,19 @@ extern "C" int tcavt_pack_weight16(const void* W, int64_t ldw, void* out, int N,
   return TCAVT_OK;
 }
 
+extern "C" size_t tcavt_pack_weight8_bytes(int N, int K) { return N > 0 && K > 0 ? (size_t)N * K + 4 * (size_t)N : 0; }
+
+extern "C" int tcavt_pack_weight8(const void* W, int64_t ldw, int dtype16, void* out, int N, int K, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(W && out && W != out && N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0 && ldw >= K && ldw % 8 == 0 && is16(dtype16),
+                  "pack_weight8: N %% 16 == 0, K %% 32 == 0, ldw >= K, ldw %% 8 == 0, out != W, dtype16 = TCAVT_F16 / TCAVT_BF16");
+  TCAVT_CHECK_ARG(aligned16(W) && aligned16(out), "pack_weight8: 16-byte alignment required");
+  auto kfn = dtype16 == TCAVT_F16 ? pack_weight8_kernel<true> : pack_weight8_kernel<false>;
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(N / 16)), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(W), (long)ldw,
+                     static_cast<unsigned char*>(out), N, K);
+  TCAVT_CHECK_LAUNCH("pack_weight8");
+  return TCAVT_OK;
+}
+
 extern "C" int tcavt_gemm_bf16(const tcavt_gemm_args* a, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(a != nullptr, "gemm_bf16: null args");
   const bool stream16 = (a->epilogue & TCAVT_EPI_NORM_OUT) && a->C == nullptr;  // 16-bit residual stream in norm_h16
@@ -200,11 +213,11 @@ extern "C" int tcavt_gemm_bf16(const tcavt_gemm_args* a, tcavt_stream_t stream) 
     }
   }
   if (a->w_layout != 0) {
-    TCAVT_CHECK_ARG(a->w_layout == TCAVT_W_FRAG16 && a->tile == 0 && skinny_shape(a->M, a->K) && batch == 1 && a->dropout_p == 0.f &&
-                        a->lda >= a->K && a->ldw == a->K && a->N % 16 == 0,
-                    "gemm_bf16: w_layout = TCAVT_W_FRAG16 (tcavt_pack_weight16 copy) goes with the skinny form only (M <= 32, "
-                    "K %% 256 == 0, N %% 16 == 0, tile 0, ldw == K)");
-    p.w_frag = 1;
+    TCAVT_CHECK_ARG((a->w_layout == TCAVT_W_FRAG16 || a->w_layout == TCAVT_W_FRAG8) && a->tile == 0 && skinny_shape(a->M, a->K) && batch == 1 &&
+                        a->dropout_p == 0.f && a->lda >= a->K && a->ldw == a->K && a->N % 16 == 0,
+                    "gemm_bf16: w_layout = TCAVT_W_FRAG16 / TCAVT_W_FRAG8 (tcavt_pack_weight16 / tcavt_pack_weight8 copy) goes with the "
+                    "skinny form only (M <= 32, K %% 256 == 0, N %% 16 == 0, tile 0, ldw == K)");
+    p.w_frag = a->w_layout == TCAVT_W_FRAG8 ? 2 : 1;
   }
   if (a->lora_part) {
     // (decode step only: the skinny form; anything else is a caller error rather than a silent no-op)

@@ -57,7 +57,8 @@ struct GemmP {
   int sk_msplit;
   int a_frag, o_frag;  // skinny form: A / the 16-bit result in fragment-major order (tcavt_gemm_args.act_layout): 0, 1 = blocks of 16
                        // tokens, 2 = one block of 8 (common.hpp frag_off)
-  int w_frag;  // skinny form: W is the fragment-major copy of tcavt_pack_weight16 (tcavt_gemm_args.w_layout)
+  int w_frag;  // skinny form: W is the fragment-major copy of tcavt_pack_weight16 (1) or the FP8 copy of tcavt_pack_weight8 (2)
+               // (tcavt_gemm_args.w_layout)
   int sk_split;
   float* sk_slab;
   int* sk_cnt;

@@ -1,6 +1,7 @@
 // The skinny GEMM form (M <= 32 rows: the decode step), auto-selected by tcavt_gemm_bf16 for tile code 0.
 #pragma once
 #include "gemm_epilogue.hpp"
+#include <type_traits>
 
 namespace tcavt {
 
@@ -22,6 +23,26 @@ __device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f3
 
 constexpr int SK_WAVES = 8;
 
+// FP8 weight stream (tcavt_gemm_args.w_layout = TCAVT_W_FRAG8, tcavt.h: tcavt_pack_weight8): a lane's eight e4m3 codes of a k-step
+// (8 bytes) -> the 16-byte MFMA operand, four v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1 (exact: every e4m3 value is an f16 and
+// a bf16 value).  The power-of-two row scale is applied to the fp32 accumulators, not here.
+template <bool F16>
+__device__ __forceinline__ u32x4 fp8x8_to16(const u32x2& v) {
+  u32x4 o;
+  if constexpr (F16) {
+    o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[0], 1.0f, false));
+    o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[0], 1.0f, true));
+    o[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[1], 1.0f, false));
+    o[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[1], 1.0f, true));
+  } else {
+    o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, false));
+    o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, true));
+    o[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, false));
+    o[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, true));
+  }
+  return o;
+}
+
 // agent-scope store / load of four floats (relaxed atomics: global_store / global_load ... sc1, coherent across the XCDs)
 __device__ __forceinline__ void sk_store(float* ptr, f32x4 v) {
 #pragma unroll
@@ -34,7 +55,7 @@ __device__ __forceinline__ f32x4 sk_load(const float* ptr) {
   return v;
 }
 
-template <int EPI, int NCB, bool F16, bool NT>
+template <int EPI, int NCB, bool F16, bool NT, bool W8 = false>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
   __shared__ f32x4 red[SK_WAVES][NCB * 2][64];
   // fused LoRA down-projection, consumer side (RoPE form): group sums of the partials, then t as 16-bit rows [32][32]
@@ -76,11 +97,16 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
   const int kbeg = (ks * SK_WAVES + wave) * kper;
   // Weight fragments: row-major W -> 16 rows x 64 bytes per instruction, K * 2 bytes apart; fragment-major copy (w_frag,
   // tcavt_pack_weight16) -> the same 1 KiB as consecutive bytes, the wave's K slice one contiguous run (k advances 16 x as fast)
+  // FP8 copy (W8, tcavt_pack_weight8): the fragment-major order at one byte per element -- 512 bytes per k-step, 8 per lane;
+  // the N fp32 row scales follow the N * K codes
   const bf16_t* wp[NCB];
   const int wstep = p.w_frag ? 16 : 1;
 #pragma unroll
-  for (int c = 0; c < NCB; ++c)
-    wp[c] = p.w_frag ? p.W + (long)ncol[c] * p.K + (long)kbeg * 16 + lane * 8 : p.W + (long)(ncol[c] + r16) * p.ldw + kbeg + kq * 8;
+  for (int c = 0; c < NCB; ++c) {
+    if constexpr (W8) wp[c] = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(p.W) + (long)ncol[c] * p.K + (long)kbeg * 16 + lane * 8);
+    else wp[c] = p.w_frag ? p.W + (long)ncol[c] * p.K + (long)kbeg * 16 + lane * 8 : p.W + (long)(ncol[c] + r16) * p.ldw + kbeg + kq * 8;
+  }
+  f32x4 wsc[W8 ? NCB : 1];  // W8: the row scales 2^k of this lane's four output columns per column block
   const bf16_t* xp0 = p.A + (long)min(mrow0 + r16, p.M - 1) * p.lda + kbeg + kq * 8;
   const bf16_t* xp1 = p.A + (long)min(16 + r16, p.M - 1) * p.lda + kbeg + kq * 8;
   // fragment-major activations: the 16 tokens' fragments of a k-step are one 1 KiB run as well (rows >= M of a block hold
@@ -94,7 +120,9 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
     xp1 = p.A + (long)16 * p.K + (long)kbeg * 16 + lane * 8;
   }
   const bool two = p.M > 16 && p.sk_msplit <= 1;
-  constexpr int U = 4;  // k-steps in flight (8 made the decode step slower: 3.08 vs 2.60 ms in round 2, and again in round 3 for the residual forms alone: 1.155 vs 1.138; so did 16 waves with K / 16 slices each: 1.55 vs 1.34 ms)
+  constexpr int U = 4;  // k-steps in flight (8 made the decode step slower: 3.08 vs 2.60 ms in round 2, and again in round 3 for the residual forms alone: 1.155 vs 1.138; so did 16 waves with K / 16 slices each: 1.55 vs 1.34 ms;
+                        // FP8 weights, whose 8 k-steps hold the bytes of 4 here: 0.782 vs 0.757 ms at B = 8, 0.971 vs 0.941 at B = 32 --
+                        // the converted operands cost the registers the narrower loads save, occupancy 3 instead of 4)
   // Epilogue operands of the two finishing waves (wave mb completes token block mb), fetched while the first batch of weight
   // loads is in flight instead of after the K loop: the row scale's partial sums, the RoPE position -> cos / sin rows, the
   // 16-bit residual, and (wave 0) the LoRA second source.  Each of these was one more dependent global-memory round trip
@@ -155,13 +183,17 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
     }
   }
   for (int k = 0; k < kper; k += 32 * U) {
-    u32x4 wf[U][NCB], x0[U], x1[U];
+    typedef typename std::conditional<W8, u32x2, u32x4>::type wfrag_t;
+    wfrag_t wf[U][NCB];
+    u32x4 x0[U], x1[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (k + 32 * u < kper) {
 #pragma unroll
         for (int c = 0; c < NCB; ++c) {
-          const u32x4* wsrc = reinterpret_cast<const u32x4*>(wp[c] + (k + 32 * u) * wstep);
+          const wfrag_t* wsrc;
+          if constexpr (W8) wsrc = reinterpret_cast<const wfrag_t*>(reinterpret_cast<const char*>(wp[c]) + (k + 32 * u) * 16);
+          else wsrc = reinterpret_cast<const wfrag_t*>(wp[c] + (k + 32 * u) * wstep);
           wf[u][c] = NT ? __builtin_nontemporal_load(wsrc) : *wsrc;
         }
         x0[u] = *reinterpret_cast<const u32x4*>(xp0 + (k + 32 * u) * xstep);
@@ -181,6 +213,13 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
           for (int u = 0; u < 32; ++u) acc_t += i + u < lp_per ? tv[u] : 0.f;
         }
         lp_sum[threadIdx.x] = acc_t;
+      }
+    }
+    if constexpr (W8) {  // (every wave scales its own partial sums: requested under the first weight batch)
+      if (k == 0) {
+        const char* sc = reinterpret_cast<const char*>(p.W) + (long)p.N * p.K;
+#pragma unroll
+        for (int c = 0; c < NCB; ++c) wsc[c] = *reinterpret_cast<const f32x4*>(sc + (long)(ncol[c] + 4 * kq) * 4);
       }
     }
     if (k == 0 && wave < 2) {
@@ -262,10 +301,22 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(GemmP p) {
       if (k + 32 * u < kper) {
 #pragma unroll
         for (int c = 0; c < NCB; ++c) {
-          acc[c][0] = mfma16<F16>(wf[u][c], x0[u], acc[c][0]);
-          if (two) acc[c][1] = mfma16<F16>(wf[u][c], x1[u], acc[c][1]);
+          u32x4 wv;
+          if constexpr (W8) wv = fp8x8_to16<F16>(wf[u][c]);
+          else wv = wf[u][c];
+          acc[c][0] = mfma16<F16>(wv, x0[u], acc[c][0]);
+          if (two) acc[c][1] = mfma16<F16>(wv, x1[u], acc[c][1]);
         }
       }
+    }
+  }
+  // W8: the codes' partial sums times the rows' power-of-two scales (exact) -- here, before the 16-bit LoRA term below and the
+  // reductions, so that every later step sees what the 16-bit path computes on the dequantised matrix, bit for bit
+  if constexpr (W8) {
+#pragma unroll
+    for (int c = 0; c < NCB; ++c) {
+      acc[c][0] *= wsc[c];
+      acc[c][1] *= wsc[c];
     }
   }
   if constexpr (EPI == EPI_ROPE) {
@@ -496,7 +547,10 @@ static int launch_skinny(const GemmP& p, hipStream_t stream) {
   // workgroups the second reader wants the L2 copy.)
   static const bool no_nt = getenv("TCAVT_SK_NO_NT") != nullptr;  // (A/B switch)
   const dim3 grid(nblk * S * msplit), block(SK_WAVES * 64);
-  if (q.w_frag && msplit == 1 && !no_nt) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NCB, F16, true>), grid, block, 0, stream, q);
+  if (q.w_frag == 2) {  // FP8 copy (TCAVT_W_FRAG8)
+    if (msplit == 1 && !no_nt) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NCB, F16, true, true>), grid, block, 0, stream, q);
+    else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NCB, F16, false, true>), grid, block, 0, stream, q);
+  } else if (q.w_frag && msplit == 1 && !no_nt) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NCB, F16, true>), grid, block, 0, stream, q);
   else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NCB, F16, false>), grid, block, 0, stream, q);
   TCAVT_CHECK_LAUNCH("gemm_bf16(skinny)");
   return TCAVT_OK;

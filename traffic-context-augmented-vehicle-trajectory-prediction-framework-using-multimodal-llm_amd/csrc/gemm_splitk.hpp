@@ -23,6 +23,73 @@ __global__ __launch_bounds__(256) void pack_weight16_kernel(const bf16_t* __rest
 }
 
 // ---------------------------------------------------------------------------
+// FP8 copy of a weight matrix for the skinny form (tcavt.h: tcavt_pack_weight8): OCP e4m3fn codes in the fragment-major order
+// above at one byte per element, one power-of-two scale per row behind them.
+// ---------------------------------------------------------------------------
+// e4m3fn code of x, round to nearest even, for finite |x| <= 448 (the caller has scaled the row): normals keep three mantissa
+// bits (the carry of the rounding runs into the exponent field by itself); below 2^-6 the code is the integer nearest to
+// |x| * 2^9, ties to even (8 = the smallest normal).  Plain integer arithmetic, the same on the host.
+__host__ __device__ __forceinline__ unsigned int e4m3_code(float x) {
+  const unsigned int bits = __builtin_bit_cast(unsigned int, x);
+  const unsigned int sign = (bits >> 24) & 0x80u, a = bits & 0x7fffffffu;
+  if (a >= 0x3c800000u) return sign | (((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3));  // |x| >= 2^-6
+  return sign | (unsigned int)__builtin_rintf(__builtin_bit_cast(float, a) * 512.f);
+}
+
+// smallest k with amax * 2^-k <= 448 (= 0.875 * 2^9); amax finite and > 0
+__host__ __device__ __forceinline__ int e4m3_row_exp(float amax) {
+  int e;
+  const float m = __builtin_frexpf(amax, &e);  // amax = m * 2^e, m in [0.5, 1)
+  return m <= 0.875f ? e - 9 : e - 8;
+}
+
+// One workgroup per block of 16 rows; 16 consecutive lanes per row find its largest magnitude (and whether all of it is finite),
+// then thread t writes the 8-byte pieces t, t + 256, ... of the block's K / 32 chunks: piece (j, l) <- W[16 b + (l & 15)][32 j +
+// 8 (l >> 4) .. + 7] * 2^-k (exact: ldexp), rounded once.  A row with a non-finite element: the NaN code everywhere, scale 1.
+template <bool F16>
+__global__ __launch_bounds__(256) void pack_weight8_kernel(const bf16_t* __restrict__ W, long ldw, unsigned char* __restrict__ out, int N, int K) {
+  __shared__ int row_k[16];
+  __shared__ int row_bad[16];
+  const long b = blockIdx.x;
+  const int t = threadIdx.x, r = t >> 4, part = t & 15;
+  const bf16_t* row = W + (16 * b + r) * ldw;
+  unsigned int amax_bits = 0u;  // (non-negative floats order like their bit patterns; inf / NaN end up on top)
+  for (int c = part * 8; c < K; c += 128) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(row + c);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      amax_bits = max(amax_bits, __builtin_bit_cast(unsigned int, from16_lo<F16>(v[i])) & 0x7fffffffu);
+      amax_bits = max(amax_bits, __builtin_bit_cast(unsigned int, from16_hi<F16>(v[i])) & 0x7fffffffu);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) amax_bits = max(amax_bits, (unsigned int)__shfl_xor((int)amax_bits, o, 64));
+  if (part == 0) {
+    const bool bad = amax_bits >= 0x7f800000u;
+    const int k = (bad || amax_bits == 0u) ? 0 : e4m3_row_exp(__builtin_bit_cast(float, amax_bits));
+    row_k[r] = k;
+    row_bad[r] = bad;
+    reinterpret_cast<float*>(out + (long)N * K)[16 * b + r] = ldexpf(1.f, k);
+  }
+  __syncthreads();
+  const int pieces = (K >> 5) * 64;
+  unsigned char* dst = out + b * 16 * K;
+  for (int pc = t; pc < pieces; pc += 256) {
+    const int l = pc & 63, j = pc >> 6, rr = l & 15;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(W + (16 * b + rr) * ldw + 32 * j + 8 * (l >> 4));
+    const int k = row_k[rr];
+    u32x2 o = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned int lo = e4m3_code(ldexpf(from16_lo<F16>(v[i]), -k)), hi = e4m3_code(ldexpf(from16_hi<F16>(v[i]), -k));
+      o[i >> 1] |= (lo | (hi << 8)) << (16 * (i & 1));
+    }
+    if (row_bad[rr]) o = u32x2{0x7f7f7f7fu, 0x7f7f7f7fu};
+    *reinterpret_cast<u32x2*>(dst + (long)pc * 8) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Split K for residual GEMMs that cannot fill the chip (round 4).  At M = 1024 (BASELINE config 4's low end: B = 8, L = 128) the
 // o / down projections are 128 tiles of 128 x 128 -- half the CUs, one 4-wave workgroup each walking 32 / 128 K-tiles alone at
 // ~1 us per K-tile (its waves issue DMA, fragment loads and MFMAs one after the other; nothing else is resident to overlap

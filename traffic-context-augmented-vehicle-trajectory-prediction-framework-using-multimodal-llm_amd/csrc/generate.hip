@@ -832,10 +832,12 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
   TCAVT_CHECK_ARG(a->stream_scale >= 0.f && a->stream_scale <= 1.f, "llama_decode_step: stream_scale must be in (0, 1] (0 means 1)");
   const float ss_ = a->stream_scale == 0.f ? 1.f : a->stream_scale;
   const float eps_s = a->rms_eps * ss_ * ss_;
-  // fragment-major weight copies (tcavt_pack_weight16): the projections' weight streams read consecutive bytes
+  // fragment-major weight copies (tcavt_pack_weight16): the projections' weight streams read consecutive bytes; or their FP8
+  // form (tcavt_pack_weight8): half the bytes
   const int wl = a->w_layout;
-  TCAVT_CHECK_ARG(wl == 0 || (wl == TCAVT_W_FRAG16 && B <= 32 && I % 256 == 0 && (nq * 64) % 256 == 0),
-                  "llama_decode_step: w_layout must be 0 or TCAVT_W_FRAG16 (B <= 32, I %% 256 == 0, nq * 64 %% 256 == 0)");
+  TCAVT_CHECK_ARG(wl == 0 || ((wl == TCAVT_W_FRAG16 || wl == TCAVT_W_FRAG8) && B <= 32 && I % 256 == 0 && (nq * 64) % 256 == 0),
+                  "llama_decode_step: w_layout must be 0, TCAVT_W_FRAG16 or TCAVT_W_FRAG8 (B <= 32, I %% 256 == 0, nq * 64 %% 256 == 0)");
+  TCAVT_CHECK_ARG(wl != TCAVT_W_FRAG8 || a->table_packed, "llama_decode_step: TCAVT_W_FRAG8 needs table_packed (the tcavt_pack_weight8 copy of table)");
   // fragment-major activations: h16, att, act, x16 in the skinny GEMMs' operand order (16 or 32 whole rows each)
   const int al = a->act_layout;
   TCAVT_CHECK_ARG(al == 0 || ((al == 1 || al == 2) && a->h == nullptr && B <= (al == 2 ? 8 : 32) && I % 256 == 0 && (nq * 64) % 256 == 0),
@@ -930,7 +932,7 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
   // lm_head: tied to the embedding table (Llama-3.2-1B: tie_word_embeddings)
   tcavt_gemm_args g = {};
   g.A = a->x16; g.lda = H; g.W = a->table; g.ldw = H; g.C = a->logits; g.ldc = a->V;
-  if (a->table_packed && B <= 32) { g.W = a->table_packed; g.w_layout = TCAVT_W_FRAG16; }
+  if (a->table_packed && B <= 32) { g.W = a->table_packed; g.w_layout = wl == TCAVT_W_FRAG8 ? TCAVT_W_FRAG8 : TCAVT_W_FRAG16; }
   g.act_layout = gA;
   g.M = B; g.N = a->V; g.K = H; g.out_dtype = TCAVT_F32; g.in_dtype = dt;
   g.splitk_ws = a->splitk_ws; g.splitk_ws_bytes = a->splitk_ws_bytes;

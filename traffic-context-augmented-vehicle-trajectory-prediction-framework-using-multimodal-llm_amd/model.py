@@ -683,6 +683,7 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
     def _invalidate(self):
         self._prep_T = None
         self._prep_dec = None
+        self._prep_dec8 = None
         self._prep_tableT = None
         _Prepared._invalidate(self)
 
@@ -748,18 +749,26 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         return SimpleNamespace(loss=loss, count=count, correct=correct, pred=pred, row_loss=row_loss, sample_nll=sample_nll,
                                sample_tokens=sample_tokens, sample_correct=sample_correct)
 
-    def decode_weights(self):
+    def decode_weights(self, dtype="fp16"):
         """Fragment-major copies of the frozen projection weights and of the tied embedding table for the decode step of
         generate_batch (ops.pack_weight16; tcavt_decode_args.w_layout = W_FRAG16): one wave instruction of the weight stream
         then reads 1 KiB of consecutive bytes instead of 16 rows x 64 bytes -- 1.09 -> 0.91 ms per step at B = 8.  A second
         copy of the decoder's weights (2.47 GB at the Llama-3.2-1B shape), made on the first generation call and dropped with
         the packed weights it was made from; the adapters' small matrices are shared with the prefill's layer array.  Returns
-        None (row-major weights) when a shape has no skinny form."""
+        None (row-major weights) when a shape has no skinny form.
+
+        dtype="fp8": the same copies as e4m3 codes with one power-of-two scale per row (ops.pack_weight8, quant.py; W_FRAG8) --
+        half the bytes per step and half the extra memory (1.24 GB).  Quantised from the prepared 16-bit matrices, the norm
+        gains already folded in: what the fp16 copies hold.  One cache per dtype, both dropped with the prepared weights."""
         from . import capi
 
+        if dtype not in ("fp16", "fp8"):
+            raise ValueError(f"decode_weights: dtype must be 'fp16' or 'fp8', got {dtype!r}")
         P = self._prepared()
-        if getattr(self, "_prep_dec", None) is not None and self._prep_dec.of is P:
-            return self._prep_dec
+        slot = "_prep_dec" if dtype == "fp16" else "_prep_dec8"
+        pack = ops.pack_weight16 if dtype == "fp16" else ops.pack_weight8
+        if getattr(self, slot, None) is not None and getattr(self, slot).of is P:
+            return getattr(self, slot)
         ll = self.shape
         if ll.hidden % 256 or ll.inter % 256 or (ll.n_q_heads * ll.head_dim) % 256 or ll.vocab % 16:
             return None
@@ -772,12 +781,12 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
                 c = carr[li]
                 for name, _ in capi.LlamaLayer._fields_:
                     setattr(c, name, getattr(ctypes_copy, name))
-                pk = [ops.pack_weight16(w) for w in (d.w_qkv, d.w_o, d.w_gu, d.w_d)]
+                pk = [pack(w) for w in (d.w_qkv, d.w_o, d.w_gu, d.w_d)]
                 keep.append(pk)
                 c.w_qkv, c.w_o, c.w_gu, c.w_d = (t.data_ptr() for t in pk)
-            table = ops.pack_weight16(P.table)
-        self._prep_dec = SimpleNamespace(of=P, carr=carr, table=table, keep=keep)
-        return self._prep_dec
+            table = pack(P.table)
+        setattr(self, slot, SimpleNamespace(of=P, carr=carr, table=table, keep=keep))
+        return getattr(self, slot)
 
     def refresh_lora(self, stacked=None):
         """Re-pack the adapter matrices (a_cat with the folded gain, b_ext, and the backward's transposes) from the
@@ -1210,7 +1219,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
 
     def generate_batch(self, vision_embs_batch, context_str_list=None, max_new_tokens=50, input_ids=None,
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
-                       no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True):
+                       no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16"):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1222,6 +1231,10 @@ class LlamaMultiModal(nn.Module, _Prepared):
         token is embedded as a text token (embed_tokens(id) + text_modality_embedding) at the sample's next position.
         Prefill = the ordinary batched decoder pass writing a KV cache; then one tcavt_llama_decode_step +
         tcavt_sample_logits per token, all state on the device, the step replayed as a hipGraph (use_graph).
+        decode_weights="fp8" (opt-in): the decode step streams the FP8 copies of the frozen weights
+        (LlamaWithCrossAttnPEFT.decode_weights) -- half the bytes per token; the prefill, the activations and the KV cache
+        stay 16-bit.  It needs the skinny path (B <= 32, a shape with a skinny form, no TCAVT_DECODE_ROWMAJOR=1) and raises
+        where that cannot run: there is no fallback.
         Returns int64 [B, max_new_tokens] token ids (pad_token_id after EOS), or a list of strings with a tokenizer."""
         from . import capi
 
@@ -1241,6 +1254,13 @@ class LlamaMultiModal(nn.Module, _Prepared):
         H, Nq, N = self.llama_hidden_size, self.qformer.num_query_tokens, int(max_new_tokens)
         if N < 1:
             raise ValueError("max_new_tokens must be >= 1")
+        if decode_weights not in ("fp16", "fp8"):
+            raise ValueError(f"generate_batch: decode_weights must be 'fp16' or 'fp8', got {decode_weights!r}")
+        if decode_weights == "fp8":
+            if B > 32:
+                raise ValueError(f"generate_batch: decode_weights='fp8' runs on the skinny decode path only (B <= 32), got B = {B}")
+            if os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") == "1":
+                raise ValueError("generate_batch: decode_weights='fp8' has no row-major form (TCAVT_DECODE_ROWMAJOR=1 is set)")
         L = Nq + Lt
         Lmax = L + N
         nkvw = ll.n_kv_heads * ll.head_dim
@@ -1293,7 +1313,10 @@ class LlamaMultiModal(nn.Module, _Prepared):
                     # fragment-major weight copies for the step's weight streams and, on the 16-bit stream, fragment-major
                     # activations between its kernels (16 or 32 whole rows per buffer); TCAVT_DECODE_ROWMAJOR=1 /
                     # TCAVT_DECODE_ACT_ROWMAJOR=1: the row-major forms (A/B, tests)
-                    DW = LW.decode_weights() if (B <= 32 and os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") != "1") else None
+                    DW = LW.decode_weights(decode_weights) if (B <= 32 and os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") != "1") else None
+                    if DW is None and decode_weights == "fp8":
+                        raise ValueError("generate_batch: decode_weights='fp8': this decoder shape has no skinny form "
+                                         "(hidden, inter and n_q_heads * head_dim must be multiples of 256, vocab of 16)")
                     # (B <= 8: row-major activation rows are HALF the bytes of a 16-token fragment -- lanes of the empty token slots
                     #  repeat the last row -- and the step is 0.89 vs 0.91 ms; B = 16: 0.98 vs 1.05, B = 32: 1.09 vs 1.21 ms)
                     frag_act = DW is not None and LW.stream16 and os.environ.get("TCAVT_DECODE_ACT_ROWMAJOR", "0") != "1"
@@ -1312,7 +1335,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
                         setattr(a, k_, v_.data_ptr())
                     a.layers, a.gamma_final = PL.carr, PL.g_final.data_ptr()
                     if DW is not None:
-                        a.layers, a.w_layout, a.table_packed = DW.carr, capi.W_FRAG16, DW.table.data_ptr()
+                        a.layers, a.table_packed = DW.carr, DW.table.data_ptr()
+                        a.w_layout = capi.W_FRAG8 if decode_weights == "fp8" else capi.W_FRAG16
                     a.act_layout = act_mode
                     a.rope_cos, a.rope_sin, a.rope_L = cos.data_ptr(), sin.data_ptr(), Lmax
                     a.table, a.txt_mod = PL.table.data_ptr(), P.txt.data_ptr()

@@ -323,6 +323,20 @@ def pack_weight16(w, out=None):
     return out
 
 
+def pack_weight8(w, out=None):
+    """FP8 copy of a 16-bit weight matrix [N, K] for the skinny (decode-step) form of gemm_bf16 (tcavt_pack_weight8;
+    tcavt_gemm_args.w_layout = W_FRAG8): uint8 [N * K + 4 * N] -- the e4m3 codes in pack_weight16's order at one byte per
+    element, then the N power-of-two row scales as fp32.  quant.py is the definition."""
+    assert w.dim() == 2 and w.dtype in (torch.float16, torch.bfloat16) and w.stride(1) == 1
+    N, K = w.shape
+    nbytes = int(capi.lib().tcavt_pack_weight8_bytes(N, K))
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    assert out.numel() == nbytes and out.dtype == torch.uint8 and out.is_contiguous()
+    capi.check(capi.lib().tcavt_pack_weight8(w.data_ptr(), w.stride(0), _DT[w.dtype], out.data_ptr(), N, K, capi.stream_ptr()), "pack_weight8")
+    return out
+
+
 def norm_npart(M, N, K):
     """Partial sums of squares per row that a NORM_OUT product [M, N] over K writes (tcavt_norm_npart)."""
     return int(lib().tcavt_norm_npart(int(M), int(N), int(K)))

@@ -1,0 +1,85 @@
+"""The FP8 weight format of the decode step (include/tcavt.h: tcavt_pack_weight8) in plain torch, on any device.
+
+This is the definition the pack kernel is tested against: OCP e4m3fn codes of the rows of a 16-bit matrix, each row scaled
+by a power of two, and the byte layout the skinny GEMM streams.  Nothing here is on a hot path.
+
+    codes, k = quantize(w)            # uint8 [N, K], int32 [N]:  code = e4m3(w * 2^-k), k minimal with amax * 2^-k <= 448
+    buf = pack(w)                     # uint8 [N * K + 4 N]: fragment-major codes, then the fp32 scales 2^k
+    wq = dequantize(codes, k, dtype)  # the 16-bit matrix code * 2^k -- what the FP8 path multiplies by, exactly
+"""
+import torch
+
+E4M3_MAX = 448.0
+NAN_CODE = 0x7F
+
+
+def row_exponents(w):
+    """int32 [N]: per row the smallest k with amax * 2^-k <= 448 (amax = the row's largest magnitude); 0 for an all-zero
+    row and for a row with a non-finite element."""
+    amax = w.detach().abs().amax(dim=1).double()
+    m, e = torch.frexp(amax)  # amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    k = torch.where(m <= 0.875, e - 9, e - 8)
+    k = torch.where((amax == 0) | ~torch.isfinite(amax), torch.zeros_like(k), k)
+    return k.to(torch.int32)
+
+
+def quantize(w):
+    """w: 16-bit [N, K].  Returns (codes uint8 [N, K], k int32 [N]): the e4m3fn value nearest to the exact product
+    w * 2^-k, ties to even; the NaN code everywhere in a row that holds a non-finite element."""
+    assert w.dim() == 2 and w.dtype in (torch.float16, torch.bfloat16)
+    k = row_exponents(w)
+    scaled = torch.ldexp(w.detach().float(), -k[:, None])  # exact: a 16-bit value times a power of two in fp32
+    codes = scaled.to(torch.float8_e4m3fn).view(torch.uint8)
+    bad = ~torch.isfinite(w.detach().float()).all(dim=1)
+    codes = torch.where(bad[:, None], torch.full_like(codes, NAN_CODE), codes)
+    return codes, k
+
+
+def dequantize(codes, k, dtype):
+    """code * 2^k as a `dtype` (fp16 / bf16) matrix [N, K]: exact whenever the product is a normal number of that type."""
+    lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(codes.device)  # (the 256 values, decoded on the host)
+    v = lut[codes.long()]
+    return torch.ldexp(v, k[:, None].to(torch.int32)).to(dtype)
+
+
+def pack_chunks(codes):
+    """uint8 [N, K] -> uint8 [N * K] in the consuming wave's order: block b (16 rows), k-step j (32 columns) is the 512-byte
+    chunk b * K / 32 + j; lane l = 16 q + r holds codes[16 b + r][32 j + 8 q : + 8] at byte 8 l."""
+    N, K = codes.shape
+    assert N % 16 == 0 and K % 32 == 0
+    return codes.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+
+
+def unpack_chunks(flat, N, K):
+    """Inverse of pack_chunks."""
+    return flat.view(N // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(N, K)
+
+
+def scales(k):
+    """fp32 [N]: exactly 2^k."""
+    return torch.ldexp(torch.ones(k.shape, dtype=torch.float32, device=k.device), k.to(torch.int32))
+
+
+def pack(w):
+    """The whole buffer tcavt_pack_weight8 writes: uint8 [N * K + 4 N]."""
+    codes, k = quantize(w)
+    return torch.cat([pack_chunks(codes), scales(k).view(torch.uint8)])
+
+
+def unpack(buf, N, K):
+    """(codes uint8 [N, K], k int32 [N]) of a packed buffer."""
+    codes = unpack_chunks(buf[: N * K], N, K)
+    sc = buf[N * K:].contiguous().view(torch.float32)
+    _, e = torch.frexp(sc)
+    return codes, (e - 1).to(torch.int32)
+
+
+def snap(w):
+    """w rounded to the FP8 format and back, in w's own type: a matrix on which the FP8 and the 16-bit decode paths agree
+    bit for bit.  fp16: anything below the smallest normal (2^-14) becomes zero, so that no product rests on how an MFMA
+    treats subnormal operands."""
+    codes, k = quantize(w)
+    wq = dequantize(codes, k, w.dtype)
+    if w.dtype == torch.float16:
+        wq = torch.where(wq.abs() < 2.0 ** -14, torch.zeros_like(wq), wq)
+    return wq
