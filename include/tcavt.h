@@ -1109,6 +1109,18 @@ int tcavt_sample_logits(float* logits, int B, int V, int64_t* history, int hist_
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 
+/* The decode step's attention on its own: one query per (sample, query head) over the keys 0 .. pos[b] of ONE layer's cache,
+ * the new token's own key included.  qkv 16-bit [B][(nq + 2 nkv) * 64] (q | k | v of the new token, already rotated);
+ * k_cache / v_cache 16-bit [B][kv_lmax][nkv * 64]; pos int32 [B]; head dimension 64, nq % nkv == 0, nq / nkv <= 8;
+ * out 16-bit [B][nq * 64], row-major for out_layout 0, in the fragment-major order of tcavt_decode_args.act_layout for
+ * out_layout 1 (16 or 32 whole rows, B <= 32, nq * 64 % 256 == 0) or 2 (8 whole rows, B <= 8): token slots >= B are not written.
+ * Contract: the caller keeps pos[b] in [0, kv_lmax - 1].  Cache row pos[b] of every kv head is overwritten with the qkv row's
+ * k and v (bit for bit); the new key and value themselves are taken from qkv, so no cache row at or beyond pos[b] is read, and
+ * no other cache row is written.  kv_lmax is limited by the score buffer (kv_lmax + 66 * min(16, ceil(kv_lmax / 64)) floats in
+ * 64 KiB).  Probabilities are normalised in fp32 and carried in fp16, as in tcavt_attn_causal_gqa. */
+int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos, void* out, int B, int nq, int nkv,
+                      int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
+
 typedef struct tcavt_decode_args {
   const tcavt_llama_layer* layers; /* HOST array, as for tcavt_llama_stack_forward (tape fields unused) */
   const float* gamma_final;

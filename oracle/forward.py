@@ -262,11 +262,12 @@ def lora_scale(cfg):
     return cfg.lora_alpha / cfg.lora_r
 
 
-def llama_decoder(W, cfg, embeds, attn_mask, r, collect=None, drop=_ident):
+def llama_decoder(W, cfg, embeds, attn_mask, r, collect=None, drop=_ident, collect_kv=None):
     """embeds [B,L,H] fp32, attn_mask [B,L] (1 = valid, right padded) -> post-final-norm hidden
     states = outputs.hidden_states[-1] (train.py:553).  drop: LoRA dropout on the adapter branch's input (PEFT:
     lora_B(lora_A(dropout(x))) with one lora_dropout module PER adapted Linear: two sites per layer, q_proj then v_proj,
-    the order HF's attention forward calls them in, modeling_llama.py:254-256)."""
+    the order HF's attention forward calls them in, modeling_llama.py:254-256).  collect_kv (a list): receives every layer's
+    (k, v) [B, L, nkv, hd] as attended (k rotated, both at the "qkv" rounding point): the KV cache of oracle/decode.py."""
     ll = cfg.llama
     r = _rounder(r)
     B, L, H = embeds.shape
@@ -312,6 +313,8 @@ def llama_decoder(W, cfg, embeds, attn_mask, r, collect=None, drop=_ident):
             return torch.cat([t1 * cos - t2 * sin, t2 * cos + t1 * sin], dim=-1)
 
         q, k, v = r(rot(q), "qkv"), r(rot(k), "qkv"), r(v, "qkv")
+        if collect_kv is not None:
+            collect_kv.append((k, v))
         qh = q.permute(0, 2, 1, 3)
         kh = k.permute(0, 2, 1, 3).repeat_interleave(nq // nkv, dim=1)
         vh = v.permute(0, 2, 1, 3).repeat_interleave(nq // nkv, dim=1)

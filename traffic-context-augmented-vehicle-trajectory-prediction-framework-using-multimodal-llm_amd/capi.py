@@ -332,6 +332,8 @@ _SIGNATURES = {
                             c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p],
     "tcavt_sample_workspace_bytes": [c_int],
     "tcavt_gather_last": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "tcavt_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
+                          c_void_p],
     "tcavt_llama_decode_step": [ctypes.POINTER(DecodeArgs), c_void_p],
     "tcavt_norm_npart": [c_int, c_int, c_int],
     "tcavt_pack_weight16": [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p],

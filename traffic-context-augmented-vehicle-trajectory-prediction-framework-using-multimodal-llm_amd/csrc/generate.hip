@@ -815,6 +815,36 @@ extern "C" int tcavt_gather_last(const void* src16, const int32_t* kv_len, void*
   return TCAVT_OK;
 }
 
+// The decode attention's host rule: KS key splits (waves) per query head -- one 64-key round each up to 1024 keys, two beyond --
+// and the LDS bytes of [kv_lmax] scores | [KS][2] (max, sum) | [KS][64] partial outputs.  false: the scores do not fit 64 KiB.
+static bool attn_decode_rule(int kv_lmax, int* KS, size_t* lds) {
+  *KS = std::min(16, (kv_lmax + 63) / 64);
+  *lds = ((size_t)kv_lmax + (size_t)*KS * 66) * sizeof(float);
+  return *lds <= 64 * 1024;
+}
+
+extern "C" int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos, void* out, int B, int nq, int nkv,
+                                 int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(qkv && k_cache && v_cache && pos && out, "attn_decode: null pointer");
+  TCAVT_CHECK_ARG(is16(dtype16), "attn_decode: dtype16 must be TCAVT_F16 or TCAVT_BF16");
+  TCAVT_CHECK_ARG(B > 0 && nq > 0 && nkv > 0 && nq % nkv == 0 && nq / nkv <= 8, "attn_decode: bad shape (B, nq, nkv > 0, nq %% nkv == 0, nq / nkv <= 8)");
+  TCAVT_CHECK_ARG(kv_lmax >= 1, "attn_decode: kv_lmax must be >= 1");
+  int KS;
+  size_t lds;
+  TCAVT_CHECK_ARG(attn_decode_rule(kv_lmax, &KS, &lds), "attn_decode: kv_lmax = %d too long for the score buffer", kv_lmax);
+  TCAVT_CHECK_ARG(out_layout == 0 || (out_layout == 1 && B <= 32 && (nq * 64) % 256 == 0) || (out_layout == 2 && B <= 8),
+                  "attn_decode: out_layout must be 0, 1 (B <= 32, nq * 64 %% 256 == 0) or 2 (B <= 8)");
+  TCAVT_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_decode: qkv and the caches must be 16-byte aligned");
+  const bool pfv = B * nq <= 512;  // (value-row prefetch: only while the grid is about one workgroup per CU)
+  auto kfn = dtype16 == TCAVT_F16 ? (pfv ? attn_decode_kernel<true, true> : attn_decode_kernel<true, false>)
+                                  : (pfv ? attn_decode_kernel<false, true> : attn_decode_kernel<false, false>);
+  hipLaunchKernelGGL(kfn, dim3(B * nq), dim3(KS * 64), lds, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), pos, static_cast<bf16_t*>(out), kv_lmax, nq, nkv, scale,
+                     KS, out_layout);
+  TCAVT_CHECK_LAUNCH("attn_decode");
+  return TCAVT_OK;
+}
+
 extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(a && a->layers && a->gamma_final && a->rope_cos && a->rope_sin && a->table && a->txt_mod && a->cur_tok && a->pos &&
                       a->h16 && a->part && a->qkv && a->att && a->act && a->k_cache && a->v_cache && a->x16 && a->logits &&
@@ -826,7 +856,6 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
   const int B = a->B, H = a->H, I = a->I, nq = a->nq, nkv = a->nkv, dt = a->dtype16;
   const int nqkv = (nq + 2 * nkv) * 64;
   const int np_in = norm_out_npart(B, H, I), np_post = norm_out_npart(B, H, nq * 64);  // see csrc/stack.hip
-  hipStream_t st = static_cast<hipStream_t>(stream);
   // scaled 16-bit image of the residual stream, as in tcavt_llama_stack_forward (the prefill that filled the cache ran at the same scale
   // or not: keys / values are true-scale either way)
   TCAVT_CHECK_ARG(a->stream_scale >= 0.f && a->stream_scale <= 1.f, "llama_decode_step: stream_scale must be in (0, 1] (0 means 1)");
@@ -851,9 +880,12 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
   TCAVT_TRY(embed_fuse_impl(a->table, a->cur_tok, a->txt_mod /* unused: Nq = 0 */, a->txt_mod, a->txt_mod, a->h, B, 0, 1, H, a->V,
                             a->bad_id_flag, dt, a->h16, a->part, np_in, ss_, al, stream));
   const size_t per_layer = (size_t)B * a->kv_lmax * nkv * 64;
-  const int KS = std::min(16, (a->kv_lmax + 63) / 64);  // key splits (waves) per query head: one 64-key round each up to 1024 keys
-  const size_t lds = ((size_t)a->kv_lmax + (size_t)KS * 66) * sizeof(float);
-  TCAVT_CHECK_ARG(lds <= 64 * 1024, "llama_decode_step: kv_lmax = %d too long for the decode attention's score buffer", a->kv_lmax);
+  {
+    int KS;
+    size_t lds;
+    TCAVT_CHECK_ARG(attn_decode_rule(a->kv_lmax, &KS, &lds), "llama_decode_step: kv_lmax = %d too long for the decode attention's score buffer",
+                    a->kv_lmax);
+  }
   for (int li = 0; li < a->n_layers; ++li) {
     const tcavt_llama_layer& w = a->layers[li];
     TCAVT_CHECK_ARG(w.w_qkv && w.w_o && w.w_gu && w.w_d && (!w.a_cat || (w.b_ext && a->t)), "llama_decode_step: layer %d: null weight", li);
@@ -886,14 +918,7 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
     bf16_t* kc = static_cast<bf16_t*>(a->k_cache) + li * per_layer;
     bf16_t* vc = static_cast<bf16_t*>(a->v_cache) + li * per_layer;
     // (the new token's k / v rows are appended to the cache by attn_decode_kernel itself)
-    {
-      const bool pfv = B * nq <= 512;  // (value-row prefetch: only while the grid is about one workgroup per CU)
-      auto kfn = dt == TCAVT_F16 ? (pfv ? attn_decode_kernel<true, true> : attn_decode_kernel<true, false>)
-                                 : (pfv ? attn_decode_kernel<false, true> : attn_decode_kernel<false, false>);
-      hipLaunchKernelGGL(kfn, dim3(B * nq), dim3(KS * 64), lds, st, static_cast<const bf16_t*>(a->qkv), kc, vc, a->pos,
-                         static_cast<bf16_t*>(a->att), a->kv_lmax, nq, nkv, 0.125f, KS, al);
-    }
-    TCAVT_CHECK_LAUNCH("attn_decode");
+    TCAVT_TRY(tcavt_attn_decode(a->qkv, kc, vc, a->pos, a->att, B, nq, nkv, a->kv_lmax, 0.125f, dt, al, stream));
     {
       tcavt_gemm_args g = {};
       g.A = a->att; g.lda = nq * 64; g.W = w.w_o; g.ldw = nq * 64; g.C = a->h; g.ldc = H; g.w_layout = wl; g.act_layout = gAO;

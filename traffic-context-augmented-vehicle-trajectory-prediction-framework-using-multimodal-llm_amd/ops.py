@@ -1062,6 +1062,23 @@ def gather_last(src16, kv_len, out16, B, L, H):
     check(lib().tcavt_gather_last(ptr(src16), ptr(kv_len), ptr(out16), B, L, H, stream_ptr()), "tcavt_gather_last")
 
 
+def attn_decode(qkv, k_cache, v_cache, pos, out, B, nq, nkv, kv_lmax, scale, out_layout=0):
+    """The decode step's attention over ONE layer's cache [B, kv_lmax, nkv * 64] (tcavt_attn_decode): appends the qkv row's
+    k | v at pos[b] and attends keys 0 .. pos[b].  out_layout 1 / 2: out in fragment-major order (16 / 32 or 8 whole rows)."""
+    _req16(qkv, "attn_decode.qkv")
+    for t, nm in ((k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
+        _req16(t, "attn_decode." + nm, like=qkv)
+    _req(pos, torch.int32, "attn_decode.pos")
+    _need(qkv, B * (nq + 2 * nkv) * 64, "attn_decode.qkv")
+    _need(k_cache, B * kv_lmax * nkv * 64, "attn_decode.k_cache")
+    _need(v_cache, B * kv_lmax * nkv * 64, "attn_decode.v_cache")
+    _need(pos, B, "attn_decode.pos")
+    rows = B if out_layout == 0 else 8 if out_layout == 2 else 16 * ((B + 15) // 16)
+    _need(out, rows * nq * 64, "attn_decode.out")
+    check(lib().tcavt_attn_decode(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(pos), ptr(out), B, nq, nkv, kv_lmax, scale,
+                                  _DT[qkv.dtype], int(out_layout), stream_ptr()), "tcavt_attn_decode")
+
+
 def llama_decode_step(args):
     """args: capi.DecodeArgs filled by model.LlamaMultiModal.generate_batch (which owns and sizes every buffer)."""
     check(lib().tcavt_llama_decode_step(ctypes.byref(args), stream_ptr()), "tcavt_llama_decode_step")
