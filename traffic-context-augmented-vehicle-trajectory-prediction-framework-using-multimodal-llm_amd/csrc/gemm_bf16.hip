@@ -190,6 +190,7 @@ extern "C" int tcavt_gemm_bf16(const tcavt_gemm_args* a, tcavt_stream_t stream) 
   p.norm_h16 = nullptr;
   p.norm_part = nullptr;
   p.res16 = nullptr;
+  p.res_pf = 0;
   p.lp_part = nullptr;
   p.lp_a = nullptr;
   p.lp_lda = 0;

@@ -82,13 +82,20 @@ __device__ __forceinline__ void unswap_pair16(const u32x4& v, u32x2& a, u32x2& b
 // the 4-wave kernel computes them once per output tile while the first operands are in flight); otherwise they are
 // summed here from the partials, all TM rows' loads in flight together.
 // pin_acc re-pins the accumulator registers behind element (i, j) in front of a row's arithmetic.
+// res_lds (NORM16 in the 4-wave kernel, optional): the output tile's 16-bit residual already in LDS (gemm_w4.hpp, residual
+// prefetch) -- this lane's 16 bytes of row j, tile pair k are at res_lds + (k >> 1) * res_half + j * 8192 + (k & 1) * 512;
+// otherwise the epilogue loads the residual from p.res16 itself.
 template <int TN, int TM>
 __device__ __forceinline__ void pin_acc(f32x4 (&acc)[TN][TM], int i, int j) {
   asm volatile("" : "+a"(acc[i][j]));
 }
+template <int V>
+struct int_c {
+  static constexpr int value = V;
+};
 template <int TM, int TN, int EPI, bool WHOLE_ONLY = false, bool F16 = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TN][TM], int m_base, int n_base, int lane,
-                                              const float* rs_lds = nullptr) {
+                                              const float* rs_lds = nullptr, const char* res_lds = nullptr, int res_half = 0) {
   constexpr int OUT16 = F16 ? TCAVT_F16 : TCAVT_BF16;
   float rsv[TM];
   if constexpr (EPI == EPI_SILU || EPI == EPI_SILU_SAVE || EPI == EPI_ROPE) {
@@ -145,7 +152,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TN][T
       if constexpr (WHOLE_ONLY) {  // (the 4-wave kernel is dispatched for ldc % 8 == 0 only: launch_w4)
         // 16-byte form (pair16 helpers above): the residual pieces are requested DW rows ahead of their use (TN / 2 loads
         // of 16 bytes per row: half the instructions of the 8-byte form for the same lines), the stores are 16 bytes as well
-        constexpr int DW = TM > 5 ? 5 : TM;
+        // Residual already in LDS (res_lds): conflict-free 16-byte LDS reads two rows ahead deliver the same u32x4 the global
+        // load would; nothing but stores is left in the vector-memory queue.  Same arithmetic in the same order either way.
         const int off16 = pair16_off(lane);
         u32x4 oldw[TM][TN / 2];
         auto fetchw = [&](int j) {
@@ -154,11 +162,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TN][T
           for (int k = 0; k < TN / 2; ++k)
             oldw[j][k] = res ? *reinterpret_cast<const u32x4*>(hrow + k * 32) : u32x4{0u, 0u, 0u, 0u};
         };
+        auto fetchl = [&](int j) {
 #pragma unroll
-        for (int j = 0; j < DW; ++j) fetchw(j);
+          for (int k = 0; k < TN / 2; ++k)
+            oldw[j][k] = *reinterpret_cast<const u32x4*>(res_lds + (k >> 1) * res_half + j * 8192 + (k & 1) * 512);
+        };
+        auto rows = [&](auto fetch, auto depth) {
+        constexpr int DW = decltype(depth)::value;
+#pragma unroll
+        for (int j = 0; j < DW; ++j) fetch(j);
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
-          if (j + DW < TM) fetchw(j + DW < TM ? j + DW : 0);
+          if (j + DW < TM) fetch(j + DW < TM ? j + DW : 0);
           const long m = m_base + j * 16 + ml;
           bf16_t* hrow = p.norm_h16 + m * p.ldc + n_base;
 #pragma unroll
@@ -193,6 +208,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[TN][T
           }
           __builtin_amdgcn_sched_barrier(0);
         }
+        };
+        if (res_lds) rows(fetchl, int_c<(TM > 2 ? 2 : TM)>{});
+        else rows(fetchw, int_c<(TM > 5 ? 5 : TM)>{});
         return;
       }
       // 8-wave kernels: bounds-checked 8-byte accesses, the residual quads one row ahead of their use

@@ -67,6 +67,8 @@ struct GemmP {
   int* nf_flag;           // NORM_OUT: receives nf_tag (CAS from 0) when a partial sum / rounded element is not finite
   int nf_tag;
   float norm_scale;       // NORM_OUT: the 16-bit image of the stream (and its partial sums) holds norm_scale * x (tcavt_gemm_args.norm_scale)
+  int res_pf;             // NORM16 + RESIDUAL in the 4-wave kernel: the residual tile arrives by LDS-DMA in the look-ahead slots past a
+                          // workgroup's last K-tile (set by launch_w4 at every launch; TCAVT_GEMM_NO_RES_PREFETCH=1 clears it)
 };
 
 // a * s + b, one rounding (s = 1: exactly a + b, so the default scale leaves every result bit for bit as it was)

@@ -19,6 +19,13 @@ namespace tcavt {
 //   phase B2: 16 MFMA on F1(t)  | ds_read F0(t+1) | DMA pieces 0..3 of tile t+2
 //
 // Same LDS image as the kernel above (128-byte rows, XOR-swizzled 16-byte chunks, two 64 KiB buffers).
+//
+// Residual prefetch (EPI_NORM16 with TCAVT_EPI_RESIDUAL, p.res_pf): the look-ahead of a workgroup's LAST output tile has no
+// operands left to fetch -- "K-tiles" nt and nt + 1 of that tile carry the tile's 16-bit residual instead (256 x 256 x 2 bytes
+// = the two 64 KiB buffers), and the epilogue reads it from LDS.  Image: K-tile nt + h holds columns [128 wn + 64 h, + 64) of
+// every wave's 128 x 128 quadrant; piece r of wave w is rows 8 r .. 8 r + 7 of w's quadrant, 128 bytes of each (whole lines,
+// as for the operands), and inside the piece lane i sits where the epilogue's lane with (lane & 7) = i & 7, lane >> 4 =
+// (i >> 3) & 3 reads the 16 bytes of its tile pair (i >> 5): see locate_res below and gemm_epilogue.  Every wave fetches its own rows.
 // ===========================================================================
 // MFMA with the accumulator pinned to AGPRs and tied in place.  Written as inline asm because the compiler's
 // VGPR/AGPR rewriting turned the 256-register accumulator of the 4-wave kernel into ~350 v_accvgpr copies per K-tile.
@@ -89,6 +96,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
   const int csw = (lane & 7) ^ (((wave & 1) * 4 + (rl >> 1)) & 7);
   const bf16_t* srcA = p.A + (long)(m0 + wave * 8 + rl) * p.lda + csw * 8;
   const bf16_t* srcW = p.W + (long)(n0 + wave * 8 + rl) * p.ldw + csw * 8;
+  const long stepA = 32 * p.lda, stepW = 32 * p.ldw;
   // next output tile of this workgroup (persistent form): where the look-ahead continues
   bool has_next = pers && vb + (int)gridDim.x < total_tiles;
   int nm0 = m0, nn0 = n0;
@@ -105,12 +113,29 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
     }
   };
   locate_next();
-  const long stepA = 32 * p.lda, stepW = 32 * p.ldw;
   // second K source (LoRA: A2 = x.A_cat^T, W2 = B_ext): its 64-deep tiles follow the main ones
   constexpr bool HASK2 = EPI == EPI_ROPE;  // only the fused q|k|v projection uses it
   const bf16_t* srcA2 = nullptr;
   const bf16_t* srcW2 = nullptr;
   long stepA2 = 0, stepW2 = 0;
+  // residual prefetch: this lane's source in the residual tile of (m0, n0) (rows 8 r + (lane & 7) of the wave's quadrant for piece
+  // r; the tile pair (lane >> 5) of a 64-column half; the 16 bytes pair16_off() gives the epilogue lane (lane >> 3) & 3 rows of 16 on)
+  constexpr bool RPF = EPI == EPI_NORM16 && BN == 256;
+  const bool rpf = RPF && p.res_pf;
+  bool tail_res = false;  // (uniform) no next output tile: the look-ahead past the last K-tile carries this tile's residual
+  long nstepA = 0, nstepW = 0;  // piece strides of the look-ahead source past the last K-tile (next tile's operands / residual rows)
+  auto locate_res = [&]() {
+    if constexpr (RPF) {
+      tail_res = rpf && !has_next;
+      nstepA = stepA;
+      nstepW = stepW;
+      if (tail_res) {
+        nxtA = p.res16 + (long)(m0 + wm * 128 + (lane & 7)) * p.ldc + n0 + wn * 128 + (lane >> 5) * 32 + pair16_off(((lane >> 3) & 3) << 4);
+        nxtW = nxtA + 64 * p.ldc;
+        nstepA = nstepW = 8 * p.ldc;
+      }
+    }
+  };
   const int nt1 = p.K >> 6;
   int nt = nt1;
   auto locate_k2 = [&]() {
@@ -129,6 +154,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
     }
   }
   locate_k2();
+  locate_res();
 
   struct Src {
     const bf16_t* a;
@@ -137,7 +163,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
   };
   auto tsrc = [&](int t) -> Src {
     if constexpr (PERS_OK) {
-      if (t >= nt && has_next) return Src{nxtA + (t - nt) * 64, nxtW + (t - nt) * 64, stepA, stepW};  // next tile's first K-tiles
+      if constexpr (RPF) {  // ... or the two halves of this tile's residual
+        if (t >= nt && (has_next || tail_res)) return Src{nxtA + (t - nt) * 64, nxtW + (t - nt) * 64, nstepA, nstepW};
+      } else {
+        if (t >= nt && has_next) return Src{nxtA + (t - nt) * 64, nxtW + (t - nt) * 64, stepA, stepW};  // next tile's first K-tiles
+      }
     }
     t = min(t, nt - 1);  // the last two K-tiles re-fetch the last tile into a free buffer (keeps the loop body uniform)
     if constexpr (HASK2) {
@@ -183,7 +213,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
   if constexpr (DEEP) {
 #pragma unroll
     for (int r = 0; r < NP; ++r) piece(1, sn1, r);  // all of tile 1 (tsrc clamps when there is none: harmless re-fetch)
-  } else if (nt > 1) {
+  } else if (nt > 1 || (RPF && tail_res)) {
 #pragma unroll
     for (int r = 0; r < EARLY; ++r) piece(1, sn1, r);
   }
@@ -215,7 +245,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
         }
         if constexpr (DEEP) {
           if (idx == 0) {
-            into_next2 = PERS_OK && has_next && t + 2 >= nt;   // the look-ahead crosses into the next output tile
+            into_next2 = PERS_OK && (has_next || (RPF && tail_res)) && t + 2 >= nt;   // the look-ahead crosses into the next output tile (or the residual)
             const int tt = into_next2 ? t + 2 - nt : min(t + 2, nt - 1);  // clamp: see tsrc
             second2 = HASK2 && !into_next2 && tt >= nt1;
             koff2 = (second2 ? tt - nt1 : tt) * 64;
@@ -223,8 +253,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
           if (idx == 3) sn2.a = (into_next2 ? nxtA : second2 ? srcA2 : srcA) + koff2;
           if (idx == 6) sn2.w = (into_next2 ? nxtW : second2 ? srcW2 : srcW) + koff2;
           if (idx == 9) {
-            sn2.sa = second2 ? stepA2 : stepA;
-            sn2.sw = second2 ? stepW2 : stepW;
+            sn2.sa = second2 ? stepA2 : (RPF && into_next2) ? nstepA : stepA;
+            sn2.sw = second2 ? stepW2 : (RPF && into_next2) ? nstepW : stepW;
           }
           if (idx == 39) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // tile t is in registers everywhere
           if (idx >= 43 && (idx & 3) == 3) piece(cur, sn2, (idx - 43) / 4);  // pieces 0..5 of tile t+2
@@ -245,7 +275,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
           continue;
         }
         if (idx == 0) {
-          into_next2 = PERS_OK && has_next && t + 2 >= nt;   // the look-ahead crosses into the next output tile
+          into_next2 = PERS_OK && (has_next || (RPF && tail_res)) && t + 2 >= nt;   // the look-ahead crosses into the next output tile (or the residual)
           const int tt = into_next2 ? t + 2 - nt : min(t + 2, nt - 1);  // clamp: see tsrc
           second2 = HASK2 && !into_next2 && tt >= nt1;
           koff2 = (second2 ? tt - nt1 : tt) * 64;
@@ -253,8 +283,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
         if (idx == 3) sn2.a = (into_next2 ? nxtA : second2 ? srcA2 : srcA) + koff2;
         if (idx == 6) sn2.w = (into_next2 ? nxtW : second2 ? srcW2 : srcW) + koff2;
         if (idx == 9) {
-          sn2.sa = second2 ? stepA2 : stepA;
-          sn2.sw = second2 ? stepW2 : stepW;
+          sn2.sa = second2 ? stepA2 : (RPF && into_next2) ? nstepA : stepA;
+          sn2.sw = second2 ? stepW2 : (RPF && into_next2) ? nstepW : stepW;
         }
       }
     if (DEEP) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NP) : "memory");  // tile t+1 landed; t+2 in flight
@@ -287,6 +317,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
   };
   for (;;) {
     for (int t = 0; t < nt; ++t) ktile(t);
+    // residual prefetch, one-barrier form: only the EARLY pieces of the second half fitted behind the last end-of-tile barrier
+    // (phase B2); the rest goes out here, into the buffer of the last K-tile (nobody reads it any more).  The DEEP form has
+    // issued both halves inside the loop.
+    const bool from_lds = RPF && tail_res;  // (uniform) this output tile's residual is in LDS / on its way there
+    if constexpr (RPF && !DEEP) {
+      if (from_lds) {
+#pragma unroll
+        for (int r = EARLY; r < NP; ++r) piece(cur ^ 1, sn1, r);
+      }
+    }
     // the accumulators are read by VALU next: cover the MFMA write latency the compiler cannot see behind the asm
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     // ... and pin every accumulator read behind those nops: an empty volatile asm that redefines the register is
@@ -315,10 +355,23 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4_kernel(GemmP p) {
       locate_k2();
       has_next = vb + (int)gridDim.x < total_tiles;
       locate_next();
+      locate_res();
     }
     __builtin_amdgcn_sched_barrier(0);
+    const char* res_lds = nullptr;
+    if constexpr (RPF) {
+      if (from_lds) {
+        // Both halves have landed for every wave before the first store of the epilogue (no load is ever queued behind stores),
+        // and no LDS-DMA outlives the workgroup.  In place (norm_h16 == res16) a tile's residual region is written by its own
+        // workgroup only, and only behind this barrier: every byte of it is in LDS by then.  Out of place the source is only read.
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        // half h is in the buffer of K-tile nt + h: cur / cur ^ 1; this lane's 16 bytes of piece r = 2 j + (ml >> 3)
+        res_lds = smem + cur * TILE_BYTES + (((lane >> 3) & 1) * NW + wave) * 1024 + ((lane >> 4) * 8 + (lane & 7)) * 16;
+      }
+    }
     gemm_epilogue<TM, TN, EPI, true, F16>(p, acc, em0 + wm * TM * 16, en0 + wn * TN * 16, lane,
-                                          (RS && p.rs_part) ? rs_base + rs_sel * 256 + wm * TM * 16 : nullptr);
+                                          (RS && p.rs_part) ? rs_base + rs_sel * 256 + wm * TM * 16 : nullptr, res_lds,
+                                          (cur ^ 1) * TILE_BYTES - cur * TILE_BYTES);
     if (!cont) {
       if constexpr (DEEP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA (the clamped re-fetches) may outlive the workgroup
       break;
@@ -399,6 +452,13 @@ static int launch_w4(const GemmP& p0, hipStream_t stream) {
   if (w4_pers_ok(EPI, DEEP) && !no_pers && n_cu >= 8 && tiles > n_cu && p.K + p.K2 >= 128) {
     p.pers_tiles = tiles;
     wgs = n_cu;
+  }
+  // residual prefetch of the 16-bit stream epilogue (see the kernel); TCAVT_GEMM_NO_RES_PREFETCH=1: the epilogue loads the
+  // residual from global memory itself.  Read at every launch, so that one process can interleave both forms (A/B).
+  p.res_pf = 0;
+  if constexpr (EPI == EPI_NORM16 && BN == 256) {
+    const char* e = getenv("TCAVT_GEMM_NO_RES_PREFETCH");
+    p.res_pf = (p.flags & TCAVT_EPI_RESIDUAL) && !(e && e[0] && e[0] != '0');
   }
   dim3 grid(wgs), block(256);
   hipLaunchKernelGGL(kfn, grid, block, lds, stream, p);
