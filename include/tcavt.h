@@ -667,6 +667,13 @@ typedef struct tcavt_llama_layer {
   float* tape_part;   /* optional, fp32 [M][npart_in]: the partial sums of squares of this layer's INPUT stream (what its fused
                          input RMSNorm reads; otherwise they live in the shared `part` and are overwritten by the o_proj
                          epilogue) -- 1 / rms of every token for the adapters' weight gradients */
+  /* Opt-in MX8 MLP (tcavt_quant_mx8 / tcavt_gemm_mx8 below; all four or none, NULL = off): the MX8 images of w_gu and w_d as
+     they stand above (norm gain folded in, gate / up rows interleaved) -- e4m3 codes [2 I][H] / [H][I] and E8M0 scale bytes
+     [2 I][H / 32] / [H][I / 32].  Not with a tape (the LoRA-trainable backward reads 16-bit pre-activations) */
+  const void* w_gu8;
+  const void* w_gu8_scale;
+  const void* w_d8;
+  const void* w_d8_scale;
 } tcavt_llama_layer;
 
 typedef struct tcavt_llama_stack_args {
@@ -723,6 +730,11 @@ typedef struct tcavt_llama_stack_args {
      tcavt_gemm_args.splitk_ws; 16 KiB + S * M * H * 4 bytes, S <= 8: 64 MiB covers M <= 2048).  NULL: one launch each */
   void* splitk_ws;
   int64_t splitk_ws_bytes;
+  /* layers with MX8 weights (tcavt_llama_layer.w_gu8 ...): workspaces for the MX8 image of the MLP's activations -- codes
+     uint8 [M][max(H, I)] and scale bytes uint8 [M][max(H, I) / 32], both 16-byte aligned.  Needs H % 128 == 0, I % 128 == 0 and
+     M > 32 (the MX8 GEMM writes H / 64 partial sums per row) */
+  void* mx8_codes;
+  void* mx8_scales;
 } tcavt_llama_stack_args;
 
 int tcavt_llama_stack_forward(const tcavt_llama_stack_args* args, tcavt_stream_t stream);
@@ -1294,6 +1306,55 @@ typedef struct tcavt_lm_eval_args {
 
 int64_t tcavt_lm_eval_workspace_bytes(int64_t rows, int V, int H);
 int tcavt_lm_eval(const tcavt_lm_eval_args* args, tcavt_stream_t stream);
+
+/* ========================================================================
+ * MX8: the OCP MXFP8-E4M3 layout with this project's scale rule -- the opt-in block-scaled MLP of the frozen decoder.
+ * A 16-bit matrix X [R][K] (K % 32 == 0) becomes
+ *   codes  uint8 [R][K]       row-major OCP e4m3fn,  code = e4m3(x * 2^-k), nearest, ties to even
+ *   scales uint8 [R][K / 32]  row-major E8M0: byte = k + 127, value 2^k
+ * with k, per (row, block of 32 along K), the smallest integer with amax * 2^-k <= 448, clamped to [-127, 127]; an all-zero
+ * block has k = 0; a block with a non-finite element has code 0x7F throughout and scale byte 127.  The definition in plain
+ * torch is quant.quantize_mx; the kernels are tested against it byte for byte.
+ * ====================================================================== */
+/* X: 16-bit [M][K] with leading dimension ldx (elements; ldx % 8 == 0, 16-byte aligned), dtype16 = TCAVT_F16 / TCAVT_BF16.
+ * codes [M][ldc] (bytes; ldc >= K, ldc % 16 == 0), scales [M][lds] (lds >= K / 32, lds % 4 == 0).  Any M >= 1, K % 128 == 0.
+ * One read of X, a half-size write; nothing outside the [M][K] and [M][K / 32] regions is written. */
+int tcavt_quant_mx8(const void* X, int64_t ldx, int dtype16, void* codes, int64_t ldc, void* scales, int64_t lds, int M, int K,
+                    tcavt_stream_t stream);
+
+/* C[m][n] = sum over 32-blocks b of 2^(ka[m][b] + kw[n][b]) * sum_{k in b} a8[m][k] * w8[n][k]  (+ fused epilogue): fp32
+ * accumulation in v_mfma_scale_f32_16x16x128_f8f6f4 with the block scales of both operands applied by the instruction.
+ * Epilogues (anything else is refused before any launch; they are the epilogues of tcavt_gemm_bf16, same arithmetic):
+ *   0                                    generic: C fp32 or 16-bit [M][N]
+ *   SILU_MUL | ROWSCALE                  C 16-bit of `dtype16` [M][N / 2], W rows gate / up interleaved in blocks of 16
+ *   NORM_OUT [| RESIDUAL]                C fp32 (+ fp32 residual) with norm_h16 / norm_part;  C == NULL: the in-place 16-bit
+ *                                        stream norm_h16 (read from norm_res16 when given), norm_scale, nonfinite_flag
+ * K % 128 == 0, N % 128 == 0, any M >= 1 (rows past M are never read out of bounds and never written).  Fixed reduction order,
+ * no atomics on data, no allocation, no synchronisation: bit-reproducible and graph-capturable. */
+typedef struct tcavt_gemm_mx8_args {
+  const void* A8;  int64_t lda;        /* uint8 [M][K] e4m3 codes; lda in bytes, % 16 == 0 */
+  const void* A_scale; int64_t ldsa;   /* uint8 [M][K / 32] E8M0; ldsa in bytes, % 4 == 0 */
+  const void* W8;  int64_t ldw;        /* uint8 [N][K] */
+  const void* W_scale; int64_t ldsw;   /* uint8 [N][K / 32] */
+  void* C;         int64_t ldc;
+  const float* residual; int64_t ldr;
+  int32_t M, N, K;
+  int32_t out_dtype;                   /* TCAVT_F32 / TCAVT_BF16 / TCAVT_F16 */
+  int32_t epilogue;
+  int32_t dtype16;                     /* type of the 16-bit side inputs / outputs (norm_h16, norm_res16, SILU_MUL's C) */
+  int32_t tile;                        /* 0 = auto, 128 = the 4-wave 128 x 128 form (the only one) */
+  int32_t rowscale_npart, rowscale_h;
+  float rowscale_eps;
+  const float* rowscale_part;
+  void* norm_h16;
+  float* norm_part;
+  const void* norm_res16;
+  float norm_scale;                    /* 0 means 1 */
+  int32_t nonfinite_tag;
+  int32_t* nonfinite_flag;
+} tcavt_gemm_mx8_args;
+
+int tcavt_gemm_mx8(const tcavt_gemm_mx8_args* args, tcavt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -67,7 +67,8 @@ class LlamaLayer(ctypes.Structure):
     """Mirror of ``tcavt_llama_layer`` (include/tcavt.h)."""
 
     _fields_ = [(n, c_void_p) for n in ("w_qkv", "a_cat", "b_ext", "w_o", "w_gu", "w_d", "tape_h_mid", "tape_h_out",
-                                        "tape_qkv", "tape_gu", "tape_t", "tape_att", "tape_lse", "tape_part")]
+                                        "tape_qkv", "tape_gu", "tape_t", "tape_att", "tape_lse", "tape_part",
+                                        "w_gu8", "w_gu8_scale", "w_d8", "w_d8_scale")]
 
 
 TLAYER_FIELDS = ("w_in", "b_in", "w_out", "b_out", "w_q", "b_q", "w_kv", "b_kv", "w_co", "b_co", "w1", "b1", "w2", "b2",
@@ -166,6 +167,22 @@ class LlamaStackArgs(ctypes.Structure):
         ("rms_eps", ctypes.c_float), ("lora_scale", ctypes.c_float), ("lora_dropout_p", ctypes.c_float),
         ("lora_first_site", ctypes.c_uint32), ("dropout_seed", ctypes.c_uint64),
         ("nonfinite_flag", c_void_p), ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_int64),
+        ("mx8_codes", c_void_p), ("mx8_scales", c_void_p),
+    ]
+
+
+class GemmMx8Args(ctypes.Structure):
+    """Mirror of ``tcavt_gemm_mx8_args`` (include/tcavt.h)."""
+
+    _fields_ = [
+        ("A8", c_void_p), ("lda", c_int64), ("A_scale", c_void_p), ("ldsa", c_int64),
+        ("W8", c_void_p), ("ldw", c_int64), ("W_scale", c_void_p), ("ldsw", c_int64),
+        ("C", c_void_p), ("ldc", c_int64), ("residual", c_void_p), ("ldr", c_int64),
+        ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("out_dtype", ctypes.c_int32), ("epilogue", ctypes.c_int32), ("dtype16", ctypes.c_int32), ("tile", ctypes.c_int32),
+        ("rowscale_npart", ctypes.c_int32), ("rowscale_h", ctypes.c_int32), ("rowscale_eps", ctypes.c_float),
+        ("rowscale_part", c_void_p), ("norm_h16", c_void_p), ("norm_part", c_void_p), ("norm_res16", c_void_p),
+        ("norm_scale", ctypes.c_float), ("nonfinite_tag", ctypes.c_int32), ("nonfinite_flag", c_void_p),
     ]
 
 
@@ -361,6 +378,8 @@ _SIGNATURES = {
     "tcavt_lm_loss_backward": [ctypes.POINTER(LmLossArgs), c_void_p],
     "tcavt_lm_eval_workspace_bytes": [c_int64, c_int, c_int],
     "tcavt_lm_eval": [ctypes.POINTER(LmEvalArgs), c_void_p],
+    "tcavt_quant_mx8": [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p],
+    "tcavt_gemm_mx8": [ctypes.POINTER(GemmMx8Args), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64}

@@ -122,6 +122,24 @@ __host__ __device__ __forceinline__ long frag_off(int m, int f, int K, int mode)
   return mode == 2 ? (long)(f >> 5) * 256 + ((f >> 3) & 3) * 64 + (m & 7) * 8 + (f & 7) : frag16_off(m, f, K);
 }
 
+// ---- FP8 (OCP e4m3fn) quantisation shared by tcavt_pack_weight8 and tcavt_quant_mx8 ----------------------------------
+// e4m3fn code of x, round to nearest even, for finite |x| <= 448 (the caller has scaled the row): normals keep three mantissa
+// bits (the carry of the rounding runs into the exponent field by itself); below 2^-6 the code is the integer nearest to
+// |x| * 2^9, ties to even (8 = the smallest normal).  Plain integer arithmetic, the same on the host.
+__host__ __device__ __forceinline__ unsigned int e4m3_code(float x) {
+  const unsigned int bits = __builtin_bit_cast(unsigned int, x);
+  const unsigned int sign = (bits >> 24) & 0x80u, a = bits & 0x7fffffffu;
+  if (a >= 0x3c800000u) return sign | (((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3));  // |x| >= 2^-6
+  return sign | (unsigned int)__builtin_rintf(__builtin_bit_cast(float, a) * 512.f);
+}
+
+// smallest k with amax * 2^-k <= 448 (= 0.875 * 2^9); amax finite and > 0
+__host__ __device__ __forceinline__ int e4m3_row_exp(float amax) {
+  int e;
+  const float m = __builtin_frexpf(amax, &e);  // amax = m * 2^e, m in [0.5, 1)
+  return m <= 0.875f ? e - 9 : e - 8;
+}
+
 // ---- wave / block reductions (wave = 64 lanes) ----------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -26,23 +26,7 @@ __global__ __launch_bounds__(256) void pack_weight16_kernel(const bf16_t* __rest
 // FP8 copy of a weight matrix for the skinny form (tcavt.h: tcavt_pack_weight8): OCP e4m3fn codes in the fragment-major order
 // above at one byte per element, one power-of-two scale per row behind them.
 // ---------------------------------------------------------------------------
-// e4m3fn code of x, round to nearest even, for finite |x| <= 448 (the caller has scaled the row): normals keep three mantissa
-// bits (the carry of the rounding runs into the exponent field by itself); below 2^-6 the code is the integer nearest to
-// |x| * 2^9, ties to even (8 = the smallest normal).  Plain integer arithmetic, the same on the host.
-__host__ __device__ __forceinline__ unsigned int e4m3_code(float x) {
-  const unsigned int bits = __builtin_bit_cast(unsigned int, x);
-  const unsigned int sign = (bits >> 24) & 0x80u, a = bits & 0x7fffffffu;
-  if (a >= 0x3c800000u) return sign | (((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3));  // |x| >= 2^-6
-  return sign | (unsigned int)__builtin_rintf(__builtin_bit_cast(float, a) * 512.f);
-}
-
-// smallest k with amax * 2^-k <= 448 (= 0.875 * 2^9); amax finite and > 0
-__host__ __device__ __forceinline__ int e4m3_row_exp(float amax) {
-  int e;
-  const float m = __builtin_frexpf(amax, &e);  // amax = m * 2^e, m in [0.5, 1)
-  return m <= 0.875f ? e - 9 : e - 8;
-}
-
+// (e4m3_code / e4m3_row_exp: common.hpp)
 // One workgroup per block of 16 rows; 16 consecutive lanes per row find its largest magnitude (and whether all of it is finite),
 // then thread t writes the 8-byte pieces t, t + 256, ... of the block's K / 32 chunks: piece (j, l) <- W[16 b + (l & 15)][32 j +
 // 8 (l >> 4) .. + 7] * 2^-k (exact: ldexp), rounded once.  A row with a non-finite element: the NaN code everywhere, scale 1.

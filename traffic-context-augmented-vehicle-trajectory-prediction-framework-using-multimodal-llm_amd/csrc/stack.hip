@@ -227,6 +227,15 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
     TCAVT_CHECK_ARG(w.w_qkv && w.w_o && w.w_gu && w.w_d && (w.a_cat == nullptr) == (w.b_ext == nullptr),
                     "llama_stack_forward: layer %d: null weight", li);
     const bool tape = w.tape_h_mid != nullptr;
+    const bool mx8 = w.w_gu8 || w.w_gu8_scale || w.w_d8 || w.w_d8_scale;  // opt-in MX8 MLP (include/tcavt.h)
+    if (mx8) {
+      TCAVT_CHECK_ARG(w.w_gu8 && w.w_gu8_scale && w.w_d8 && w.w_d8_scale, "llama_stack_forward: layer %d: the four MX8 pointers come together", li);
+      TCAVT_CHECK_ARG(!tape, "llama_stack_forward: layer %d: MX8 weights cannot run with a tape (the backward reads 16-bit pre-activations)", li);
+      TCAVT_CHECK_ARG(a->mx8_codes && a->mx8_scales && aligned16(a->mx8_codes) && aligned16(a->mx8_scales),
+                      "llama_stack_forward: MX8 layers need the mx8_codes / mx8_scales workspaces (16-byte aligned)");
+      TCAVT_CHECK_ARG(H % 128 == 0 && I % 128 == 0 && np_in == H / 64 && np_post == H / 64,
+                      "llama_stack_forward: MX8 layers need H %% 128 == 0, I %% 128 == 0 and more than 32 rows (H=%d, I=%d, M=%d)", H, I, M);
+    }
     if (tape) TCAVT_CHECK_ARG(ss_ == 1.f, "llama_stack_forward: a tape keeps the streams at scale 1 (stream_scale must be 0 or 1)");
     if (tape) TCAVT_CHECK_ARG(w.tape_h_out && w.tape_qkv && w.tape_gu && (!w.a_cat || w.tape_t), "llama_stack_forward: layer %d: incomplete tape", li);
     void* qkv = tape ? w.tape_qkv : a->qkv;
@@ -304,7 +313,17 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
       g.rowscale_part = a->part; g.rowscale_npart = np_post; g.rowscale_h = H; g.rowscale_eps = eps_s;
       if (tape) { g.silu_preact = w.tape_gu; g.ld_preact = 2 * I; }
       ev.rec(6);
-      TCAVT_TRY(tcavt_gemm_bf16(&g, stream));
+      if (mx8) {  // quantise the 16-bit stream, then the same epilogue on the block-scaled product
+        TCAVT_TRY(tcavt_quant_mx8(g.A, H, dt, a->mx8_codes, H, a->mx8_scales, H / 32, M, H, stream));
+        tcavt_gemm_mx8_args x = {};
+        x.A8 = a->mx8_codes; x.lda = H; x.A_scale = a->mx8_scales; x.ldsa = H / 32;
+        x.W8 = w.w_gu8; x.ldw = H; x.W_scale = w.w_gu8_scale; x.ldsw = H / 32;
+        x.C = a->act; x.ldc = I; x.M = M; x.N = 2 * I; x.K = H; x.out_dtype = dt; x.dtype16 = dt; x.epilogue = g.epilogue;
+        x.rowscale_part = a->part; x.rowscale_npart = np_post; x.rowscale_h = H; x.rowscale_eps = eps_s;
+        TCAVT_TRY(tcavt_gemm_mx8(&x, stream));
+      } else {
+        TCAVT_TRY(tcavt_gemm_bf16(&g, stream));
+      }
       ev.rec(7);
     }
     // ---- h_out = h_mid + act . W_d^T; again the next norm's inputs
@@ -319,7 +338,19 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
       g.splitk_ws = a->splitk_ws; g.splitk_ws_bytes = a->splitk_ws_bytes;
       g.nonfinite_flag = a->nonfinite_flag; g.nonfinite_tag = 2 + 2 * li;
       ev.rec(8);
-      TCAVT_TRY(tcavt_gemm_bf16(&g, stream));
+      if (mx8) {
+        TCAVT_TRY(tcavt_quant_mx8(a->act, I, dt, a->mx8_codes, I, a->mx8_scales, I / 32, M, I, stream));
+        tcavt_gemm_mx8_args x = {};
+        x.A8 = a->mx8_codes; x.lda = I; x.A_scale = a->mx8_scales; x.ldsa = I / 32;
+        x.W8 = w.w_d8; x.ldw = I; x.W_scale = w.w_d8_scale; x.ldsw = I / 32;
+        x.C = g.C; x.ldc = H; x.residual = g.residual; x.ldr = H; x.M = M; x.N = H; x.K = I;
+        x.out_dtype = TCAVT_F32; x.dtype16 = dt; x.epilogue = g.epilogue;
+        x.norm_h16 = g.norm_h16; x.norm_part = g.norm_part; x.norm_res16 = g.norm_res16; x.norm_scale = ss_;
+        x.nonfinite_flag = g.nonfinite_flag; x.nonfinite_tag = g.nonfinite_tag;
+        TCAVT_TRY(tcavt_gemm_mx8(&x, stream));
+      } else {
+        TCAVT_TRY(tcavt_gemm_bf16(&g, stream));
+      }
       ev.rec(9);
     }
     h = h_out;

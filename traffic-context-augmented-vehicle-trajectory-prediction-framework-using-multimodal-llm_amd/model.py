@@ -566,6 +566,10 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         # fp16 operands with an fp32 residual stream (h != NULL in tcavt_llama_stack_args): the stream itself has no range limit,
         # its 16-bit copy is the only fp16 image (10 instead of 4 bytes per element through the residual epilogues)
         self.wide_stream = False
+        # Opt-in MX8 MLP (mlp_weights, MultiModalTrajectoryModel.set_mlp_precision): "mx8" runs gate|up and down of every pass
+        # without a tape on the block-scaled FP8 MFMA.  "fp16" (the default): the 16-bit kernels, bit for bit as before.
+        self.mlp_precision = "fp16"
+        self._prep_mx8 = None
 
     def set_stream_contract(self, stream_scale=1.0, wide_stream=False):
         """See stream_scale / wide_stream above.  Nothing is re-packed: with the stream's image at s x the whole q|k|v accumulator
@@ -684,6 +688,7 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
         self._prep_T = None
         self._prep_dec = None
         self._prep_dec8 = None
+        self._prep_mx8 = None
         self._prep_tableT = None
         _Prepared._invalidate(self)
 
@@ -787,6 +792,35 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
             table = pack(P.table)
         setattr(self, slot, SimpleNamespace(of=P, carr=carr, table=table, keep=keep))
         return getattr(self, slot)
+
+    def mlp_weights(self, dtype="mx8"):
+        """MX8 images (ops.quant_mx8, quant.quantize_mx: e4m3 codes + one E8M0 scale per 32 elements along K) of the frozen gate|up
+        and down matrices for the opt-in MX8 MLP, and a copy of the layer array that names them (tcavt_llama_layer.w_gu8 ...).
+        Quantised from the prepared 16-bit matrices, the norm gain already folded in.  A second, 33/64-size copy of the MLP
+        weights (0.83 GB at the Llama-3.2-1B shape), made on the first MX8 pass and dropped with the packed weights it was made
+        from, like decode_weights."""
+        from . import capi
+
+        if dtype != "mx8":
+            raise ValueError(f"mlp_weights: dtype must be 'mx8', got {dtype!r}")
+        ll = self.shape
+        if ll.hidden % 128 or ll.inter % 128:
+            raise ValueError(f"mlp_weights: the MX8 MLP needs hidden and inter to be multiples of 128, got {ll.hidden} / {ll.inter}")
+        P = self._prepared()
+        if self._prep_mx8 is not None and self._prep_mx8.of is P:
+            return self._prep_mx8
+        carr = (capi.LlamaLayer * len(P.layers))()
+        keep = []
+        with torch.no_grad():
+            for li, d in enumerate(P.layers):
+                c = carr[li]
+                for name, _ in capi.LlamaLayer._fields_:
+                    setattr(c, name, getattr(P.carr[li], name))
+                gu, d8 = ops.quant_mx8(d.w_gu), ops.quant_mx8(d.w_d)
+                keep.append((gu, d8))
+                c.w_gu8, c.w_gu8_scale, c.w_d8, c.w_d8_scale = gu[0].data_ptr(), gu[1].data_ptr(), d8[0].data_ptr(), d8[1].data_ptr()
+        self._prep_mx8 = SimpleNamespace(of=P, carr=carr, keep=keep)
+        return self._prep_mx8
 
     def refresh_lora(self, stacked=None):
         """Re-pack the adapter matrices (a_cat with the folded gain, b_ext, and the backward's transposes) from the
@@ -906,6 +940,18 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
             qkv = ws.get("ll.qkv", (M, nqkv), self.storage, dev)
             args.qkv = qkv.data_ptr()
             keep.append(qkv)
+        if self.mlp_precision == "mx8":  # opt-in MX8 MLP: no fallback -- what cannot run raises
+            if self.save_for_backward:
+                raise capi.TcavtError("decoder_stack: mlp_precision='mx8' cannot run with a tape (the LoRA-trainable backward reads "
+                                      "16-bit pre-activations); set_mlp_precision('fp16') for training passes")
+            if M <= 32:
+                raise capi.TcavtError(f"decoder_stack: mlp_precision='mx8' needs more than 32 rows (B * L = {M})")
+            carr = self.mlp_weights("mx8").carr
+            kmax = max(H, ll.inter)
+            mxc = ws.get("ll.mx8.codes", (M, kmax), torch.uint8, dev)
+            mxs = ws.get("ll.mx8.scales", (M, kmax // 32), torch.uint8, dev)
+            args.mx8_codes, args.mx8_scales = mxc.data_ptr(), mxs.data_ptr()
+            keep += [mxc, mxs]
         if self.use_lora:
             t = ws.get("ll.lora_t", (M, 64), self.storage, dev, zero=True)
             args.t = t.data_ptr()
@@ -1844,6 +1890,20 @@ class MultiModalTrajectoryModel(nn.Module):
             raise ValueError("stream_scale must be a power of two in (0, 1]")
         self._auto_range = "pending" if auto else None
         self.range_contract = None
+        return self
+
+    def set_mlp_precision(self, precision="fp16"):
+        """Precision of the frozen decoder's MLP GEMMs (gate|up and down) in every decoder pass that keeps no tape: forward,
+        evaluate_model at any K, lm_evaluate and the prefill of generate_batch.  "fp16" (the default): the 16-bit kernels.  "mx8"
+        (opt-in): activations and weights as MXFP8-E4M3 blocks of 32 (quant.quantize_mx) on the block-scaled MFMA
+        (LlamaWithCrossAttnPEFT.mlp_weights).  The decode step and the KV cache are unaffected.  There is no fallback: a pass that
+        cannot run on MX8 (a tape, hidden or inter not a multiple of 128, 32 rows or fewer) raises."""
+        if precision not in ("fp16", "mx8"):
+            raise ValueError(f"set_mlp_precision: precision must be 'fp16' or 'mx8', got {precision!r}")
+        lw = self.mllm.llama_wrapper
+        if precision == "mx8" and (lw.shape.hidden % 128 or lw.shape.inter % 128):
+            raise ValueError(f"set_mlp_precision: 'mx8' needs hidden and inter to be multiples of 128, got {lw.shape.hidden} / {lw.shape.inter}")
+        lw.mlp_precision = precision
         return self
 
     def _calibrate_range(self, vision_embs, context_str, input_ids, attention_mask, labels):

@@ -337,6 +337,50 @@ def pack_weight8(w, out=None):
     return out
 
 
+def quant_mx8(x, codes=None, scales=None):
+    """MX8 image of a 16-bit matrix x [M, K] (K % 128 == 0; a column slice with unit column stride is fine): e4m3 codes uint8
+    [M, K] and E8M0 scale bytes uint8 [M, K / 32], byte for byte quant.quantize_mx (tcavt_quant_mx8)."""
+    _req16(x, "quant_mx8.x", rows_ok=True)
+    M, K = x.shape
+    if codes is None:
+        codes = torch.empty((M, K), dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+    for t, nm, cols in ((codes, "codes", K), (scales, "scales", K // 32)):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < M or t.shape[1] < cols or (not t.is_cuda and not _ALLOW_CPU):
+            raise capi.TcavtError(f"quant_mx8.{nm}: uint8 GPU tensor of at least ({M}, {cols}) with unit column stride required")
+    check(lib().tcavt_quant_mx8(ptr(x), x.stride(0), _DT[x.dtype], ptr(codes), codes.stride(0), ptr(scales), scales.stride(0), M, K,
+                                stream_ptr()), "tcavt_quant_mx8")
+    return codes, scales
+
+
+def gemm_mx8(a8, a_scale, w8, w_scale, out, dtype16, *, epilogue=0, **fields):
+    """C = dequantize_mx(a8, a_scale) @ dequantize_mx(w8, w_scale).T on the block-scaled MFMA (tcavt_gemm_mx8).  a8 [M, K], w8 [N, K]
+    uint8 codes, a_scale / w_scale uint8 [.., K / 32]; out: fp32 or `dtype16` [M, N] ([M, N / 2] with SILU_MUL), or None with
+    NORM_OUT for the in-place 16-bit stream.  `fields`: further tcavt_gemm_mx8_args members (tensors are passed by pointer)."""
+    for t, nm in ((a8, "a8"), (a_scale, "a_scale"), (w8, "w8"), (w_scale, "w_scale")):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1 or (not t.is_cuda and not _ALLOW_CPU):
+            raise capi.TcavtError(f"gemm_mx8.{nm}: 2-D uint8 GPU tensor with unit column stride required")
+    M, K = a8.shape
+    N = w8.shape[0]
+    if w8.shape[1] != K or a_scale.shape[0] < M or w_scale.shape[0] < N or a_scale.shape[1] < K // 32 or w_scale.shape[1] < K // 32:
+        raise capi.TcavtError("gemm_mx8: operand / scale shapes do not match (M, K), (N, K), (.., K / 32)")
+    args = capi.GemmMx8Args()
+    args.A8, args.lda, args.A_scale, args.ldsa = a8.data_ptr(), a8.stride(0), a_scale.data_ptr(), a_scale.stride(0)
+    args.W8, args.ldw, args.W_scale, args.ldsw = w8.data_ptr(), w8.stride(0), w_scale.data_ptr(), w_scale.stride(0)
+    args.M, args.N, args.K = M, N, K
+    args.dtype16, args.epilogue = _DT[dtype16], epilogue
+    if out is not None:
+        n_out = N // 2 if epilogue & EPI_SILU_MUL else N
+        if (not out.is_cuda and not _ALLOW_CPU) or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < n_out:
+            raise capi.TcavtError(f"gemm_mx8.out: 2-D GPU tensor of at least ({M}, {n_out}) with unit column stride required")
+        args.C, args.ldc, args.out_dtype = out.data_ptr(), out.stride(0), _DT[out.dtype]
+    for k, v in fields.items():
+        setattr(args, k, v.data_ptr() if torch.is_tensor(v) else v)
+    check(lib().tcavt_gemm_mx8(ctypes.byref(args), stream_ptr()), "tcavt_gemm_mx8")
+    return out
+
+
 def norm_npart(M, N, K):
     """Partial sums of squares per row that a NORM_OUT product [M, N] over K writes (tcavt_norm_npart)."""
     return int(lib().tcavt_norm_npart(int(M), int(N), int(K)))

@@ -6,6 +6,12 @@ by a power of two, and the byte layout the skinny GEMM streams.  Nothing here is
     codes, k = quantize(w)            # uint8 [N, K], int32 [N]:  code = e4m3(w * 2^-k), k minimal with amax * 2^-k <= 448
     buf = pack(w)                     # uint8 [N * K + 4 N]: fragment-major codes, then the fp32 scales 2^k
     wq = dequantize(codes, k, dtype)  # the 16-bit matrix code * 2^k -- what the FP8 path multiplies by, exactly
+
+"MX8" (tcavt_quant_mx8 / tcavt_gemm_mx8, the opt-in block-scaled MLP of the frozen decoder) is the OCP MXFP8-E4M3 layout with the
+same scale rule applied per block of 32 along K instead of per row:
+
+    codes, sb = quantize_mx(x)        # uint8 [R, K], uint8 [R, K / 32]: E8M0 scale bytes, byte = k + 127, value 2^k
+    xq = dequantize_mx(codes, sb, dtype)  # code * 2^k, exact (float64 allowed)
 """
 import torch
 
@@ -83,3 +89,43 @@ def snap(w):
     if w.dtype == torch.float16:
         wq = torch.where(wq.abs() < 2.0 ** -14, torch.zeros_like(wq), wq)
     return wq
+
+
+MX_BLOCK = 32
+E8M0_BIAS = 127
+
+
+def quantize_mx(x):
+    """x: 16-bit [R, K], K % 32 == 0.  Returns (codes uint8 [R, K], scale bytes uint8 [R, K / 32]).  Per (row, block of 32 along K):
+    k = row_exponents' rule on the block (the smallest k with amax * 2^-k <= 448), clamped to [-127, 127]; byte = k + 127;
+    code = e4m3fn(x * 2^-k), nearest, ties to even (never saturates; below the clamp the codes underflow).  An all-zero block
+    has k = 0; a block with a non-finite element has the NaN code throughout and scale byte 127."""
+    assert x.dim() == 2 and x.dtype in (torch.float16, torch.bfloat16) and x.shape[1] % MX_BLOCK == 0
+    R, K = x.shape
+    xb = x.detach().reshape(R * (K // MX_BLOCK), MX_BLOCK)
+    k = row_exponents(xb).clamp(-E8M0_BIAS, E8M0_BIAS)
+    scaled = torch.ldexp(xb.double(), -k[:, None]).float()  # exact in float64; its fp32 image is exact or below every e4m3 step
+    codes = scaled.to(torch.float8_e4m3fn).view(torch.uint8)
+    bad = ~torch.isfinite(xb.float()).all(dim=1)
+    codes = torch.where(bad[:, None], torch.full_like(codes, NAN_CODE), codes)
+    return codes.reshape(R, K), (k + E8M0_BIAS).to(torch.uint8).reshape(R, K // MX_BLOCK)
+
+
+def dequantize_mx(codes, scale_bytes, dtype):
+    """code * 2^(byte - 127) as `dtype` (fp16 / bf16 / fp32 / float64) [R, K]: exact whenever the product is a number of that
+    type (always in float64)."""
+    lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).double().to(codes.device)
+    R, K = codes.shape
+    v = lut[codes.long()].reshape(R, K // MX_BLOCK, MX_BLOCK)
+    k = scale_bytes.to(torch.int32) - E8M0_BIAS
+    return torch.ldexp(v, k[:, :, None]).reshape(R, K).to(dtype)
+
+
+def snap_mx(x):
+    """x rounded to the MX8 format and back, in x's own type (fp16: anything below the smallest normal becomes zero, as in
+    `snap`)."""
+    codes, sb = quantize_mx(x)
+    xq = dequantize_mx(codes, sb, x.dtype)
+    if x.dtype == torch.float16:
+        xq = torch.where(xq.abs() < 2.0 ** -14, torch.zeros_like(xq), xq)
+    return xq
