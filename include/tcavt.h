@@ -726,6 +726,16 @@ typedef struct tcavt_llama_stack_args {
      2 + 2 * layer (down_proj) into it if it is still 0 (tcavt_gemm_args.nonfinite_flag): the first layer whose output left
      the 16-bit range, or whose inputs already had */
   int32_t* nonfinite_flag;
+  /* optional, instead of k_cache / v_cache: the FP8 cache ("KV8", see tcavt_kv_store8) -- codes uint8
+     [n_layers][B][nkv][kv_lmax][64] and scale bytes uint8 [n_layers][B][nkv][kv_lmax][2] for keys and for values.  All four or
+     none (zero = off); together with k_cache / v_cache the call is refused.  With them set the stack stores every layer's
+     rotated k | v through tcavt_kv_store8 instead of the 16-bit store; the attention reads the 16-bit q|k|v as always, so the
+     stack's output does not depend on the cache type.  (These four sit in front of splitk_ws rather than at the very end of the
+     struct: the struct's tail is pinned.) */
+  void* kv8_k_codes;
+  void* kv8_k_scales;
+  void* kv8_v_codes;
+  void* kv8_v_scales;
   /* optional: workspace for the two-launch split K of the residual projections on grids that leave CUs idle (small B * L:
      tcavt_gemm_args.splitk_ws; 16 KiB + S * M * H * 4 bytes, S <= 8: 64 MiB covers M <= 2048).  NULL: one launch each */
   void* splitk_ws;
@@ -1133,6 +1143,31 @@ int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int
 int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos, void* out, int B, int nq, int nkv,
                       int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
 
+/* ---- "KV8": the opt-in FP8 KV cache of the decode step ------------------------------------------------------------------
+ * A cached key or value row of one kv head (64 elements) is stored as the OCP MXFP8-E4M3 image of that row, exactly
+ * quant.quantize_mx: 64 e4m3fn codes and 2 E8M0 scale bytes, one per block of 32 along the head dimension (byte = k + 127, k the
+ * smallest integer with amax * 2^-k <= 448, clamped to [-127, 127]; an all-zero block has k = 0; a block with a non-finite element
+ * has code 0x7F throughout and scale byte 127).  The planes of ONE layer are HEAD-MAJOR, so that the rows of a kv head are
+ * consecutive and 16 keys are one contiguous KiB:
+ *     codes   uint8 [B][nkv][kv_lmax][64]        scales  uint8 [B][nkv][kv_lmax][2]
+ * one pair for the keys and one for the values; the code planes must be 16-byte aligned, the scale planes 2-byte aligned.
+ *
+ * The prefill store of one layer: rows (b, l < L) of the rotated k | v columns of qkv 16-bit [B * L][(nq + 2 nkv) * 64] go to
+ * positions l of sample b's planes, byte for byte quant.kv8_quantize; positions >= L and everything outside the planes are not
+ * written.  One launch. */
+int tcavt_kv_store8(const void* qkv, int B, int L, int kv_lmax, int nq, int nkv, int dtype16, void* k_codes, void* k_scales,
+                    void* v_codes, void* v_scales, tcavt_stream_t stream);
+
+/* tcavt_attn_decode on ONE layer's FP8 cache: the same contract -- one query per (sample, query head) over keys 0 .. pos[b], head
+ * dimension 64, nq % nkv == 0, nq / nkv <= 8, the three out_layouts with their B limits, pos[b] in [0, kv_lmax - 1] kept by the
+ * caller, token slots >= B of out untouched, kv_lmax limited by the same score buffer.  The new token's own key and value are
+ * used at 16-bit precision from qkv; row pos[b] of every kv head is overwritten with quantize_mx of the qkv row's k and v (byte for
+ * byte), no other byte of the four planes is written and no row at or beyond pos[b] is read; every earlier row counts as
+ * code * 2^k, exactly, in fp32.  Scores and sums fp32, one global maximum and one global sum per head, probabilities rounded to
+ * fp16 once relative to the final sum, fp32 accumulation.  One launch, no allocation, no synchronisation. */
+int tcavt_attn_decode8(const void* qkv, void* k_codes, void* k_scales, void* v_codes, void* v_scales, const int32_t* pos, void* out,
+                       int B, int nq, int nkv, int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
+
 typedef struct tcavt_decode_args {
   const tcavt_llama_layer* layers; /* HOST array, as for tcavt_llama_stack_forward (tape fields unused) */
   const float* gamma_final;
@@ -1149,7 +1184,8 @@ typedef struct tcavt_decode_args {
   void* att;                       /* 16-bit [B][nq * 64] */
   void* act;                       /* 16-bit [B][I] */
   void* t;                         /* 16-bit [B][64] (LoRA; zero-initialised once) */
-  void* k_cache;                   /* 16-bit [n_layers][B][kv_lmax][nkv * 64], filled up to pos[b] by the prefill / earlier steps */
+  void* k_cache;                   /* 16-bit [n_layers][B][kv_lmax][nkv * 64], filled up to pos[b] by the prefill / earlier steps
+                                      (NULL, both, with the kv8_* planes at the end of the struct) */
   void* v_cache;
   void* x16;                       /* 16-bit [B][H]: final-norm output */
   float* logits;                   /* fp32 [B][V] */
@@ -1171,6 +1207,14 @@ typedef struct tcavt_decode_args {
                                       tokens (TCAVT_ACT_BLOCK8; buffers of 8 whole rows, B <= 8).  Needs h == NULL */
   const void* table_packed;        /* optional: tcavt_pack_weight16 copy of `table` for the lm_head product (the token lookup
                                       keeps reading `table`) */
+  /* optional, instead of k_cache / v_cache: the FP8 cache of tcavt_kv_store8 / tcavt_attn_decode8 -- codes uint8
+     [n_layers][B][nkv][kv_lmax][64], scale bytes uint8 [n_layers][B][nkv][kv_lmax][2], keys and values.  All four or none
+     (zero = off); together with k_cache / v_cache the call is refused before anything is launched.  With them set every layer's
+     attention is tcavt_attn_decode8; every other launch of the step is the same, at every B, w_layout and act_layout */
+  void* kv8_k_codes;
+  void* kv8_k_scales;
+  void* kv8_v_codes;
+  void* kv8_v_scales;
 } tcavt_decode_args;
 
 int tcavt_llama_decode_step(const tcavt_decode_args* args, tcavt_stream_t stream);

@@ -2,13 +2,17 @@
 tools/bench_generate.py.  Measurement tool; never on the product path.
 
     python tools/decode_breakdown.py gpurun_out/r02/prof_gen/gen_kernel_trace.csv
+    python tools/decode_breakdown.py <kernel trace csv> --attn
+
+--attn: only the attention launch's own time (attn_decode_kernel / attn_decode8_kernel: count, total, average) -- the figure the
+fp16-cache and fp8-cache arms of profiles/decode_kv8.txt are compared by.
 """
 import collections
 import csv
 import sys
 
 
-def main(path):
+def main(path, attn_only=False):
     rows = list(csv.DictReader(open(path)))
     for r in rows:
         r["s"], r["e"] = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
@@ -19,6 +23,8 @@ def main(path):
     print(f"decode step: {len(step)} kernels, span {(step[-1]['e'] - step[0]['s']) / 1000:.1f} us, "
           f"sum of kernel durations {sum(r['e'] - r['s'] for r in step) / 1000:.1f} us")
     acc = collections.defaultdict(lambda: [0, 0])
+    if attn_only:
+        step = [r for r in step if "attn_decode" in r["Kernel_Name"]]
     for r in step:
         k = r["Kernel_Name"].split("(")[0][-60:]
         acc[k][0] += 1
@@ -28,4 +34,4 @@ def main(path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main([a for a in sys.argv[1:] if a != "--attn"][0], "--attn" in sys.argv[1:])

@@ -166,7 +166,9 @@ class LlamaStackArgs(ctypes.Structure):
         ("kv_lmax", ctypes.c_int32), ("gemm_tile", ctypes.c_int32), ("npart_in", ctypes.c_int32), ("stream_scale", ctypes.c_float),
         ("rms_eps", ctypes.c_float), ("lora_scale", ctypes.c_float), ("lora_dropout_p", ctypes.c_float),
         ("lora_first_site", ctypes.c_uint32), ("dropout_seed", ctypes.c_uint64),
-        ("nonfinite_flag", c_void_p), ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_int64),
+        ("nonfinite_flag", c_void_p),
+        ("kv8_k_codes", c_void_p), ("kv8_k_scales", c_void_p), ("kv8_v_codes", c_void_p), ("kv8_v_scales", c_void_p),
+        ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_int64),
         ("mx8_codes", c_void_p), ("mx8_scales", c_void_p),
     ]
 
@@ -229,7 +231,8 @@ class DecodeArgs(ctypes.Structure):
             "n_layers", "B", "H", "I", "nq", "nkv", "V", "dtype16", "kv_lmax", "rope_L")] + [
         ("rms_eps", c_float), ("lora_scale", c_float), ("nonfinite_flag", c_void_p), ("splitk_ws", c_void_p),
         ("splitk_ws_bytes", c_int64), ("lora_part", c_void_p), ("lora_rank", c_int), ("stream_scale", ctypes.c_float),
-        ("w_layout", ctypes.c_int32), ("act_layout", ctypes.c_int32), ("table_packed", c_void_p)]
+        ("w_layout", ctypes.c_int32), ("act_layout", ctypes.c_int32), ("table_packed", c_void_p),
+        ("kv8_k_codes", c_void_p), ("kv8_k_scales", c_void_p), ("kv8_v_codes", c_void_p), ("kv8_v_scales", c_void_p)]
 
 
 class LmLossArgs(ctypes.Structure):
@@ -351,6 +354,9 @@ _SIGNATURES = {
     "tcavt_gather_last": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "tcavt_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
                           c_void_p],
+    "tcavt_kv_store8": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tcavt_attn_decode8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                           c_int, c_int, c_void_p],
     "tcavt_llama_decode_step": [ctypes.POINTER(DecodeArgs), c_void_p],
     "tcavt_norm_npart": [c_int, c_int, c_int],
     "tcavt_pack_weight16": [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p],

@@ -200,6 +200,12 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
   TCAVT_CHECK_ARG(a->lora_dropout_p >= 0.f && a->lora_dropout_p < 1.f, "llama_stack_forward: lora_dropout_p must be in [0, 1)");
   TCAVT_CHECK_ARG((a->k_cache == nullptr) == (a->v_cache == nullptr) && (!a->k_cache || a->kv_lmax >= a->L),
                   "llama_stack_forward: k_cache / v_cache go together, kv_lmax >= L");
+  // the generation cache a prefill fills: the 16-bit pair, or the four FP8 planes (tcavt_kv_store8) -- not both
+  const bool kv8 = a->kv8_k_codes || a->kv8_k_scales || a->kv8_v_codes || a->kv8_v_scales;
+  TCAVT_CHECK_ARG(!kv8 || (a->kv8_k_codes && a->kv8_k_scales && a->kv8_v_codes && a->kv8_v_scales),
+                  "llama_stack_forward: the four kv8 planes come together");
+  TCAVT_CHECK_ARG(!kv8 || (!a->k_cache && !a->v_cache), "llama_stack_forward: the kv8 planes and k_cache / v_cache exclude each other");
+  TCAVT_CHECK_ARG(!kv8 || a->kv_lmax >= a->L, "llama_stack_forward: kv8 planes need kv_lmax >= L");
   // attention: K and V^T of a kv head resident in LDS up to TCAVT_ATTN_RESIDENT_MAX_L rows, streamed in key chunks beyond (refused before any launch
   // past the streaming entry's cap)
   TCAVT_CHECK_ARG(a->L <= TCAVT_ATTN_STREAM_MAX_L, "llama_stack_forward: L=%d exceeds the decoder attention's limit of %d", a->L,
@@ -281,6 +287,11 @@ extern "C" int tcavt_llama_stack_forward(const tcavt_llama_stack_args* a, tcavt_
                          static_cast<bf16_t*>(a->k_cache) + li * per_layer, static_cast<bf16_t*>(a->v_cache) + li * per_layer,
                          a->L, a->kv_lmax, nq, nkv);
       TCAVT_CHECK_LAUNCH("kv_store");
+    } else if (kv8) {  // quantised on the way into the cache: no 16-bit cache exists
+      const size_t rows = (size_t)li * a->B * nkv * a->kv_lmax;  // cached rows in front of this layer's planes
+      TCAVT_TRY(tcavt_kv_store8(qkv, a->B, a->L, a->kv_lmax, nq, nkv, dt, static_cast<unsigned char*>(a->kv8_k_codes) + rows * 64,
+                                static_cast<unsigned char*>(a->kv8_k_scales) + rows * 2, static_cast<unsigned char*>(a->kv8_v_codes) + rows * 64,
+                                static_cast<unsigned char*>(a->kv8_v_scales) + rows * 2, stream));
     }
     // ---- causal grouped-query attention
     ev.rec(2);

@@ -879,7 +879,9 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
     def decoder_stack(self, h, kv_len, B, L, out_f32=None, out_bf16=None, kv_cache=None, nonfinite_flag=None):
         """h: fp32 [B*L, H] residual stream (updated in place unless a tape is kept), or None with ``stream16`` (the stream
         is norm_inputs()[0]); norm_inputs() must have been filled; kv_len int32 [B].  One C call: tcavt_llama_stack_forward (csrc/stack.hip).  kv_cache = (k, v, lmax):
-        16-bit [layers, B, lmax, nkv*64] tensors that receive the rotated keys / values (generation prefill)."""
+        16-bit [layers, B, lmax, nkv*64] tensors that receive the rotated keys / values (generation prefill); or the FP8 form
+        (k_codes, k_scales, v_codes, v_scales, lmax): uint8 [layers, B, nkv, lmax, 64] codes and uint8 [layers, B, nkv, lmax, 2] scale
+        bytes (quant.kv8_quantize of what the 16-bit form would hold; the stack's own output is the same either way)."""
         from . import capi
 
         ll, P, ws = self.shape, self._prepared(), self._ws
@@ -981,7 +983,17 @@ class LlamaWithCrossAttnPEFT(nn.Module, _Prepared):
             args.out16 = out_bf16.data_ptr()
         if (h is not None and h.dtype != torch.float32) or kv_len.dtype != torch.int32:
             raise capi.TcavtError("decoder_stack: h fp32 and kv_len int32 required")
-        if kv_cache is not None:
+        if kv_cache is not None and len(kv_cache) == 5:
+            kcod, ksc, vcod, vsc, lmax = kv_cache
+            rows = ll.layers * B * nkv * lmax
+            if any(t.dtype != torch.uint8 for t in (kcod, ksc, vcod, vsc)) or kcod.numel() < rows * 64 or vcod.numel() < rows * 64 or \
+                    ksc.numel() < rows * 2 or vsc.numel() < rows * 2 or lmax < L:
+                raise capi.TcavtError("decoder_stack.kv_cache: the FP8 form is four uint8 tensors, codes [layers, B, nkv, lmax, 64] and scale "
+                                      "bytes [layers, B, nkv, lmax, 2] for keys and values, with lmax >= L")
+            args.kv8_k_codes, args.kv8_k_scales = kcod.data_ptr(), ksc.data_ptr()
+            args.kv8_v_codes, args.kv8_v_scales, args.kv_lmax = vcod.data_ptr(), vsc.data_ptr(), lmax
+            keep += [kcod, ksc, vcod, vsc]
+        elif kv_cache is not None:
             kc, vc, lmax = kv_cache
             need = ll.layers * B * lmax * nkv * hd
             if kc.dtype != self.storage or vc.dtype != self.storage or kc.numel() < need or vc.numel() < need or lmax < L:
@@ -1265,7 +1277,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
 
     def generate_batch(self, vision_embs_batch, context_str_list=None, max_new_tokens=50, input_ids=None,
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
-                       no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16"):
+                       no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
+                       kv_cache="fp16"):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1281,9 +1294,17 @@ class LlamaMultiModal(nn.Module, _Prepared):
         (LlamaWithCrossAttnPEFT.decode_weights) -- half the bytes per token; the prefill, the activations and the KV cache
         stay 16-bit.  It needs the skinny path (B <= 32, a shape with a skinny form, no TCAVT_DECODE_ROWMAJOR=1) and raises
         where that cannot run: there is no fallback.
+        kv_cache="fp8" (opt-in, independent of decode_weights): the KV cache is kept in the "KV8" format (quant.kv8_quantize: e4m3
+        codes with one power-of-two scale per 32 elements of a head's row, head-major planes) -- 66 instead of 128 bytes per cached
+        row and kv head.  The prefill itself is unchanged (its attention reads the 16-bit q|k|v; only the store into the cache
+        quantises, tcavt_kv_store8), so the first generated token does not depend on the cache type; every decode step uses its
+        own key / value at 16-bit precision, writes them quantised and sees every earlier row as code * 2^k (tcavt_attn_decode8).
+        Any other value raises ValueError.
         Returns int64 [B, max_new_tokens] token ids (pad_token_id after EOS), or a list of strings with a tokenizer."""
         from . import capi
 
+        if kv_cache not in ("fp16", "fp8"):  # (before anything touches a device)
+            raise ValueError(f"generate_batch: kv_cache must be 'fp16' or 'fp8', got {kv_cache!r}")
         if input_ids is None:
             if self.tokenizer is None or context_str_list is None:
                 raise NotImplementedError(
@@ -1327,10 +1348,16 @@ class LlamaMultiModal(nn.Module, _Prepared):
                 kv_len = ws.get("gen.kvlen", (B,), i32, dev)
                 ops.mask_to_kvlen(attention_mask.to(i64).contiguous(), Nq, kv_len, flags[1:2])
                 self._last_flags = flags
-                kc = ws.get("gen.kc", (ll.layers, B, Lmax, nkvw), st, dev)
-                vc = ws.get("gen.vc", (ll.layers, B, Lmax, nkvw), st, dev)
+                if kv_cache == "fp8":  # the four KV8 planes; no 16-bit cache exists
+                    kv8 = tuple(ws.get(f"gen.kv8.{nm}", (ll.layers, B, ll.n_kv_heads, Lmax, per), torch.uint8, dev)
+                                for nm, per in (("kc", 64), ("ks", 2), ("vc", 64), ("vs", 2)))
+                    cache = kv8 + (Lmax,)
+                else:
+                    kc = ws.get("gen.kc", (ll.layers, B, Lmax, nkvw), st, dev)
+                    vc = ws.get("gen.vc", (ll.layers, B, Lmax, nkvw), st, dev)
+                    cache = (kc, vc, Lmax)
                 final16 = ws.get("gen.final16", (B * L, H), st, dev)
-                LW.decoder_stack(h, kv_len, B, L, out_bf16=final16, kv_cache=(kc, vc, Lmax), nonfinite_flag=flags[2:3])
+                LW.decoder_stack(h, kv_len, B, L, out_bf16=final16, kv_cache=cache, nonfinite_flag=flags[2:3])
                 x16 = ws.get("gen.x16", (B, H), st, dev)
                 ops.gather_last(final16, kv_len, x16, B, L, H)
                 logits = ws.get("gen.logits", (B, ll.vocab), torch.float32, dev)
@@ -1387,7 +1414,11 @@ class LlamaMultiModal(nn.Module, _Prepared):
                     a.rope_cos, a.rope_sin, a.rope_L = cos.data_ptr(), sin.data_ptr(), Lmax
                     a.table, a.txt_mod = PL.table.data_ptr(), P.txt.data_ptr()
                     a.cur_tok, a.pos = cur.data_ptr(), pos.data_ptr()
-                    a.k_cache, a.v_cache, a.kv_lmax = kc.data_ptr(), vc.data_ptr(), Lmax
+                    if kv_cache == "fp8":
+                        a.kv8_k_codes, a.kv8_k_scales, a.kv8_v_codes, a.kv8_v_scales = (t_.data_ptr() for t_ in kv8)
+                        a.kv_lmax = Lmax
+                    else:
+                        a.k_cache, a.v_cache, a.kv_lmax = kc.data_ptr(), vc.data_ptr(), Lmax
                     dx16 = ws.get("gen.dx16", (Br, H), st, dev, zero=True) if frag_act else x16
                     a.x16, a.logits, a.bad_id_flag = dx16.data_ptr(), logits.data_ptr(), flags.data_ptr()
                     a.nonfinite_flag = flags[2:3].data_ptr()

@@ -1123,6 +1123,39 @@ def attn_decode(qkv, k_cache, v_cache, pos, out, B, nq, nkv, kv_lmax, scale, out
                                   _DT[qkv.dtype], int(out_layout), stream_ptr()), "tcavt_attn_decode")
 
 
+def _kv8_planes(planes, rows, what):
+    kcod, ksc, vcod, vsc = planes
+    for t, nm, per in ((kcod, "k_codes", 64), (ksc, "k_scales", 2), (vcod, "v_codes", 64), (vsc, "v_scales", 2)):
+        _req(t, torch.uint8, f"{what}.{nm}")
+        _need(t, rows * per, f"{what}.{nm}")
+
+
+def kv_store8(qkv, B, L, kv_lmax, nq, nkv, k_codes, k_scales, v_codes, v_scales):
+    """Prefill store of ONE layer into the FP8 cache (tcavt_kv_store8): rows (b, l < L) of the rotated k | v columns of qkv
+    [B * L, (nq + 2 nkv) * 64] -> positions l of the head-major planes, codes uint8 [B, nkv, kv_lmax, 64] and scale bytes uint8
+    [B, nkv, kv_lmax, 2]; byte for byte quant.kv8_quantize."""
+    _req16(qkv, "kv_store8.qkv")
+    _need(qkv, B * L * (nq + 2 * nkv) * 64, "kv_store8.qkv")
+    _kv8_planes((k_codes, k_scales, v_codes, v_scales), B * nkv * kv_lmax, "kv_store8")
+    check(lib().tcavt_kv_store8(ptr(qkv), B, L, kv_lmax, nq, nkv, _DT[qkv.dtype], ptr(k_codes), ptr(k_scales), ptr(v_codes),
+                                ptr(v_scales), stream_ptr()), "tcavt_kv_store8")
+
+
+def attn_decode8(qkv, k_codes, k_scales, v_codes, v_scales, pos, out, B, nq, nkv, kv_lmax, scale, out_layout=0):
+    """attn_decode over ONE layer's FP8 cache (tcavt_attn_decode8; planes as for kv_store8): appends the qkv row's k | v at
+    pos[b], quantised, and attends the cached keys 0 .. pos[b] - 1 as code * 2^k plus the new key / value at 16-bit precision."""
+    _req16(qkv, "attn_decode8.qkv")
+    _req16(out, "attn_decode8.out", like=qkv)
+    _req(pos, torch.int32, "attn_decode8.pos")
+    _need(qkv, B * (nq + 2 * nkv) * 64, "attn_decode8.qkv")
+    _kv8_planes((k_codes, k_scales, v_codes, v_scales), B * nkv * kv_lmax, "attn_decode8")
+    _need(pos, B, "attn_decode8.pos")
+    rows = B if out_layout == 0 else 8 if out_layout == 2 else 16 * ((B + 15) // 16)
+    _need(out, rows * nq * 64, "attn_decode8.out")
+    check(lib().tcavt_attn_decode8(ptr(qkv), ptr(k_codes), ptr(k_scales), ptr(v_codes), ptr(v_scales), ptr(pos), ptr(out), B, nq, nkv,
+                                   kv_lmax, scale, _DT[qkv.dtype], int(out_layout), stream_ptr()), "tcavt_attn_decode8")
+
+
 def llama_decode_step(args):
     """args: capi.DecodeArgs filled by model.LlamaMultiModal.generate_batch (which owns and sizes every buffer)."""
     check(lib().tcavt_llama_decode_step(ctypes.byref(args), stream_ptr()), "tcavt_llama_decode_step")

@@ -12,6 +12,12 @@ same scale rule applied per block of 32 along K instead of per row:
 
     codes, sb = quantize_mx(x)        # uint8 [R, K], uint8 [R, K / 32]: E8M0 scale bytes, byte = k + 127, value 2^k
     xq = dequantize_mx(codes, sb, dtype)  # code * 2^k, exact (float64 allowed)
+
+"KV8" (tcavt_kv_store8 / tcavt_attn_decode8, the opt-in FP8 KV cache of the decode step) is quantize_mx of every cached 64-element
+row of a kv head, stored head-major:
+
+    codes, sb = kv8_quantize(kv16)    # [B, L, nkv * 64] -> uint8 [B, nkv, L, 64], uint8 [B, nkv, L, 2]
+    kv = kv8_dequantize(codes, sb, dtype)  # back to [B, L, nkv * 64], exact (float64 allowed)
 """
 import torch
 
@@ -129,3 +135,27 @@ def snap_mx(x):
     if x.dtype == torch.float16:
         xq = torch.where(xq.abs() < 2.0 ** -14, torch.zeros_like(xq), xq)
     return xq
+
+
+KV_HEAD_DIM = 64
+
+
+def kv8_quantize(kv16):
+    """"KV8", the opt-in FP8 KV cache of the decode step (include/tcavt.h: tcavt_kv_store8 / tcavt_attn_decode8): a cached key or value
+    row of one kv head (64 elements) is quantize_mx of that row -- 64 e4m3fn codes and 2 E8M0 scale bytes -- and the rows of one kv
+    head are consecutive (head-major).  kv16: 16-bit [B, L, nkv * 64] (the 16-bit cache's token-major order).
+    Returns (codes uint8 [B, nkv, L, 64], scale bytes uint8 [B, nkv, L, 2])."""
+    assert kv16.dim() == 3 and kv16.shape[2] % KV_HEAD_DIM == 0
+    B, L, w = kv16.shape
+    nkv = w // KV_HEAD_DIM
+    rows = kv16.detach().reshape(B, L, nkv, KV_HEAD_DIM).permute(0, 2, 1, 3).reshape(B * nkv * L, KV_HEAD_DIM)
+    codes, sb = quantize_mx(rows)
+    return codes.reshape(B, nkv, L, KV_HEAD_DIM), sb.reshape(B, nkv, L, KV_HEAD_DIM // MX_BLOCK)
+
+
+def kv8_dequantize(codes, scale_bytes, dtype):
+    """code * 2^(byte - 127) of a KV8 plane pair, back in token-major order: `dtype` (fp16 / bf16 / fp32 / float64) [B, L, nkv * 64]."""
+    B, nkv, L, d = codes.shape
+    assert d == KV_HEAD_DIM and tuple(scale_bytes.shape) == (B, nkv, L, KV_HEAD_DIM // MX_BLOCK)
+    x = dequantize_mx(codes.reshape(B * nkv * L, d), scale_bytes.reshape(B * nkv * L, d // MX_BLOCK), dtype)
+    return x.reshape(B, nkv, L, d).permute(0, 2, 1, 3).reshape(B, L, nkv * d)
