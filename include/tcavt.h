@@ -1128,6 +1128,71 @@ int tcavt_sample_logits(float* logits, int B, int V, int64_t* history, int hist_
                         int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
                         int64_t workspace_bytes, tcavt_stream_t stream);
 
+/* tcavt_sample_logits with PER-SLOT bookkeeping, for a pool of S decode slots that hold requests of different age (a slot is
+ * refilled with the next request when its request ends).  logits, history, hist_cap, hist_len, params, cur_tok, pos, finished,
+ * out_tokens, out_cap, advance_pos, workspace and stream are those of tcavt_sample_logits (a slot is a sample); three differ:
+ *   step     int32 [S]: step[s] is the index of the token being chosen for the request in slot s
+ *   max_new  int32 [S]: the token budget of the request in slot s
+ *   out_row  int64 [S]: the row of out_tokens the slot writes to; its low 32 bits take the sample index's place in the Philox
+ *            counter, which is (step[s], out_row[s], 0x5A3B, 0): a request's draws do not depend on the slot it runs in.
+ * A slot with finished[s] == 0: the token is the one tcavt_sample_logits selects for the row's scores and history at (step, sample) =
+ * (step[s], out_row[s]) -- same processors, candidate order, first-maximum rule, penalty and bans in place; it goes to
+ * out_tokens[out_row[s] * out_cap + step[s]], to cur_tok[s] and to the history; pos[s] += 1 when advance_pos != 0; finished[s] = 1 if
+ * the token is EOS or step[s] + 1 == max_new[s]; step[s] += 1.
+ * A slot with finished[s] != 0 is INERT: cur_tok[s] = pad_token_id and nothing else of its state is written (no out_tokens element,
+ * no history element, not hist_len, step or pos); its logits row may still be processed in place.  An idle or finished slot thus
+ * keeps re-running the decode step on the pad token at a frozen pos[s], which rewrites cache row pos[s] of its own slot only.
+ * Both forms exist: one-stage (workspace NULL) and two-stage, with the workspace contract of tcavt_sample_logits -- the control
+ * words are zero between calls, and calls of either entry may alternate on one workspace (each slot's merging workgroup owns
+ * its step word: no cross-workgroup ticket is taken).  V, top_k and hist_cap limits as for tcavt_sample_logits.  Bad arguments
+ * are refused before any launch and tcavt_last_error names the argument. */
+int tcavt_sample_logits_slots(float* logits, int S, int V, int64_t* history, int hist_cap, int32_t* hist_len,
+                              const tcavt_sample_params* params, int32_t* step, const int32_t* max_new, const int64_t* out_row,
+                              int64_t* cur_tok, int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos,
+                              void* workspace, int64_t workspace_bytes, tcavt_stream_t stream);
+
+/* Admission of a freshly prefilled request into slot `slot` of an S-slot pool, in one launch: the request's one-sample cache
+ * (what tcavt_llama_stack_forward wrote at B = 1) is copied into the slot's rows of the pool's cache, and the slot's
+ * bookkeeping for tcavt_sample_logits_slots / tcavt_llama_decode_step at B = S is reset.
+ * The source and the destination come in ONE of two forms -- all pointers of one form, none of the other; mixing is refused:
+ *   16-bit: src_k / src_v [n_layers][1][src_lmax][nkv * 64]  ->  dst_k / dst_v [n_layers][S][kv_lmax][nkv * 64]
+ *   KV8:    the four planes [n_layers][1][nkv][src_lmax][64 | 2]  ->  [n_layers][S][nkv][kv_lmax][64 | 2]
+ * Rows 0 .. rows - 1 of every layer and kv head of the slot become the source rows, byte for byte; no other byte of the
+ * destination is written (other slots, rows >= rows of this slot, everything outside the planes).
+ * State: history[slot][0 .. n_ids) = prompt_ids; hist_len[slot] = *kv_len - n_image; pos[slot] = *kv_len; step[slot] = 0;
+ * finished[slot] = 0; max_new[slot] = max_new_value; out_row[slot] = out_row_value; cur_tok is left for the sampler (not written).
+ * Refused before the launch: rows outside [1, min(src_lmax, kv_lmax)], slot outside [0, S), caches / code planes that are not
+ * 16-byte aligned (scale planes: 2-byte), n_ids outside [0, hist_cap], null or mixed pointers. */
+typedef struct tcavt_slot_admit_args {
+  const void* src_k;               /* 16-bit form (all four, or none) */
+  const void* src_v;
+  void* dst_k;
+  void* dst_v;
+  const void* src_k_codes;         /* KV8 form (all eight, or none) */
+  const void* src_k_scales;
+  const void* src_v_codes;
+  const void* src_v_scales;
+  void* dst_k_codes;
+  void* dst_k_scales;
+  void* dst_v_codes;
+  void* dst_v_scales;
+  const int64_t* prompt_ids;       /* int64 [n_ids]: the request's prompt row (right padded) */
+  const int32_t* kv_len;           /* device int32 [1]: the prefill's kv_len = n_image + valid prompt tokens */
+  int64_t* history;                /* int64 [S][hist_cap] */
+  int32_t* hist_len;               /* the S-slot arrays of tcavt_sample_logits_slots */
+  int32_t* step;
+  int32_t* max_new;
+  int64_t* out_row;
+  int32_t* pos;
+  int32_t* finished;
+  int64_t* cur_tok;
+  int64_t out_row_value;
+  int32_t n_layers, S, slot, rows, src_lmax, kv_lmax, nkv, dtype16;
+  int32_t n_ids, hist_cap, n_image, max_new_value;
+} tcavt_slot_admit_args;
+
+int tcavt_slot_admit(const tcavt_slot_admit_args* args, tcavt_stream_t stream);
+
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 

@@ -1,0 +1,100 @@
+"""A request list through the slot pool (LlamaMultiModal.generate_pool) against the same requests as consecutive generate_batch
+calls, at the full model size (Llama-3.2-1B shape) on one MI355X, in one process.
+    python tools/bench_generate_pool.py [--requests 256] [--text-len 240] [--min-new 16] [--max-new 128] [--slots 8 32]
+                                        [--poll 1 8 32] [--reps 2] [--out profiles/generate_pool.txt]
+Requests end on per-request token budgets drawn uniformly from [min-new, max-new] with a fixed seed (random weights do not emit
+EOS on cue).  The baseline is what a caller has without the pool: batches of B requests, each run for max-new tokens (a static
+batch cannot know its rows' budgets: with EOS it runs until max_new_tokens whatever its rows do).  Greedy, fp16 weights and cache.
+Reported per configuration: wall time, useful tokens / s = sum of the budgets / wall time, and for the pool the decode steps and
+the mean number of live slots per step (tokens chosen in decode steps / steps)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from tcavt_amd import capi, config, model, synth
+from tcavt_amd.weights import make_weights
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--requests", type=int, default=256)
+ap.add_argument("--text-len", type=int, default=240)
+ap.add_argument("--min-new", type=int, default=16)
+ap.add_argument("--max-new", type=int, default=128)
+ap.add_argument("--slots", type=int, nargs="+", default=[8, 32])
+ap.add_argument("--poll", type=int, nargs="+", default=[1, 8, 32])
+ap.add_argument("--reps", type=int, default=2)
+ap.add_argument("--preset", default="llama32_1b")
+ap.add_argument("--out", default=None, help="also write the result lines to this file")
+args = ap.parse_args()
+capi.init(0)
+dev = torch.device("cuda:0")
+cfg = config.PRESETS[args.preset]()
+with torch.device(dev):
+    m = model.MultiModalTrajectoryModel.from_config(cfg)
+m.load_weights(make_weights(cfg, seed=1, backend="torch", device=dev)).eval()
+R = args.requests
+b = synth.make_batch(cfg, R, text_len=args.text_len, seed=3, ragged=True, min_text=min(128, args.text_len // 2))
+g = {k: torch.from_numpy(v).to(dev) for k, v in b.items()}
+budgets = np.random.default_rng(7).integers(args.min_new, args.max_new + 1, size=R).tolist()
+useful = int(sum(budgets))
+kw = dict(do_sample=False, repetition_penalty=1.0, no_repeat_ngram_size=0)
+
+
+def run_batches(B, n=R):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    outs = [m.mllm.generate_batch(g["vision_emb"][i:i + B], None, max_new_tokens=args.max_new, input_ids=g["input_ids"][i:i + B],
+                                  attention_mask=g["attention_mask"][i:i + B], **kw).clone() for i in range(0, n, B)]
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, torch.cat(outs)
+
+
+def run_pool(S, poll, n=R):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = m.mllm.generate_pool(g["vision_emb"][:n], g["input_ids"][:n], g["attention_mask"][:n], max_new_tokens=budgets[:n], slots=S,
+                               poll_every=poll, **kw)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+lines = []
+
+
+def report(**rec):
+    lines.append(json.dumps(rec))
+    print(lines[-1], flush=True)
+
+
+report(workload=f"{R} requests, prompt {cfg.q_num_query_tokens}+{args.text_len} tokens (ragged), budgets uniform {args.min_new}..{args.max_new} "
+                f"(seed 7): {useful} useful tokens, mean {useful / R:.1f}; greedy, fp16 weights and cache; hipGraph replay",
+       preset=args.preset)
+ref = {}
+for S in args.slots:  # warm-up of every shape the timed windows use: packed weights, workspaces, kernels, graph capture paths
+    run_batches(S, n=S)
+    run_pool(S, args.poll[0], n=min(R, 2 * S))
+for rep in range(args.reps):  # (the configurations alternate inside a repetition: the spread between repetitions is the noise)
+    for S in args.slots:
+        t, out_b = run_batches(S)
+        ref[S] = out_b
+        report(path="generate_batch", batch=S, rep=rep, wall_s=round(t, 3), useful_tokens_per_s=round(useful / t, 1),
+               decode_rows_computed=R * (args.max_new - 1), useful_share=round((useful - R) / (R * (args.max_new - 1)), 3))
+        for poll in args.poll:
+            t, out_p = run_pool(S, poll)
+            st = m.mllm.pool_stats
+            # a request's tokens in the pool are those of its row in a static batch, up to its budget (greedy; both paths compute a
+            # row independently of its neighbours, but a B = 1 prefill may round differently from the batched one: reported, not asserted)
+            same = sum(bool(torch.equal(out_p[r, :budgets[r]], out_b[r, :budgets[r]])) for r in range(R))
+            report(path="generate_pool", slots=S, poll_every=poll, rep=rep, wall_s=round(t, 3), useful_tokens_per_s=round(useful / t, 1),
+                   decode_steps=st["steps"], mean_live_slots_per_step=round((useful - R) / st["steps"], 2),
+                   requests_equal_to_static_batch=f"{same}/{R}",
+                   finite=bool(((out_p >= 0) & (out_p < cfg.llama.vocab)).all().item()))
+m.mllm.check_flags()
+if args.out:
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")

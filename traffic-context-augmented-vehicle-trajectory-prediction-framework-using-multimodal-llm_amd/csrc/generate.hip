@@ -377,6 +377,60 @@ __global__ __launch_bounds__(256) void gather_last_kernel(const bf16_t* __restri
     *reinterpret_cast<u32x4*>(out + (long)b * H + c) = *reinterpret_cast<const u32x4*>(s + c);
 }
 
+// tcavt_slot_admit: a freshly prefilled request (a one-sample cache) moves into slot `slot` of an S-slot cache and the slot's
+// bookkeeping is reset, in one launch.  Both cache forms are segments of consecutive rows on either side -- 16-bit: a layer of the
+// k or v cache, rows of nkv * 128 bytes; KV8: a (layer, kv head) of a plane, rows of 64 code bytes or 2 scale bytes -- so a thread
+// copies one 16-byte piece of a segment (or one row's two scale bytes), and one more workgroup behind the copying ones writes the
+// slot's state.  Segment g = (layer, i < inner) starts at row g * src_lmax of the source and at row
+// ((layer * S + slot) * inner + i) * kv_lmax of the destination.
+struct AdmitP {
+  const unsigned char* src[4];  // 16-bit: k, v; KV8: k codes, v codes, k scales, v scales
+  unsigned char* dst[4];
+  long pieces;   // 16-byte pieces of a segment: rows * row_bytes / 16
+  long n_wide;   // threads that copy a 16-byte piece: 2 * segs * pieces; behind them (KV8) 2 * segs * rows copy a scale pair
+  long n_copy;
+  int segs, inner, S, slot, rows, src_lmax, kv_lmax, row_bytes;
+  const long* prompt_ids;
+  const int* kv_len;
+  long* history;
+  int *hist_len, *step, *max_new, *pos, *finished;
+  long* out_row;
+  long out_row_value;
+  int n_ids, hist_cap, n_image, max_new_value;
+};
+
+__global__ __launch_bounds__(256) void slot_admit_kernel(AdmitP a) {
+  if (blockIdx.x == gridDim.x - 1) {  // the slot's state (cur_tok is the sampler's)
+    long* h = a.history + (long)a.slot * a.hist_cap;
+    for (int i = threadIdx.x; i < a.n_ids; i += 256) h[i] = a.prompt_ids[i];
+    if (threadIdx.x == 0) {
+      const int kl = *a.kv_len;
+      a.hist_len[a.slot] = kl - a.n_image;
+      a.pos[a.slot] = kl;
+      a.step[a.slot] = 0;
+      a.finished[a.slot] = 0;
+      a.max_new[a.slot] = a.max_new_value;
+      a.out_row[a.slot] = a.out_row_value;
+    }
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_copy) return;
+  const bool wide = i < a.n_wide;
+  const long j = wide ? i : i - a.n_wide;
+  const long per = wide ? a.pieces : (long)a.rows;  // units of a segment
+  const long per_plane = a.segs * per;
+  const int kv = (int)(j / per_plane);
+  const long r = j - kv * per_plane;
+  const long g = r / per, e = r - g * per;
+  const long srow = g * a.src_lmax, drow = ((g / a.inner * a.S + a.slot) * a.inner + g % a.inner) * a.kv_lmax;
+  if (wide) {
+    reinterpret_cast<u32x4*>(a.dst[kv] + drow * a.row_bytes)[e] = reinterpret_cast<const u32x4*>(a.src[kv] + srow * a.row_bytes)[e];
+  } else {
+    reinterpret_cast<unsigned short*>(a.dst[2 + kv] + drow * 2)[e] = reinterpret_cast<const unsigned short*>(a.src[2 + kv] + srow * 2)[e];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Logits processors + token selection, one workgroup per sample (HF generation: RepetitionPenaltyLogitsProcessor,
 // NoRepeatNGramLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, in that order; the warpers
@@ -630,12 +684,17 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
 }
 
 // `pre` (ws.cand_v != nullptr): stage 2 of the two-stage form -- the processors are done and the candidates come from the slices
+// SLOTS (tcavt_sample_logits_slots): the bookkeeping is per slot -- step_p, max_new and out_row are arrays [B]; slot b chooses token
+// step_p[b] of output row out_row[b] (which is also its Philox row), ends on EOS or when its budget max_new[b] is used up, and a
+// finished slot is inert: cur_tok[b] = pad and nothing else of its state is written.  The selection itself is the same code.
+template <bool SLOTS>
 __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logits, int V, long* __restrict__ history,
                                                        int hist_cap, int* __restrict__ hist_len, SampleP sp,
                                                        int* __restrict__ step_p, long* __restrict__ cur_tok,
                                                        int* __restrict__ pos, int* __restrict__ finished,
                                                        long* __restrict__ out_tokens, int out_cap, int advance_pos, SliceWs ws,
-                                                       int n_samples) {
+                                                       int n_samples, const int* __restrict__ max_new,
+                                                       const long* __restrict__ out_row) {
   __shared__ float cv[SMP_CAP];
   __shared__ int ci[SMP_CAP];
   __shared__ float rv[SMP_T / 64];
@@ -651,7 +710,7 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
   float* x = logits + (long)b * V;
   long* hist = history + (long)b * hist_cap;
   const int hl = min(hist_len[b], hist_cap);
-  const int step = *step_p;
+  const int step = SLOTS ? step_p[b] : *step_p;
   const bool pre = ws.cand_v != nullptr;
   __shared__ int s_ovf;
   if (pre) {
@@ -920,7 +979,7 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
       float kt = 0.f;
       for (int j = 0; j < keep; ++j) kt += __expf(cv[j] - m);
       unsigned int r[4];
-      philox4x32_10((unsigned int)step, (unsigned int)b, 0x5A3Bu, 0u, sp.seed_lo, sp.seed_hi, r);
+      philox4x32_10((unsigned int)step, SLOTS ? (unsigned int)out_row[b] : (unsigned int)b, 0x5A3Bu, 0u, sp.seed_lo, sp.seed_hi, r);
       const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f) * kt;
       float acc = 0.f;
       int pick = keep - 1;
@@ -932,6 +991,24 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
     }
     __syncthreads();
     tok = besti;
+  }
+  if constexpr (SLOTS) {
+    if (tid == 0) {
+      if (finished[b] != 0) {  // inert: the decode step keeps running this slot on the pad token at its frozen position
+        cur_tok[b] = sp.pad;
+      } else {
+        if (step < out_cap) out_tokens[out_row[b] * out_cap + step] = tok;
+        cur_tok[b] = tok;
+        if (hl < hist_cap) {
+          hist[hl] = tok;
+          hist_len[b] = hl + 1;
+        }
+        if (advance_pos) pos[b] += 1;
+        if ((sp.eos >= 0 && tok == sp.eos) || step + 1 == max_new[b]) finished[b] = 1;
+        step_p[b] = step + 1;  // (the slot's own word: no ticket)
+      }
+    }
+    return;
   }
   if (tid == 0) {
     // a finished sample keeps emitting the pad token (HF generate pads finished rows)
@@ -974,16 +1051,15 @@ extern "C" int64_t tcavt_sample_workspace_bytes(int B) {
   return 64 + (((int64_t)B * 4 + 63) & ~(int64_t)63) + (int64_t)B * SMP_G * 8 + (int64_t)B * SMP_G * SMP_LCAP * 8;
 }
 
-extern "C" int tcavt_sample_logits(float* logits, int B, int V, int64_t* history, int hist_cap, int32_t* hist_len,
-                                   const tcavt_sample_params* sp, int32_t* step, int64_t* cur_tok, int32_t* pos,
-                                   int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
-                                   int64_t workspace_bytes, tcavt_stream_t stream) {
-  TCAVT_CHECK_ARG(logits && history && hist_len && sp && step && cur_tok && pos && finished && out_tokens && B > 0 && V > 0 &&
-                      hist_cap > 0 && out_cap > 0,
-                  "sample_logits: bad args");
+// tcavt_sample_logits (max_new == out_row == NULL, one step word) and tcavt_sample_logits_slots (arrays [B]) share the launches
+static int sample_logits_impl(const char* who, float* logits, int B, int V, int64_t* history, int hist_cap, int32_t* hist_len,
+                              const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row, int64_t* cur_tok,
+                              int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
+                              int64_t workspace_bytes, tcavt_stream_t stream) {
+  const bool slots = max_new || out_row;
   TCAVT_CHECK_ARG(!sp->do_sample || (sp->temperature > 0.f && sp->top_k >= 1 && sp->top_k <= SMP_CAP && sp->top_p > 0.f && sp->top_p <= 1.f),
-                  "sample_logits: sampling needs temperature > 0, 1 <= top_k <= %d, 0 < top_p <= 1", SMP_CAP);
-  TCAVT_CHECK_ARG(sp->repetition_penalty > 0.f && sp->no_repeat_ngram_size >= 0, "sample_logits: bad repetition_penalty / no_repeat_ngram_size");
+                  "%s: sampling needs temperature > 0, 1 <= top_k <= %d, 0 < top_p <= 1", who, SMP_CAP);
+  TCAVT_CHECK_ARG(sp->repetition_penalty > 0.f && sp->no_repeat_ngram_size >= 0, "%s: bad repetition_penalty / no_repeat_ngram_size", who);
   SampleP p;
   p.temperature = sp->temperature; p.top_p = sp->top_p; p.rep_penalty = sp->repetition_penalty;
   p.top_k = sp->top_k; p.no_repeat_ngram = sp->no_repeat_ngram_size; p.do_sample = sp->do_sample;
@@ -995,7 +1071,7 @@ extern "C" int tcavt_sample_logits(float* logits, int B, int V, int64_t* history
   const int64_t need = tcavt_sample_workspace_bytes(B);
   const int chunk4 = ((V >> 2) + SMP_G - 1) / SMP_G;
   if (workspace && workspace_bytes >= need && (V & 3) == 0 && aligned16(logits) && chunk4 <= SMP_E4 * SMP_T) {
-    TCAVT_CHECK_ARG(aligned16(workspace), "sample_logits: workspace must be 16-byte aligned");
+    TCAVT_CHECK_ARG(aligned16(workspace), "%s: workspace must be 16-byte aligned", who);
     char* w = static_cast<char*>(workspace);
     ws.ticket = reinterpret_cast<int*>(w);
     ws.ovf = reinterpret_cast<int*>(w + 64);
@@ -1007,12 +1083,39 @@ extern "C" int tcavt_sample_logits(float* logits, int B, int V, int64_t* history
     hipLaunchKernelGGL(sample_slice_kernel, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V, reinterpret_cast<const long*>(history), hist_cap,
                        hist_len, p, ws);
   }
-  hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(SMP_T), 0, st, logits, V, reinterpret_cast<long*>(history), hist_cap,
-                     hist_len, p, step, reinterpret_cast<long*>(cur_tok), pos, finished, reinterpret_cast<long*>(out_tokens),
-                     out_cap, advance_pos, ws, B);
-  if (!ws.cand_v) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
-  TCAVT_CHECK_LAUNCH("sample_logits");
+  hipLaunchKernelGGL(slots ? sample_kernel<true> : sample_kernel<false>, dim3(B), dim3(SMP_T), 0, st, logits, V,
+                     reinterpret_cast<long*>(history), hist_cap, hist_len, p, step, reinterpret_cast<long*>(cur_tok), pos, finished,
+                     reinterpret_cast<long*>(out_tokens), out_cap, advance_pos, ws, B, max_new, reinterpret_cast<const long*>(out_row));
+  if (!ws.cand_v && !slots) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
+  TCAVT_CHECK_LAUNCH(who);
   return TCAVT_OK;
+}
+
+extern "C" int tcavt_sample_logits(float* logits, int B, int V, int64_t* history, int hist_cap, int32_t* hist_len,
+                                   const tcavt_sample_params* sp, int32_t* step, int64_t* cur_tok, int32_t* pos,
+                                   int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
+                                   int64_t workspace_bytes, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(logits && history && hist_len && sp && step && cur_tok && pos && finished && out_tokens && B > 0 && V > 0 &&
+                      hist_cap > 0 && out_cap > 0,
+                  "sample_logits: bad args");
+  return sample_logits_impl("sample_logits", logits, B, V, history, hist_cap, hist_len, sp, step, nullptr, nullptr, cur_tok, pos, finished,
+                            out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tcavt_sample_logits_slots(float* logits, int S, int V, int64_t* history, int hist_cap, int32_t* hist_len,
+                                         const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row,
+                                         int64_t* cur_tok, int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap,
+                                         int advance_pos, void* workspace, int64_t workspace_bytes, tcavt_stream_t stream) {
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {logits, "logits"}, {history, "history"}, {hist_len, "hist_len"}, {sp, "params"}, {step, "step"}, {max_new, "max_new"},
+      {out_row, "out_row"}, {cur_tok, "cur_tok"}, {pos, "pos"}, {finished, "finished"}, {out_tokens, "out_tokens"}};
+  for (const auto& a : ptrs) TCAVT_CHECK_ARG(a.p, "sample_logits_slots: %s is a null pointer", a.name);
+  TCAVT_CHECK_ARG(S > 0, "sample_logits_slots: S = %d must be > 0", S);
+  TCAVT_CHECK_ARG(V > 0, "sample_logits_slots: V = %d must be > 0", V);
+  TCAVT_CHECK_ARG(hist_cap > 0, "sample_logits_slots: hist_cap = %d must be > 0", hist_cap);
+  TCAVT_CHECK_ARG(out_cap > 0, "sample_logits_slots: out_cap = %d must be > 0", out_cap);
+  return sample_logits_impl("sample_logits_slots", logits, S, V, history, hist_cap, hist_len, sp, step, max_new, out_row, cur_tok, pos,
+                            finished, out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H,
@@ -1093,6 +1196,65 @@ extern "C" int tcavt_attn_decode8(const void* qkv, void* k_codes, void* k_scales
                      static_cast<unsigned char*>(k_codes), static_cast<unsigned char*>(k_scales), static_cast<unsigned char*>(v_codes),
                      static_cast<unsigned char*>(v_scales), pos, static_cast<bf16_t*>(out), kv_lmax, nq, nkv, scale, KS, out_layout);
   TCAVT_CHECK_LAUNCH("attn_decode8");
+  return TCAVT_OK;
+}
+
+extern "C" int tcavt_slot_admit(const tcavt_slot_admit_args* a, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "slot_admit: args is a null pointer");
+  const bool f16 = a->src_k || a->src_v || a->dst_k || a->dst_v;
+  const bool kv8 = a->src_k_codes || a->src_k_scales || a->src_v_codes || a->src_v_scales || a->dst_k_codes || a->dst_k_scales ||
+                   a->dst_v_codes || a->dst_v_scales;
+  TCAVT_CHECK_ARG(!(f16 && kv8), "slot_admit: the 16-bit caches (src_k .. dst_v) and the kv8 planes exclude each other");
+  TCAVT_CHECK_ARG(f16 || kv8, "slot_admit: null pointer (src_k / src_v / dst_k / dst_v, or the eight kv8 planes)");
+  TCAVT_CHECK_ARG(!f16 || (a->src_k && a->src_v && a->dst_k && a->dst_v), "slot_admit: null pointer: src_k, src_v, dst_k and dst_v come together");
+  TCAVT_CHECK_ARG(!kv8 || (a->src_k_codes && a->src_k_scales && a->src_v_codes && a->src_v_scales && a->dst_k_codes && a->dst_k_scales &&
+                           a->dst_v_codes && a->dst_v_scales),
+                  "slot_admit: null pointer: the eight kv8 planes come together");
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {a->prompt_ids, "prompt_ids"}, {a->kv_len, "kv_len"}, {a->history, "history"}, {a->hist_len, "hist_len"}, {a->step, "step"},
+      {a->max_new, "max_new"}, {a->out_row, "out_row"}, {a->pos, "pos"}, {a->finished, "finished"}, {a->cur_tok, "cur_tok"}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p, "slot_admit: %s is a null pointer", q.name);
+  TCAVT_CHECK_ARG(is16(a->dtype16), "slot_admit: dtype16 must be TCAVT_F16 or TCAVT_BF16");
+  TCAVT_CHECK_ARG(a->n_layers > 0 && a->S > 0 && a->nkv > 0 && a->src_lmax > 0 && a->kv_lmax > 0,
+                  "slot_admit: bad shape (n_layers, S, nkv, src_lmax, kv_lmax > 0)");
+  TCAVT_CHECK_ARG(a->slot >= 0 && a->slot < a->S, "slot_admit: slot = %d outside [0, S = %d)", a->slot, a->S);
+  TCAVT_CHECK_ARG(a->rows >= 1 && a->rows <= std::min(a->src_lmax, a->kv_lmax), "slot_admit: rows = %d must be in [1, min(src_lmax = %d, kv_lmax = %d)]",
+                  a->rows, a->src_lmax, a->kv_lmax);
+  TCAVT_CHECK_ARG(a->hist_cap > 0 && a->n_ids >= 0 && a->n_ids <= a->hist_cap, "slot_admit: n_ids = %d must be in [0, hist_cap = %d]", a->n_ids,
+                  a->hist_cap);
+  TCAVT_CHECK_ARG(a->n_image >= 0 && a->max_new_value >= 1 && a->out_row_value >= 0,
+                  "slot_admit: n_image >= 0, max_new_value >= 1 and out_row_value >= 0 required");
+  AdmitP p = {};
+  if (kv8) {
+    TCAVT_CHECK_ARG(aligned16(a->src_k_codes) && aligned16(a->src_v_codes) && aligned16(a->dst_k_codes) && aligned16(a->dst_v_codes),
+                    "slot_admit: the code planes must be 16-byte aligned");
+    TCAVT_CHECK_ARG(((reinterpret_cast<uintptr_t>(a->src_k_scales) | reinterpret_cast<uintptr_t>(a->src_v_scales) |
+                      reinterpret_cast<uintptr_t>(a->dst_k_scales) | reinterpret_cast<uintptr_t>(a->dst_v_scales)) & 1) == 0,
+                    "slot_admit: the scale planes must be 2-byte aligned");
+    const void* src[4] = {a->src_k_codes, a->src_v_codes, a->src_k_scales, a->src_v_scales};
+    void* dst[4] = {a->dst_k_codes, a->dst_v_codes, a->dst_k_scales, a->dst_v_scales};
+    for (int i = 0; i < 4; ++i) { p.src[i] = static_cast<const unsigned char*>(src[i]); p.dst[i] = static_cast<unsigned char*>(dst[i]); }
+    p.inner = a->nkv; p.row_bytes = 64;
+  } else {
+    TCAVT_CHECK_ARG(aligned16(a->src_k) && aligned16(a->src_v) && aligned16(a->dst_k) && aligned16(a->dst_v),
+                    "slot_admit: the caches must be 16-byte aligned");
+    p.src[0] = static_cast<const unsigned char*>(a->src_k); p.src[1] = static_cast<const unsigned char*>(a->src_v);
+    p.dst[0] = static_cast<unsigned char*>(a->dst_k); p.dst[1] = static_cast<unsigned char*>(a->dst_v);
+    p.inner = 1; p.row_bytes = a->nkv * 128;
+  }
+  p.segs = a->n_layers * p.inner;
+  p.S = a->S; p.slot = a->slot; p.rows = a->rows; p.src_lmax = a->src_lmax; p.kv_lmax = a->kv_lmax;
+  p.pieces = (long)a->rows * (p.row_bytes / 16);
+  p.n_wide = 2L * p.segs * p.pieces;
+  p.n_copy = p.n_wide + (kv8 ? 2L * p.segs * a->rows : 0L);
+  const long blocks = (p.n_copy + 255) / 256 + 1;
+  TCAVT_CHECK_ARG(blocks <= 0x7fffffffL, "slot_admit: too many rows");
+  p.prompt_ids = reinterpret_cast<const long*>(a->prompt_ids); p.kv_len = a->kv_len; p.history = reinterpret_cast<long*>(a->history);
+  p.hist_len = a->hist_len; p.step = a->step; p.max_new = a->max_new; p.pos = a->pos; p.finished = a->finished;
+  p.out_row = reinterpret_cast<long*>(a->out_row); p.out_row_value = a->out_row_value;
+  p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image; p.max_new_value = a->max_new_value;
+  hipLaunchKernelGGL(slot_admit_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  TCAVT_CHECK_LAUNCH("slot_admit");
   return TCAVT_OK;
 }
 

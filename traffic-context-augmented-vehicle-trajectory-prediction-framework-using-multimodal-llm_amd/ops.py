@@ -1096,6 +1096,70 @@ def sample_logits(logits, history, hist_len, params, step, cur_tok, pos, finishe
                                     stream_ptr()), "tcavt_sample_logits")
 
 
+def sample_logits_slots(logits, history, hist_len, params, step, max_new, out_row, cur_tok, pos, finished, out_tokens, advance_pos,
+                        workspace=None):
+    """sample_logits with per-slot bookkeeping (tcavt_sample_logits_slots): step / max_new int32 [S], out_row int64 [S] -- slot s
+    chooses token step[s] of out_tokens[out_row[s]] (its Philox row too), ends on EOS or at its budget, and is inert once finished.
+    The state tensors may be views that start at a slot (one-row logits of a request being admitted)."""
+    S, V = logits.shape
+    if workspace is not None:
+        _req(workspace, torch.uint8, "sample_logits_slots.workspace")
+    _req(logits, torch.float32, "sample_logits_slots.logits")
+    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (step, torch.int32, S, "step"),
+                         (max_new, torch.int32, S, "max_new"), (out_row, torch.int64, S, "out_row"), (cur_tok, torch.int64, S, "cur_tok"),
+                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (out_tokens, torch.int64, 1, "out_tokens")):
+        _req(t, dt, "sample_logits_slots." + nm)
+        _need(t, n, "sample_logits_slots." + nm)
+    if history.dim() != 2 or history.shape[0] != S or out_tokens.dim() != 2:
+        raise capi.TcavtError("sample_logits_slots: history needs one row per slot, out_tokens one row per request")
+    check(lib().tcavt_sample_logits_slots(ptr(logits), S, V, ptr(history), history.shape[1], ptr(hist_len), ctypes.byref(params),
+                                          ptr(step), ptr(max_new), ptr(out_row), ptr(cur_tok), ptr(pos), ptr(finished),
+                                          ptr(out_tokens), out_tokens.shape[1], int(advance_pos), ptr(workspace),
+                                          workspace.numel() if workspace is not None else 0, stream_ptr()),
+          "tcavt_sample_logits_slots")
+
+
+def slot_admit(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value, out_row_value,
+               history, hist_len, step, max_new, out_row, pos, finished, cur_tok):
+    """A freshly prefilled request moves into slot `slot` of an S-slot pool in one launch (tcavt_slot_admit).  src / dst: the
+    one-sample cache and the pool's cache, both (k, v) 16-bit [n_layers, 1 | S, lmax, nkv * 64] or both the four KV8 planes
+    (k_codes, k_scales, v_codes, v_scales) [n_layers, 1 | S, nkv, lmax, 64 | 2]; rows 0 .. rows - 1 are copied byte for byte.
+    The slot's state: history row = prompt_ids, hist_len = *kv_len - n_image, pos = *kv_len, step = 0, finished = 0, max_new and
+    out_row as given; cur_tok is left for the sampler."""
+    a = capi.SlotAdmitArgs()
+    if len(src) != len(dst) or len(src) not in (2, 4):
+        raise capi.TcavtError("slot_admit: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
+    if len(src) == 2:
+        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, 1), (src[1], "src_v", src_lmax, 1), (dst[0], "dst_k", kv_lmax, S), (dst[1], "dst_v", kv_lmax, S)):
+            _req16(t, "slot_admit." + nm, like=src[0])
+            _need(t, n_layers * n * lmax * nkv * 64, "slot_admit." + nm)
+            setattr(a, nm, t.data_ptr())
+        a.dtype16 = _DT[src[0].dtype]
+    else:
+        _kv8_planes(src, n_layers * nkv * src_lmax, "slot_admit.src")
+        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, "slot_admit.dst")
+        for side, planes in (("src", src), ("dst", dst)):
+            for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
+                setattr(a, f"{side}_{nm}", t.data_ptr())
+        a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+    _req(prompt_ids, torch.int64, "slot_admit.prompt_ids")
+    _req(kv_len, torch.int32, "slot_admit.kv_len")
+    _need(kv_len, 1, "slot_admit.kv_len")
+    for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
+                      (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
+                      (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
+        _req(t, dt, "slot_admit." + nm)
+        _need(t, S, "slot_admit." + nm)
+        setattr(a, nm, t.data_ptr())
+    if history.dim() != 2 or history.shape[0] != S:
+        raise capi.TcavtError("slot_admit: history needs one row per slot")
+    a.prompt_ids, a.kv_len = prompt_ids.data_ptr(), kv_len.data_ptr()
+    a.n_layers, a.S, a.slot, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, S, int(slot), int(rows), src_lmax, kv_lmax, nkv
+    a.n_ids, a.hist_cap, a.n_image = prompt_ids.numel(), history.shape[1], int(n_image)
+    a.max_new_value, a.out_row_value = int(max_new_value), int(out_row_value)
+    check(lib().tcavt_slot_admit(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit")
+
+
 def gather_last(src16, kv_len, out16, B, L, H):
     _req16(src16, "gather_last.src16")
     _req16(out16, "gather_last.out16", like=src16)
