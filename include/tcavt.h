@@ -1193,6 +1193,71 @@ typedef struct tcavt_slot_admit_args {
 
 int tcavt_slot_admit(const tcavt_slot_admit_args* args, tcavt_stream_t stream);
 
+/* The grouped form of tcavt_slot_admit: G freshly prefilled requests (a G-sample cache, what tcavt_llama_stack_forward wrote at
+ * B = G) move into their slots of an S-slot pool in ONE launch, and everything that differs per row comes from DEVICE arrays, so
+ * that the launch is the same for every group (hipGraph-capturable):
+ *   16-bit: src_k / src_v [n_layers][G][src_lmax][nkv * 64]  ->  dst_k / dst_v [n_layers][S][kv_lmax][nkv * 64]
+ *   KV8:    the four planes [n_layers][G][nkv][src_lmax][64 | 2]  ->  [n_layers][S][nkv][kv_lmax][64 | 2]
+ * (one form, all of its pointers, none of the other's, as in tcavt_slot_admit).
+ *   slot           int32 [G]: the destination slot of row g.  slot[g] < 0: a PAD row -- nothing of it is read or written.
+ *                  slot[g] >= S: nothing is written for the row and *bad_slot_flag is set to 1; the kernel never faults on a
+ *                  bad value.  The slots of a group must be DISTINCT: that is the caller's contract and is not checked (two rows
+ *                  with one slot would race on its bytes).
+ *   kv_len         int32 [G]: the prefill's kv_len per row (n_image + valid prompt tokens)
+ *   max_new_value  int32 [G], out_row_value int64 [G]: the request's budget and its output / Philox row
+ *   prompt_ids     int64 [G][n_ids]: the prompt rows (right padded)
+ * For an admitted row g with s = slot[g]: rows 0 .. rows - 1 of every layer and kv head of slot s become the source's rows of
+ * sample g, byte for byte (16-byte pieces; the scale planes in 2-byte pieces), and no other byte of the destination changes.
+ * State, exactly as tcavt_slot_admit: history[s][0 .. n_ids) = prompt_ids[g]; hist_len[s] = kv_len[g] - n_image; pos[s] = kv_len[g];
+ * step[s] = 0; finished[s] = 0; max_new[s] = max_new_value[g]; out_row[s] = out_row_value[g]; cur_tok is left for the sampler.
+ * Refused before the launch (tcavt_last_error names the argument): null or mixed pointers, caches / code planes that are not
+ * 16-byte aligned (scale planes: 2-byte), rows outside [1, min(src_lmax, kv_lmax)], G < 1, n_ids outside [0, hist_cap]. */
+typedef struct tcavt_slot_admit_group_args {
+  const void* src_k;               /* 16-bit form (all four, or none) */
+  const void* src_v;
+  void* dst_k;
+  void* dst_v;
+  const void* src_k_codes;         /* KV8 form (all eight, or none) */
+  const void* src_k_scales;
+  const void* src_v_codes;
+  const void* src_v_scales;
+  void* dst_k_codes;
+  void* dst_k_scales;
+  void* dst_v_codes;
+  void* dst_v_scales;
+  const int32_t* slot;             /* device int32 [G] */
+  const int32_t* kv_len;           /* device int32 [G] */
+  const int32_t* max_new_value;    /* device int32 [G] */
+  const int64_t* out_row_value;    /* device int64 [G] */
+  const int64_t* prompt_ids;       /* device int64 [G][n_ids] */
+  int32_t* bad_slot_flag;          /* device int32 [1] */
+  int64_t* history;                /* int64 [S][hist_cap] */
+  int32_t* hist_len;               /* the S-slot arrays of tcavt_sample_logits_slots */
+  int32_t* step;
+  int32_t* max_new;
+  int64_t* out_row;
+  int32_t* pos;
+  int32_t* finished;
+  int64_t* cur_tok;
+  int32_t n_layers, S, G, rows, src_lmax, kv_lmax, nkv, dtype16;
+  int32_t n_ids, hist_cap, n_image, reserved;
+} tcavt_slot_admit_group_args;
+
+int tcavt_slot_admit_group(const tcavt_slot_admit_group_args* args, tcavt_stream_t stream);
+
+/* tcavt_sample_logits_slots for the G logits rows of a grouped admission: logits fp32 [G][V]; slot_of_row device int32 [G]; logits
+ * row g chooses a token for slot s = slot_of_row[g] of the S-slot state arrays (history [S][hist_cap], hist_len, step, max_new,
+ * out_row, cur_tok, pos, finished: all [S]) -- exactly the token tcavt_sample_logits_slots chooses for that logits row and that
+ * slot's state: same processors, candidate order, first-maximum rule and Philox counter (step[s], out_row[s], 0x5A3B, 0); the
+ * state of slot s advances as there.  A row whose map entry is negative or >= S is SKIPPED: no state, no out_tokens element,
+ * no logits element and no workspace word is written for it.  The entries >= 0 must be distinct (the caller's contract).
+ * Both forms exist; the workspace is tcavt_sample_workspace_bytes(G) bytes under the contract of tcavt_sample_logits: control
+ * words zero between calls, and calls may alternate with the other two entries on one workspace. */
+int tcavt_sample_logits_rows(float* logits, int G, int V, const int32_t* slot_of_row, int S, int64_t* history, int hist_cap,
+                             int32_t* hist_len, const tcavt_sample_params* params, int32_t* step, const int32_t* max_new,
+                             const int64_t* out_row, int64_t* cur_tok, int32_t* pos, int32_t* finished, int64_t* out_tokens,
+                             int out_cap, int advance_pos, void* workspace, int64_t workspace_bytes, tcavt_stream_t stream);
+
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 

@@ -1,12 +1,15 @@
 """A request list through the slot pool (LlamaMultiModal.generate_pool) against the same requests as consecutive generate_batch
 calls, at the full model size (Llama-3.2-1B shape) on one MI355X, in one process.
     python tools/bench_generate_pool.py [--requests 256] [--text-len 240] [--min-new 16] [--max-new 128] [--slots 8 32]
-                                        [--poll 1 8 32] [--reps 2] [--out profiles/generate_pool.txt]
+                                        [--poll 1 8 32] [--admit-group 1 2 4 8] [--reps 2] [--out profiles/generate_pool.txt]
 Requests end on per-request token budgets drawn uniformly from [min-new, max-new] with a fixed seed (random weights do not emit
 EOS on cue).  The baseline is what a caller has without the pool: batches of B requests, each run for max-new tokens (a static
 batch cannot know its rows' budgets: with EOS it runs until max_new_tokens whatever its rows do).  Greedy, fp16 weights and cache.
 Reported per configuration: wall time, useful tokens / s = sum of the budgets / wall time, and for the pool the decode steps and
-the mean number of live slots per step (tokens chosen in decode steps / steps)."""
+the mean number of live slots per step (tokens chosen in decode steps / steps).
+--admit-group: the widths G of the grouped admission (generate_pool(admit_group=G)) to run as further arms, 1 = one request per
+prefill; per arm also the group passes and the pad rows they carried, and after each repetition, per G, equal_across_pool_sizes = the
+requests whose tokens are identical at every pool size (the contract of a fixed G: all of them)."""
 import argparse
 import json
 import os
@@ -27,6 +30,7 @@ ap.add_argument("--min-new", type=int, default=16)
 ap.add_argument("--max-new", type=int, default=128)
 ap.add_argument("--slots", type=int, nargs="+", default=[8, 32])
 ap.add_argument("--poll", type=int, nargs="+", default=[1, 8, 32])
+ap.add_argument("--admit-group", type=int, nargs="+", default=[1])
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--preset", default="llama32_1b")
 ap.add_argument("--out", default=None, help="also write the result lines to this file")
@@ -54,11 +58,11 @@ def run_batches(B, n=R):
     return time.perf_counter() - t0, torch.cat(outs)
 
 
-def run_pool(S, poll, n=R):
+def run_pool(S, poll, n=R, G=1):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = m.mllm.generate_pool(g["vision_emb"][:n], g["input_ids"][:n], g["attention_mask"][:n], max_new_tokens=budgets[:n], slots=S,
-                               poll_every=poll, **kw)
+                               poll_every=poll, admit_group=G, **kw)
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
 
@@ -77,23 +81,34 @@ report(workload=f"{R} requests, prompt {cfg.q_num_query_tokens}+{args.text_len} 
 ref = {}
 for S in args.slots:  # warm-up of every shape the timed windows use: packed weights, workspaces, kernels, graph capture paths
     run_batches(S, n=S)
-    run_pool(S, args.poll[0], n=min(R, 2 * S))
+    for G in args.admit_group:  # (2 S requests: the eager group pass, its capture and a replay)
+        if G <= S:
+            run_pool(S, args.poll[0], n=min(R, 2 * S), G=G)
 for rep in range(args.reps):  # (the configurations alternate inside a repetition: the spread between repetitions is the noise)
+    by_group = {}
     for S in args.slots:
         t, out_b = run_batches(S)
         ref[S] = out_b
         report(path="generate_batch", batch=S, rep=rep, wall_s=round(t, 3), useful_tokens_per_s=round(useful / t, 1),
                decode_rows_computed=R * (args.max_new - 1), useful_share=round((useful - R) / (R * (args.max_new - 1)), 3))
-        for poll in args.poll:
-            t, out_p = run_pool(S, poll)
+        for poll, G in ((p_, g_) for p_ in args.poll for g_ in args.admit_group if g_ <= S):
+            t, out_p = run_pool(S, poll, G=G)
             st = m.mllm.pool_stats
+            by_group.setdefault((poll, G), []).append(out_p.clone())
             # a request's tokens in the pool are those of its row in a static batch, up to its budget (greedy; both paths compute a
             # row independently of its neighbours, but a B = 1 prefill may round differently from the batched one: reported, not asserted)
             same = sum(bool(torch.equal(out_p[r, :budgets[r]], out_b[r, :budgets[r]])) for r in range(R))
-            report(path="generate_pool", slots=S, poll_every=poll, rep=rep, wall_s=round(t, 3), useful_tokens_per_s=round(useful / t, 1),
-                   decode_steps=st["steps"], mean_live_slots_per_step=round((useful - R) / st["steps"], 2),
+            report(path="generate_pool", slots=S, poll_every=poll, admit_group=G, rep=rep, wall_s=round(t, 3),
+                   useful_tokens_per_s=round(useful / t, 1), decode_steps=st["steps"],
+                   mean_live_slots_per_step=round((useful - R) / st["steps"], 2), group_passes=len(st["groups"]),
+                   pad_rows=sum(G - len(reqs) for reqs, _, _ in st["groups"]),
                    requests_equal_to_static_batch=f"{same}/{R}",
                    finite=bool(((out_p >= 0) & (out_p < cfg.llama.vocab)).all().item()))
+    for (poll, G), outs in by_group.items():
+        if len(outs) > 1:
+            same = sum(all(bool(torch.equal(o[r], outs[0][r])) for o in outs[1:]) for r in range(R))
+            report(check="equal_across_pool_sizes", poll_every=poll, admit_group=G, rep=rep, slots=[S for S in args.slots if G <= S],
+                   requests=f"{same}/{R}")
 m.mllm.check_flags()
 if args.out:
     with open(args.out, "w") as f:

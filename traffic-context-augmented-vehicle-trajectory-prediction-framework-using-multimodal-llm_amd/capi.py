@@ -232,6 +232,17 @@ class SlotAdmitArgs(ctypes.Structure):
             "n_layers", "S", "slot", "rows", "src_lmax", "kv_lmax", "nkv", "dtype16", "n_ids", "hist_cap", "n_image", "max_new_value")]
 
 
+class SlotAdmitGroupArgs(ctypes.Structure):
+    """Mirror of ``tcavt_slot_admit_group_args`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in (
+        "src_k", "src_v", "dst_k", "dst_v", "src_k_codes", "src_k_scales", "src_v_codes", "src_v_scales", "dst_k_codes",
+        "dst_k_scales", "dst_v_codes", "dst_v_scales", "slot", "kv_len", "max_new_value", "out_row_value", "prompt_ids",
+        "bad_slot_flag", "history", "hist_len", "step", "max_new", "out_row", "pos", "finished", "cur_tok")] + [
+            (n, ctypes.c_int32) for n in ("n_layers", "S", "G", "rows", "src_lmax", "kv_lmax", "nkv", "dtype16", "n_ids", "hist_cap",
+                                          "n_image", "reserved")]
+
+
 class DecodeArgs(ctypes.Structure):
     """Mirror of ``tcavt_decode_args`` (include/tcavt.h)."""
 
@@ -363,6 +374,10 @@ _SIGNATURES = {
     "tcavt_sample_logits_slots": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(SampleParams), c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p],
     "tcavt_slot_admit": [ctypes.POINTER(SlotAdmitArgs), c_void_p],
+    "tcavt_slot_admit_group": [ctypes.POINTER(SlotAdmitGroupArgs), c_void_p],
+    "tcavt_sample_logits_rows": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(SampleParams),
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                 c_int64, c_void_p],
     "tcavt_sample_workspace_bytes": [c_int],
     "tcavt_gather_last": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "tcavt_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,

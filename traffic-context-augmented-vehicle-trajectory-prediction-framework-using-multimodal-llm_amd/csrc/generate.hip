@@ -431,6 +431,69 @@ __global__ __launch_bounds__(256) void slot_admit_kernel(AdmitP a) {
   }
 }
 
+// tcavt_slot_admit_group: slot_admit_kernel for the G samples of a grouped prefill, blockIdx.y = the group's row.  The source is a
+// G-sample cache, so segment (layer, i < inner) of row g starts at source row ((layer * G + g) * inner + i) * src_lmax; the slot, the
+// kv_len, the budget and the output row of a row are read from DEVICE arrays (the launch is the same for every group: capturable).
+// slot[g] < 0: a pad row, its workgroups leave at once; slot[g] >= S: nothing is written but the flag.  Every index below is
+// bounded by the host-checked shape once 0 <= slot < S holds.
+struct AdmitGroupP {
+  const unsigned char* src[4];
+  unsigned char* dst[4];
+  long pieces, n_wide, n_copy;  // as AdmitP, per row of the group
+  int segs, inner, S, G, rows, src_lmax, kv_lmax, row_bytes;
+  const int* slot;
+  const int* kv_len;
+  const int* max_new_value;
+  const long* out_row_value;
+  const long* prompt_ids;
+  int* bad_slot_flag;
+  long* history;
+  int *hist_len, *step, *max_new, *pos, *finished;
+  long* out_row;
+  int n_ids, hist_cap, n_image;
+};
+
+__global__ __launch_bounds__(256) void slot_admit_group_kernel(AdmitGroupP a) {
+  const int g = blockIdx.y;
+  const int slot = a.slot[g];
+  if (slot < 0) return;  // pad row
+  if (slot >= a.S) {
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *a.bad_slot_flag = 1;
+    return;
+  }
+  if (blockIdx.x == gridDim.x - 1) {  // the slot's state (cur_tok is the sampler's)
+    long* h = a.history + (long)slot * a.hist_cap;
+    const long* ids = a.prompt_ids + (long)g * a.n_ids;
+    for (int i = threadIdx.x; i < a.n_ids; i += 256) h[i] = ids[i];
+    if (threadIdx.x == 0) {
+      const int kl = a.kv_len[g];
+      a.hist_len[slot] = kl - a.n_image;
+      a.pos[slot] = kl;
+      a.step[slot] = 0;
+      a.finished[slot] = 0;
+      a.max_new[slot] = a.max_new_value[g];
+      a.out_row[slot] = a.out_row_value[g];
+    }
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_copy) return;
+  const bool wide = i < a.n_wide;
+  const long j = wide ? i : i - a.n_wide;
+  const long per = wide ? a.pieces : (long)a.rows;  // units of a segment
+  const long per_plane = a.segs * per;
+  const int kv = (int)(j / per_plane);
+  const long r = j - kv * per_plane;
+  const long sg = r / per, e = r - sg * per;
+  const long layer = sg / a.inner, in = sg % a.inner;
+  const long srow = ((layer * a.G + g) * a.inner + in) * a.src_lmax, drow = ((layer * a.S + slot) * a.inner + in) * a.kv_lmax;
+  if (wide) {
+    reinterpret_cast<u32x4*>(a.dst[kv] + drow * a.row_bytes)[e] = reinterpret_cast<const u32x4*>(a.src[kv] + srow * a.row_bytes)[e];
+  } else {
+    reinterpret_cast<unsigned short*>(a.dst[2 + kv] + drow * 2)[e] = reinterpret_cast<const unsigned short*>(a.src[2 + kv] + srow * 2)[e];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Logits processors + token selection, one workgroup per sample (HF generation: RepetitionPenaltyLogitsProcessor,
 // NoRepeatNGramLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, in that order; the warpers
@@ -500,7 +563,8 @@ struct SliceWs {  // views into the caller's workspace (tcavt_sample_logits: lay
 };
 
 __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__ logits, int V, const long* __restrict__ history,
-                                                             int hist_cap, const int* __restrict__ hist_len, SampleP sp, SliceWs ws) {
+                                                             int hist_cap, const int* __restrict__ hist_len, SampleP sp, SliceWs ws,
+                                                             const int* __restrict__ slot_of_row, int S) {
   __shared__ int hist_bins[SMP_BINS];
   __shared__ float lv[SMP_LCAP];
   __shared__ __attribute__((aligned(16))) int li[SMP_LCAP];
@@ -509,9 +573,12 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
   __shared__ float s_max, s_min;
   __shared__ int s_bi, list_n, thr_bin;
   const int b = blockIdx.x / SMP_G, g = blockIdx.x % SMP_G, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // (slot_of_row: logits row b belongs to slot sb of the state arrays; a row without a slot is skipped, nothing of it is written)
+  const int sb = slot_of_row ? slot_of_row[b] : b;
+  if (sb < 0 || sb >= S) return;  // (uniform)
   float* x = logits + (long)b * V;
-  const long* hist = history + (long)b * hist_cap;
-  const int hl = min(hist_len[b], hist_cap);
+  const long* hist = history + (long)sb * hist_cap;
+  const int hl = min(hist_len[sb], hist_cap);
   const int V4 = V >> 2, chunk4 = (V4 + SMP_G - 1) / SMP_G;
   const int lo4 = g * chunk4, hi4 = min(lo4 + chunk4, V4);
   const long lo = 4L * lo4, hi = 4L * hi4;
@@ -687,14 +754,19 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
 // SLOTS (tcavt_sample_logits_slots): the bookkeeping is per slot -- step_p, max_new and out_row are arrays [B]; slot b chooses token
 // step_p[b] of output row out_row[b] (which is also its Philox row), ends on EOS or when its budget max_new[b] is used up, and a
 // finished slot is inert: cur_tok[b] = pad and nothing else of its state is written.  The selection itself is the same code.
-template <bool SLOTS>
+// ROWS (tcavt_sample_logits_rows): SLOTS, with the logits row and the workspace indexed by the workgroup b and the state by the slot
+// sb = slot_of_row[b] of n_state slots; a row without a slot leaves before it has written anything.
+constexpr int SMP_BATCH = 0, SMP_SLOTS = 1, SMP_ROWS = 2;
+template <int MODE>
 __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logits, int V, long* __restrict__ history,
                                                        int hist_cap, int* __restrict__ hist_len, SampleP sp,
                                                        int* __restrict__ step_p, long* __restrict__ cur_tok,
                                                        int* __restrict__ pos, int* __restrict__ finished,
                                                        long* __restrict__ out_tokens, int out_cap, int advance_pos, SliceWs ws,
                                                        int n_samples, const int* __restrict__ max_new,
-                                                       const long* __restrict__ out_row) {
+                                                       const long* __restrict__ out_row, const int* __restrict__ slot_of_row,
+                                                       int n_state) {
+  constexpr bool SLOTS = MODE != SMP_BATCH;
   __shared__ float cv[SMP_CAP];
   __shared__ int ci[SMP_CAP];
   __shared__ float rv[SMP_T / 64];
@@ -707,10 +779,15 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
   __shared__ __attribute__((aligned(16))) int list_i[SMP_LIST];
   __shared__ int list_n, thr_bin, keep_n;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int sb = b;  // the row's entry of the state arrays
+  if constexpr (MODE == SMP_ROWS) {
+    sb = slot_of_row[b];
+    if (sb < 0 || sb >= n_state) return;  // (uniform)
+  }
   float* x = logits + (long)b * V;
-  long* hist = history + (long)b * hist_cap;
-  const int hl = min(hist_len[b], hist_cap);
-  const int step = SLOTS ? step_p[b] : *step_p;
+  long* hist = history + (long)sb * hist_cap;
+  const int hl = min(hist_len[sb], hist_cap);
+  const int step = SLOTS ? step_p[sb] : *step_p;
   const bool pre = ws.cand_v != nullptr;
   __shared__ int s_ovf;
   if (pre) {
@@ -979,7 +1056,7 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
       float kt = 0.f;
       for (int j = 0; j < keep; ++j) kt += __expf(cv[j] - m);
       unsigned int r[4];
-      philox4x32_10((unsigned int)step, SLOTS ? (unsigned int)out_row[b] : (unsigned int)b, 0x5A3Bu, 0u, sp.seed_lo, sp.seed_hi, r);
+      philox4x32_10((unsigned int)step, SLOTS ? (unsigned int)out_row[sb] : (unsigned int)b, 0x5A3Bu, 0u, sp.seed_lo, sp.seed_hi, r);
       const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f) * kt;
       float acc = 0.f;
       int pick = keep - 1;
@@ -994,18 +1071,18 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
   }
   if constexpr (SLOTS) {
     if (tid == 0) {
-      if (finished[b] != 0) {  // inert: the decode step keeps running this slot on the pad token at its frozen position
-        cur_tok[b] = sp.pad;
+      if (finished[sb] != 0) {  // inert: the decode step keeps running this slot on the pad token at its frozen position
+        cur_tok[sb] = sp.pad;
       } else {
-        if (step < out_cap) out_tokens[out_row[b] * out_cap + step] = tok;
-        cur_tok[b] = tok;
+        if (step < out_cap) out_tokens[out_row[sb] * out_cap + step] = tok;
+        cur_tok[sb] = tok;
         if (hl < hist_cap) {
           hist[hl] = tok;
-          hist_len[b] = hl + 1;
+          hist_len[sb] = hl + 1;
         }
-        if (advance_pos) pos[b] += 1;
-        if ((sp.eos >= 0 && tok == sp.eos) || step + 1 == max_new[b]) finished[b] = 1;
-        step_p[b] = step + 1;  // (the slot's own word: no ticket)
+        if (advance_pos) pos[sb] += 1;
+        if ((sp.eos >= 0 && tok == sp.eos) || step + 1 == max_new[sb]) finished[sb] = 1;
+        step_p[sb] = step + 1;  // (the slot's own word: no ticket)
       }
     }
     return;
@@ -1051,9 +1128,10 @@ extern "C" int64_t tcavt_sample_workspace_bytes(int B) {
   return 64 + (((int64_t)B * 4 + 63) & ~(int64_t)63) + (int64_t)B * SMP_G * 8 + (int64_t)B * SMP_G * SMP_LCAP * 8;
 }
 
-// tcavt_sample_logits (max_new == out_row == NULL, one step word) and tcavt_sample_logits_slots (arrays [B]) share the launches
-static int sample_logits_impl(const char* who, float* logits, int B, int V, int64_t* history, int hist_cap, int32_t* hist_len,
-                              const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row, int64_t* cur_tok,
+// tcavt_sample_logits (max_new == out_row == NULL, one step word), tcavt_sample_logits_slots (arrays [B]) and tcavt_sample_logits_rows
+// (slot_of_row: B logits rows on the state of n_state slots) share the launches
+static int sample_logits_impl(const char* who, float* logits, int B, int V, const int32_t* slot_of_row, int n_state, int64_t* history,
+                              int hist_cap, int32_t* hist_len, const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row, int64_t* cur_tok,
                               int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
                               int64_t workspace_bytes, tcavt_stream_t stream) {
   const bool slots = max_new || out_row;
@@ -1081,11 +1159,12 @@ static int sample_logits_impl(const char* who, float* logits, int B, int V, int6
     ws.cand_v = reinterpret_cast<float*>(w + off); off += (size_t)B * SMP_G * SMP_LCAP * 4;
     ws.cand_i = reinterpret_cast<int*>(w + off);
     hipLaunchKernelGGL(sample_slice_kernel, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V, reinterpret_cast<const long*>(history), hist_cap,
-                       hist_len, p, ws);
+                       hist_len, p, ws, slot_of_row, n_state);
   }
-  hipLaunchKernelGGL(slots ? sample_kernel<true> : sample_kernel<false>, dim3(B), dim3(SMP_T), 0, st, logits, V,
-                     reinterpret_cast<long*>(history), hist_cap, hist_len, p, step, reinterpret_cast<long*>(cur_tok), pos, finished,
-                     reinterpret_cast<long*>(out_tokens), out_cap, advance_pos, ws, B, max_new, reinterpret_cast<const long*>(out_row));
+  hipLaunchKernelGGL(slot_of_row ? sample_kernel<SMP_ROWS> : slots ? sample_kernel<SMP_SLOTS> : sample_kernel<SMP_BATCH>, dim3(B), dim3(SMP_T),
+                     0, st, logits, V, reinterpret_cast<long*>(history), hist_cap, hist_len, p, step, reinterpret_cast<long*>(cur_tok), pos,
+                     finished, reinterpret_cast<long*>(out_tokens), out_cap, advance_pos, ws, B, max_new,
+                     reinterpret_cast<const long*>(out_row), slot_of_row, n_state);
   if (!ws.cand_v && !slots) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
   TCAVT_CHECK_LAUNCH(who);
   return TCAVT_OK;
@@ -1098,7 +1177,7 @@ extern "C" int tcavt_sample_logits(float* logits, int B, int V, int64_t* history
   TCAVT_CHECK_ARG(logits && history && hist_len && sp && step && cur_tok && pos && finished && out_tokens && B > 0 && V > 0 &&
                       hist_cap > 0 && out_cap > 0,
                   "sample_logits: bad args");
-  return sample_logits_impl("sample_logits", logits, B, V, history, hist_cap, hist_len, sp, step, nullptr, nullptr, cur_tok, pos, finished,
+  return sample_logits_impl("sample_logits", logits, B, V, nullptr, B, history, hist_cap, hist_len, sp, step, nullptr, nullptr, cur_tok, pos, finished,
                             out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
 }
 
@@ -1114,8 +1193,25 @@ extern "C" int tcavt_sample_logits_slots(float* logits, int S, int V, int64_t* h
   TCAVT_CHECK_ARG(V > 0, "sample_logits_slots: V = %d must be > 0", V);
   TCAVT_CHECK_ARG(hist_cap > 0, "sample_logits_slots: hist_cap = %d must be > 0", hist_cap);
   TCAVT_CHECK_ARG(out_cap > 0, "sample_logits_slots: out_cap = %d must be > 0", out_cap);
-  return sample_logits_impl("sample_logits_slots", logits, S, V, history, hist_cap, hist_len, sp, step, max_new, out_row, cur_tok, pos,
+  return sample_logits_impl("sample_logits_slots", logits, S, V, nullptr, S, history, hist_cap, hist_len, sp, step, max_new, out_row, cur_tok, pos,
                             finished, out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tcavt_sample_logits_rows(float* logits, int G, int V, const int32_t* slot_of_row, int S, int64_t* history, int hist_cap,
+                                        int32_t* hist_len, const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new,
+                                        const int64_t* out_row, int64_t* cur_tok, int32_t* pos, int32_t* finished, int64_t* out_tokens,
+                                        int out_cap, int advance_pos, void* workspace, int64_t workspace_bytes, tcavt_stream_t stream) {
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {logits, "logits"}, {slot_of_row, "slot_of_row"}, {history, "history"}, {hist_len, "hist_len"}, {sp, "params"}, {step, "step"},
+      {max_new, "max_new"}, {out_row, "out_row"}, {cur_tok, "cur_tok"}, {pos, "pos"}, {finished, "finished"}, {out_tokens, "out_tokens"}};
+  for (const auto& a : ptrs) TCAVT_CHECK_ARG(a.p, "sample_logits_rows: %s is a null pointer", a.name);
+  TCAVT_CHECK_ARG(G > 0, "sample_logits_rows: G = %d must be > 0", G);
+  TCAVT_CHECK_ARG(S > 0, "sample_logits_rows: S = %d must be > 0", S);
+  TCAVT_CHECK_ARG(V > 0, "sample_logits_rows: V = %d must be > 0", V);
+  TCAVT_CHECK_ARG(hist_cap > 0, "sample_logits_rows: hist_cap = %d must be > 0", hist_cap);
+  TCAVT_CHECK_ARG(out_cap > 0, "sample_logits_rows: out_cap = %d must be > 0", out_cap);
+  return sample_logits_impl("sample_logits_rows", logits, G, V, slot_of_row, S, history, hist_cap, hist_len, sp, step, max_new, out_row,
+                            cur_tok, pos, finished, out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H,
@@ -1255,6 +1351,69 @@ extern "C" int tcavt_slot_admit(const tcavt_slot_admit_args* a, tcavt_stream_t s
   p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image; p.max_new_value = a->max_new_value;
   hipLaunchKernelGGL(slot_admit_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   TCAVT_CHECK_LAUNCH("slot_admit");
+  return TCAVT_OK;
+}
+
+extern "C" int tcavt_slot_admit_group(const tcavt_slot_admit_group_args* a, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "slot_admit_group: args is a null pointer");
+  const bool f16 = a->src_k || a->src_v || a->dst_k || a->dst_v;
+  const bool kv8 = a->src_k_codes || a->src_k_scales || a->src_v_codes || a->src_v_scales || a->dst_k_codes || a->dst_k_scales ||
+                   a->dst_v_codes || a->dst_v_scales;
+  TCAVT_CHECK_ARG(!(f16 && kv8), "slot_admit_group: the 16-bit caches (src_k .. dst_v) and the kv8 planes exclude each other");
+  TCAVT_CHECK_ARG(f16 || kv8, "slot_admit_group: null pointer (src_k / src_v / dst_k / dst_v, or the eight kv8 planes)");
+  TCAVT_CHECK_ARG(!f16 || (a->src_k && a->src_v && a->dst_k && a->dst_v),
+                  "slot_admit_group: null pointer: src_k, src_v, dst_k and dst_v come together");
+  TCAVT_CHECK_ARG(!kv8 || (a->src_k_codes && a->src_k_scales && a->src_v_codes && a->src_v_scales && a->dst_k_codes && a->dst_k_scales &&
+                           a->dst_v_codes && a->dst_v_scales),
+                  "slot_admit_group: null pointer: the eight kv8 planes come together");
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {a->slot, "slot"}, {a->kv_len, "kv_len"}, {a->max_new_value, "max_new_value"}, {a->out_row_value, "out_row_value"},
+      {a->prompt_ids, "prompt_ids"}, {a->bad_slot_flag, "bad_slot_flag"}, {a->history, "history"}, {a->hist_len, "hist_len"},
+      {a->step, "step"}, {a->max_new, "max_new"}, {a->out_row, "out_row"}, {a->pos, "pos"}, {a->finished, "finished"}, {a->cur_tok, "cur_tok"}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p, "slot_admit_group: %s is a null pointer", q.name);
+  TCAVT_CHECK_ARG(is16(a->dtype16), "slot_admit_group: dtype16 must be TCAVT_F16 or TCAVT_BF16");
+  TCAVT_CHECK_ARG(a->G >= 1, "slot_admit_group: G = %d must be >= 1", a->G);
+  TCAVT_CHECK_ARG(a->G <= 65535, "slot_admit_group: G = %d must be <= 65535", a->G);
+  TCAVT_CHECK_ARG(a->n_layers > 0 && a->S > 0 && a->nkv > 0 && a->src_lmax > 0 && a->kv_lmax > 0,
+                  "slot_admit_group: bad shape (n_layers, S, nkv, src_lmax, kv_lmax > 0)");
+  TCAVT_CHECK_ARG(a->rows >= 1 && a->rows <= std::min(a->src_lmax, a->kv_lmax),
+                  "slot_admit_group: rows = %d must be in [1, min(src_lmax = %d, kv_lmax = %d)]", a->rows, a->src_lmax, a->kv_lmax);
+  TCAVT_CHECK_ARG(a->hist_cap > 0 && a->n_ids >= 0 && a->n_ids <= a->hist_cap, "slot_admit_group: n_ids = %d must be in [0, hist_cap = %d]",
+                  a->n_ids, a->hist_cap);
+  TCAVT_CHECK_ARG(a->n_image >= 0, "slot_admit_group: n_image = %d must be >= 0", a->n_image);
+  AdmitGroupP p = {};
+  if (kv8) {
+    TCAVT_CHECK_ARG(aligned16(a->src_k_codes) && aligned16(a->src_v_codes) && aligned16(a->dst_k_codes) && aligned16(a->dst_v_codes),
+                    "slot_admit_group: the code planes must be 16-byte aligned");
+    TCAVT_CHECK_ARG(((reinterpret_cast<uintptr_t>(a->src_k_scales) | reinterpret_cast<uintptr_t>(a->src_v_scales) |
+                      reinterpret_cast<uintptr_t>(a->dst_k_scales) | reinterpret_cast<uintptr_t>(a->dst_v_scales)) & 1) == 0,
+                    "slot_admit_group: the scale planes must be 2-byte aligned");
+    const void* src[4] = {a->src_k_codes, a->src_v_codes, a->src_k_scales, a->src_v_scales};
+    void* dst[4] = {a->dst_k_codes, a->dst_v_codes, a->dst_k_scales, a->dst_v_scales};
+    for (int i = 0; i < 4; ++i) { p.src[i] = static_cast<const unsigned char*>(src[i]); p.dst[i] = static_cast<unsigned char*>(dst[i]); }
+    p.inner = a->nkv; p.row_bytes = 64;
+  } else {
+    TCAVT_CHECK_ARG(aligned16(a->src_k) && aligned16(a->src_v) && aligned16(a->dst_k) && aligned16(a->dst_v),
+                    "slot_admit_group: the caches must be 16-byte aligned");
+    p.src[0] = static_cast<const unsigned char*>(a->src_k); p.src[1] = static_cast<const unsigned char*>(a->src_v);
+    p.dst[0] = static_cast<unsigned char*>(a->dst_k); p.dst[1] = static_cast<unsigned char*>(a->dst_v);
+    p.inner = 1; p.row_bytes = a->nkv * 128;
+  }
+  p.segs = a->n_layers * p.inner;
+  p.S = a->S; p.G = a->G; p.rows = a->rows; p.src_lmax = a->src_lmax; p.kv_lmax = a->kv_lmax;
+  p.pieces = (long)a->rows * (p.row_bytes / 16);
+  p.n_wide = 2L * p.segs * p.pieces;
+  p.n_copy = p.n_wide + (kv8 ? 2L * p.segs * a->rows : 0L);
+  const long blocks = (p.n_copy + 255) / 256 + 1;
+  TCAVT_CHECK_ARG(blocks <= 0x7fffffffL, "slot_admit_group: too many rows");
+  p.slot = a->slot; p.kv_len = a->kv_len; p.max_new_value = a->max_new_value;
+  p.out_row_value = reinterpret_cast<const long*>(a->out_row_value); p.prompt_ids = reinterpret_cast<const long*>(a->prompt_ids);
+  p.bad_slot_flag = a->bad_slot_flag; p.history = reinterpret_cast<long*>(a->history);
+  p.hist_len = a->hist_len; p.step = a->step; p.max_new = a->max_new; p.pos = a->pos; p.finished = a->finished;
+  p.out_row = reinterpret_cast<long*>(a->out_row);
+  p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image;
+  hipLaunchKernelGGL(slot_admit_group_kernel, dim3((unsigned)blocks, (unsigned)a->G), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  TCAVT_CHECK_LAUNCH("slot_admit_group");
   return TCAVT_OK;
 }
 

@@ -1260,6 +1260,9 @@ class LlamaMultiModal(nn.Module, _Prepared):
         if getattr(self, "_lm_flag", None) is not None and self._lm_flag.item():
             self._lm_flag.zero_()
             raise ValueError("labels contain ids outside [0, vocab) other than -100, or a label at or beyond a sample's valid length")
+        if getattr(self, "_pool_flag", None) is not None and self._pool_flag.item():
+            self._pool_flag.zero_()
+            raise ValueError("generate_pool: a grouped admission named a slot outside the pool (tcavt_slot_admit_group)")
         if getattr(self, "_last_flags", None) is None:
             return
         f = self._last_flags.tolist()
@@ -1470,7 +1473,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
 
     def generate_pool(self, vision_embs, input_ids, attention_mask, max_new_tokens=128, slots=8, poll_every=1, do_sample=True,
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
-                      pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16"):
+                      pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1):
         """Text generation over a LIST of R requests on a fixed pool of ``slots`` decode slots ("slot
         pool"): request r is served exactly once, first in first out, and the moment a request ends (EOS, or its budget) the
         next one of the queue is prefilled into its slot -- no decode row computes pad tokens for longer than one poll interval.
@@ -1483,7 +1486,19 @@ class LlamaMultiModal(nn.Module, _Prepared):
         then the refills (poll_every = 1 measured best of 1 / 8 / 32, profiles/generate_pool.txt); the very first step runs eagerly and unpolled (the kernels' warm-up, then the capture).  A finished or idle slot is inert: it re-runs the step on the pad token at a frozen position.
         Returns int64 [R, max budget] (pad_token_id after each request's end), or strings with a tokenizer; check_flags()
         works afterwards as after generate_batch.  ``self.pool_stats`` of the last call: "steps" (decode steps run), "admitted" and
-        "retired" [(request, slot, steps run by then)] -- retirement is seen at a poll, up to poll_every steps after the end."""
+        "retired" [(request, slot, steps run by then)] -- retirement is seen at a poll, up to poll_every steps after the end.
+        ``admit_group`` = G (1 <= G <= slots; anything else raises ValueError): G = 1, the default, is the path above.  G >= 2:
+        requests are admitted in groups of up to G (pool.SlotScheduler.admission_groups: a group goes when min(G, waiting requests)
+        slots are free) and EVERY admission is one decoder pass at exactly B = G rows -- Q-Former, embedding, stack,
+        tcavt_slot_admit_group, lm_head, tcavt_sample_logits_rows -- a short group being filled with pad rows (the group's first
+        request again, admitted nowhere).  M = G * L is then constant, so every kernel form is, and with ``use_graph`` the pass is
+        captured after its first, eager run and replayed for every later group (only the staging buffers pool.pg.* change).
+        Contract: for a FIXED G a request's tokens do not depend on the schedule, the slot, its row in the group, its partners or
+        the pad rows; they may differ from its tokens at another G, admit_group = 1 included, because the kernel forms differ with
+        M.  Measured on 256 requests (profiles/generate_pool_groups.txt): at 32 slots G = 2 / 4 / 8 serve the list in 1.22 / 1.02 /
+        0.99 s against 1.57 s at G = 1 and 1.23 s for generate_batch; at 8 slots in 2.75 / 2.83 / 3.43 s against 2.95 s (G = 8 loses).
+        Recommended: admit_group=4 (it wins at both sizes); G = 2 for small pools, G = 8 from 32 slots on.  The default stays 1.
+        ``self.pool_stats["groups"]``: [(requests, slots, steps run by then)] per group pass, in row order (empty at G = 1)."""
         from . import capi
         from .pool import SlotScheduler
 
@@ -1497,6 +1512,9 @@ class LlamaMultiModal(nn.Module, _Prepared):
             raise ValueError(f"generate_pool: slots must be >= 1, got {slots}")
         if poll_every < 1:
             raise ValueError(f"generate_pool: poll_every must be >= 1, got {poll_every}")
+        G = int(admit_group)
+        if not 1 <= G <= S:
+            raise ValueError(f"generate_pool: admit_group must be in [1, slots = {S}], got {admit_group}")
         if input_ids.dim() != 2 or attention_mask.shape != input_ids.shape or vision_embs.shape[0] != input_ids.shape[0]:
             raise ValueError("generate_pool: vision_embs [R, ...], input_ids [R, Lt] and attention_mask [R, Lt] must agree")
         R, Lt = input_ids.shape
@@ -1519,7 +1537,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
         dev = vision_embs.device
         i32, i64 = torch.int32, torch.int64
         out = torch.full((R, Nmax), int(pad_token_id), dtype=i64, device=dev)
-        self.pool_stats = dict(steps=0, admitted=[], retired=[])
+        self.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
+        self._pool_flag = None  # (the grouped admission's bad-slot flag: check_flags)
         if R == 0:
             return [] if self.tokenizer is not None else out
         input_ids = input_ids.to(dev).contiguous()
@@ -1595,9 +1614,75 @@ class LlamaMultiModal(nn.Module, _Prepared):
                     ops.sample_logits_slots(logits1, history[s:s + 1], hist_len[s:], sp, step[s:], max_new[s:], out_row[s:], cur[s:],
                                             pos[s:], finished[s:], out, advance_pos=False, workspace=sws1)
 
-                sched, graph, stats = SlotScheduler(R, S), None, self.pool_stats
+                if G > 1:
+                    # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
+                    # with pad rows (its first request again, slot -1), so M = G * L and with it every kernel form is constant
+                    pg_vis = ws.get("pool.pg.vis", (G,) + tuple(vision_embs.shape[1:]), vision_embs.dtype, dev)
+                    pg_ids = ws.get("pool.pg.ids", (G, Lt), i64, dev)
+                    pg_mask = ws.get("pool.pg.mask", (G, Lt), i64, dev)
+                    pg_slot = ws.get("pool.pg.slot", (G,), i32, dev)
+                    pg_budget = ws.get("pool.pg.budget", (G,), i32, dev)
+                    pg_outrow = ws.get("pool.pg.outrow", (G,), i64, dev)
+                    if kv_cache == "fp8":
+                        pg_cache = tuple(ws.get(f"pool.pg.kv8.{nm}", (ll.layers, G, nkv, L, per), torch.uint8, dev) for nm, per in planes)
+                    else:
+                        pg_cache = tuple(ws.get(f"pool.pg.{nm}", (ll.layers, G, L, nkvw), st, dev) for nm in ("kc", "vc"))
+                    pg_logits = ws.get("pool.pg.logits", (G, ll.vocab), torch.float32, dev)
+                    pg_kvlen = ws.get("pool.pg.kvlen", (G,), i32, dev)
+                    pg_final16 = ws.get("pool.pg.final16", (G * L, H), st, dev)
+                    pg_x16 = ws.get("pool.pg.x16", (G, H), st, dev)
+                    pg_h = None if LW.stream16 else ws.get("pool.pg.h", (G * L, H), torch.float32, dev)
+                    pg_sws = None
+                    if sws is not None:
+                        pg_sws = ws.get("pool.pg.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(G)),), torch.uint8, dev, zero=True)
+                    bad_slot = self._pool_flag = ws.get("pool.pg.bad_slot", (1,), i32, dev, zero=True)
+                    vis_all = vision_embs.contiguous()
+                    budgets_dev = torch.tensor(budgets, dtype=i32, device=dev)
+
+                    def stage(group):
+                        # the group's rows of the request list -> the staging buffers (device-side gathers; two small uploads)
+                        reqs = [r for _, r in group] + [group[0][1]] * (G - len(group))
+                        idx = torch.tensor(reqs, dtype=i64, device=dev)
+                        torch.index_select(vis_all, 0, idx, out=pg_vis)
+                        torch.index_select(input_ids, 0, idx, out=pg_ids)
+                        torch.index_select(mask64, 0, idx, out=pg_mask)
+                        torch.index_select(budgets_dev, 0, idx, out=pg_budget)
+                        pg_outrow.copy_(idx)
+                        pg_slot.copy_(torch.tensor([s for s, _ in group] + [-1] * (G - len(group)), dtype=i32, device=dev))
+
+                    def group_pass():
+                        img = self._image_tokens(pg_vis)
+                        h16, part = LW.norm_inputs(G * L, dev)
+                        ops.embed_fuse(PL.table, pg_ids, img, P.vis, P.txt, pg_h, flags[0:1], h16=h16, part=part,
+                                       npart=LW.norm_npart(G * L), stream_scale=LW.stream_scale)
+                        ops.mask_to_kvlen(pg_mask, Nq, pg_kvlen, flags[1:2])
+                        LW.decoder_stack(pg_h, pg_kvlen, G, L, out_bf16=pg_final16, kv_cache=pg_cache + (L,), nonfinite_flag=flags[2:3])
+                        ops.slot_admit_group(pg_cache, cache, pg_slot, L, L, Lmax, ll.layers, S, nkv, pg_ids, pg_kvlen, Nq, pg_budget,
+                                             pg_outrow, bad_slot, history, hist_len, step, max_new, out_row, pos, finished, cur)
+                        ops.gather_last(pg_final16, pg_kvlen, pg_x16, G, L, H)
+                        ops.gemm_bf16(pg_x16, PL.table, out=pg_logits)  # lm_head, tied to embed_tokens
+                        ops.sample_logits_rows(pg_logits, pg_slot, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
+                                               advance_pos=False, workspace=pg_sws)
+
+                sched, graph, stats = SlotScheduler(R, S, G), None, self.pool_stats
+                pg_graph = None
                 while True:
-                    for s, r in sched.admissions():
+                    for group in (sched.admission_groups() if G > 1 else ()):
+                        stage(group)
+                        if not stats["groups"]:
+                            group_pass()  # the first pass runs eagerly: the warm-up of the workspaces and of every kernel form
+                        elif use_graph and dev.type == "cuda":
+                            if pg_graph is None:  # captured once (the capture launches nothing); only the staging buffers change
+                                torch.cuda.synchronize()
+                                pg_graph = torch.cuda.CUDAGraph()
+                                with torch.cuda.graph(pg_graph):
+                                    group_pass()
+                            pg_graph.replay()
+                        else:
+                            group_pass()
+                        stats["groups"].append((tuple(r for _, r in group), tuple(s for s, _ in group), stats["steps"]))
+                        stats["admitted"] += [(r, s, stats["steps"]) for s, r in group]
+                    for s, r in (sched.admissions() if G == 1 else ()):
                         admit(s, r)
                         stats["admitted"].append((r, s, stats["steps"]))
                     if not sched.busy():

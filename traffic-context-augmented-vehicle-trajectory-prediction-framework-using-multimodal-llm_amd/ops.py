@@ -1160,6 +1160,81 @@ def slot_admit(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt
     check(lib().tcavt_slot_admit(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit")
 
 
+def sample_logits_rows(logits, slot_of_row, history, hist_len, params, step, max_new, out_row, cur_tok, pos, finished, out_tokens,
+                       advance_pos, workspace=None):
+    """sample_logits_slots for the G logits rows of a grouped admission (tcavt_sample_logits_rows): logits [G, V]; slot_of_row int32
+    [G] on the device; row g chooses the token of slot slot_of_row[g] of the S-slot state (history [S, cap] and the [S] arrays);
+    a row whose entry is negative or >= S is skipped.  workspace: sample_workspace(G, device)."""
+    G, V = logits.shape
+    if workspace is not None:
+        _req(workspace, torch.uint8, "sample_logits_rows.workspace")
+    _req(logits, torch.float32, "sample_logits_rows.logits")
+    _req(slot_of_row, torch.int32, "sample_logits_rows.slot_of_row")
+    _need(slot_of_row, G, "sample_logits_rows.slot_of_row")
+    if history.dim() != 2 or out_tokens.dim() != 2:
+        raise capi.TcavtError("sample_logits_rows: history needs one row per slot, out_tokens one row per request")
+    S = history.shape[0]
+    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (step, torch.int32, S, "step"),
+                         (max_new, torch.int32, S, "max_new"), (out_row, torch.int64, S, "out_row"), (cur_tok, torch.int64, S, "cur_tok"),
+                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (out_tokens, torch.int64, 1, "out_tokens")):
+        _req(t, dt, "sample_logits_rows." + nm)
+        _need(t, n, "sample_logits_rows." + nm)
+    check(lib().tcavt_sample_logits_rows(ptr(logits), G, V, ptr(slot_of_row), S, ptr(history), history.shape[1], ptr(hist_len),
+                                         ctypes.byref(params), ptr(step), ptr(max_new), ptr(out_row), ptr(cur_tok), ptr(pos),
+                                         ptr(finished), ptr(out_tokens), out_tokens.shape[1], int(advance_pos), ptr(workspace),
+                                         workspace.numel() if workspace is not None else 0, stream_ptr()),
+          "tcavt_sample_logits_rows")
+
+
+def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value,
+                     out_row_value, bad_slot_flag, history, hist_len, step, max_new, out_row, pos, finished, cur_tok):
+    """The G samples of a grouped prefill move into their slots of an S-slot pool in one launch (tcavt_slot_admit_group).  src: the
+    G-sample cache, dst: the pool's cache, both (k, v) 16-bit [n_layers, G | S, lmax, nkv * 64] or both the four KV8 planes
+    [n_layers, G | S, nkv, lmax, 64 | 2].  Per row, on the device: slot int32 [G] (< 0: a pad row; >= S: nothing written,
+    bad_slot_flag int32 [1] set; the slots of a group are distinct), kv_len int32 [G], max_new_value int32 [G], out_row_value int64
+    [G], prompt_ids int64 [G, n_ids].  State of an admitted slot as slot_admit."""
+    a = capi.SlotAdmitGroupArgs()
+    if len(src) != len(dst) or len(src) not in (2, 4):
+        raise capi.TcavtError("slot_admit_group: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
+    _req(slot, torch.int32, "slot_admit_group.slot")
+    G = slot.numel()
+    if G < 1:
+        raise capi.TcavtError("slot_admit_group: slot needs one entry per row of the group")
+    if len(src) == 2:
+        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, G), (src[1], "src_v", src_lmax, G), (dst[0], "dst_k", kv_lmax, S), (dst[1], "dst_v", kv_lmax, S)):
+            _req16(t, "slot_admit_group." + nm, like=src[0])
+            _need(t, n_layers * n * lmax * nkv * 64, "slot_admit_group." + nm)
+            setattr(a, nm, t.data_ptr())
+        a.dtype16 = _DT[src[0].dtype]
+    else:
+        _kv8_planes(src, n_layers * G * nkv * src_lmax, "slot_admit_group.src")
+        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, "slot_admit_group.dst")
+        for side, planes in (("src", src), ("dst", dst)):
+            for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
+                setattr(a, f"{side}_{nm}", t.data_ptr())
+        a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+    if prompt_ids.dim() != 2 or prompt_ids.shape[0] != G:
+        raise capi.TcavtError("slot_admit_group: prompt_ids needs one row per row of the group")
+    for t, dt, n, nm in ((kv_len, torch.int32, G, "kv_len"), (max_new_value, torch.int32, G, "max_new_value"),
+                         (out_row_value, torch.int64, G, "out_row_value"), (prompt_ids, torch.int64, G, "prompt_ids"),
+                         (bad_slot_flag, torch.int32, 1, "bad_slot_flag")):
+        _req(t, dt, "slot_admit_group." + nm)
+        _need(t, n, "slot_admit_group." + nm)
+        setattr(a, nm, t.data_ptr())
+    a.slot = slot.data_ptr()
+    for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
+                      (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
+                      (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
+        _req(t, dt, "slot_admit_group." + nm)
+        _need(t, S, "slot_admit_group." + nm)
+        setattr(a, nm, t.data_ptr())
+    if history.dim() != 2 or history.shape[0] != S:
+        raise capi.TcavtError("slot_admit_group: history needs one row per slot")
+    a.n_layers, a.S, a.G, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, S, G, int(rows), src_lmax, kv_lmax, nkv
+    a.n_ids, a.hist_cap, a.n_image = prompt_ids.shape[1], history.shape[1], int(n_image)
+    check(lib().tcavt_slot_admit_group(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit_group")
+
+
 def gather_last(src16, kv_len, out16, B, L, H):
     _req16(src16, "gather_last.src16")
     _req16(out16, "gather_last.out16", like=src16)

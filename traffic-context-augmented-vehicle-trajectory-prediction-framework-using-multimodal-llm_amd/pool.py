@@ -5,12 +5,16 @@ device -- so that it can be driven by a scripted `finished` feed."""
 class SlotScheduler:
     """R requests are served exactly once, first in first out, by a fixed pool of decode slots.  The caller alternates
     ``admissions()`` (prefill each returned request into its slot), some decode steps, and ``retire(finished)`` with the
-    device's per-slot finished flags, until ``busy()`` is false."""
+    device's per-slot finished flags, until ``busy()`` is false.
+    ``group`` = G > 1: admissions come in groups of fixed width (``admission_groups()``): a group is released only when
+    min(G, waiting requests) slots are free, so that every admission pass of the caller has the same shape."""
 
-    def __init__(self, n_requests, slots):
+    def __init__(self, n_requests, slots, group=1):
         if slots < 1 or n_requests < 0:
             raise ValueError("SlotScheduler: slots >= 1 and n_requests >= 0 required")
-        self.n_requests, self.slots = int(n_requests), int(slots)
+        if not 1 <= int(group) <= int(slots):
+            raise ValueError(f"SlotScheduler: group = {group} must be in [1, slots = {slots}]")
+        self.n_requests, self.slots, self.group = int(n_requests), int(slots), int(group)
         self.slot_request = [None] * self.slots  # the live request of every slot
         self.next_request = 0
         self.retired = []  # (request, slot) in the order they ended
@@ -25,6 +29,25 @@ class SlotScheduler:
                 self.slot_request[s] = self.next_request
                 out.append((s, self.next_request))
                 self.next_request += 1
+        return out
+
+    def admission_groups(self):
+        """-> [[(slot, request), ...], ...]: groups of up to ``group`` pairs, first in first out, lowest free slots first; the
+        slots are taken.  A group is released only while free slots >= min(group, waiting requests): at the start
+        slots // group full groups go at once, a free slot then waits for group - 1 others (or for the queue to be shorter
+        than the group), and the tail goes as soon as there is room for all of it.  group = 1: admissions(), one pair per group."""
+        out = []
+        while self.next_request < self.n_requests:
+            need = min(self.group, self.n_requests - self.next_request)
+            free = [s for s in range(self.slots) if self.slot_request[s] is None]
+            if len(free) < need:
+                break
+            g = []
+            for s in free[:need]:
+                self.slot_request[s] = self.next_request
+                g.append((s, self.next_request))
+                self.next_request += 1
+            out.append(g)
         return out
 
     def retire(self, finished):
