@@ -1258,6 +1258,66 @@ int tcavt_sample_logits_rows(float* logits, int G, int V, const int32_t* slot_of
                              const int64_t* out_row, int64_t* cur_tok, int32_t* pos, int32_t* finished, int64_t* out_tokens,
                              int out_cap, int advance_pos, void* workspace, int64_t workspace_bytes, tcavt_stream_t stream);
 
+/* Ending rules of a request beyond the one eos_token_id, for tcavt_sample_tokens.  Every field is optional (NULL / 0); a struct
+ * with nothing set, like a NULL pointer to one, leaves the call launch for launch the corresponding existing entry.
+ * A LIVE row (finished == 0; in the rows form its map entry in range) choosing token number `step` of its request:
+ *   min_new_tokens  while step < min_new_tokens the scores of eos_token_id (when >= 0) and of every id of the stop set are -inf, in
+ *                   place, together with the other processors (HF MinNewTokensLengthLogitsProcessor with eos_token_id as a list).
+ *   stop_bitmap     device uint32 [(V + 31) / 32], bit (id & 31) of word (id >> 5): the row ends when the chosen token is in the
+ *                   set; the token is emitted and kept (as HF keeps an EOS of an eos_token_id list).  Bits at or beyond V are ignored.
+ *   stop_seqs       device int64 [n_seqs][8] with stop_seq_len device int32 [n_seqs], n_seqs <= 16: sequence q of length n =
+ *                   stop_seq_len[q] (ids stop_seqs[q][0 .. n)) ends the row when step + 1 >= n and the row's last n generated
+ *                   tokens -- the new one and history elements hist_len - 1 ... hist_len - n + 1 -- equal it.  A match never
+ *                   reaches into the prompt, and does not depend on min_new_tokens (HF: stopping criteria and logits processors
+ *                   are separate).  A length outside [1, 8] makes the sequence never match; no length value makes the kernel
+ *                   read out of bounds.
+ *   finish_reason   device int32, indexed like the rows of out_tokens (the sample b; out_row[s] in the slots and rows forms, so
+ *                   a request's record outlives its slot): written once, by the step that ends the request --
+ *                   1 EOS, 2 stop token, 3 stop sequence, 4 budget (step + 1 == max_new[s]; slots and rows forms only).  When
+ *                   several apply in one step the smallest number wins.  0 (still running) is the caller's initial value.
+ *   n_generated     device int32, indexed likewise: step + 1 at the end of the request, the ending token included.
+ * Inert, finished and skipped rows write neither array.  Everything else of a row's step -- out_tokens, cur_tok, history, pos,
+ * step, the Philox counter, the workspace words -- is what the existing entries do.
+ * Caller's contract: hist_cap holds the prompt and every generated token (a full history no longer grows, and a sequence is
+ * matched only against history elements that exist); the history of a row holds the request's own generated tokens at its end.
+ * Refused before any launch (tcavt_last_error names the argument): n_seqs outside [0, 16]; n_seqs > 0 with stop_seqs or
+ * stop_seq_len NULL; min_new_tokens < 0; min_new_tokens > 0 with neither eos_token_id >= 0 nor stop_bitmap (nothing to ban);
+ * a stop_bitmap that is not 4-byte aligned. */
+typedef struct tcavt_stop_rules {
+  const uint32_t* stop_bitmap;
+  const int64_t* stop_seqs;
+  const int32_t* stop_seq_len;
+  int32_t* finish_reason;
+  int32_t* n_generated;
+  int32_t n_seqs;
+  int32_t min_new_tokens;
+} tcavt_stop_rules;
+
+/* The three token-selection entries in one: the arguments of tcavt_sample_logits / _slots / _rows under their names there, and
+ * the form follows from the pointers exactly as there -- slot_of_row != NULL: tcavt_sample_logits_rows (rows = G logits rows on
+ * the state of n_state slots); else max_new / out_row != NULL (both): tcavt_sample_logits_slots (rows = S; n_state is ignored);
+ * else tcavt_sample_logits (rows = B; step is one word).  stop: optional ending rules (tcavt_stop_rules above). */
+typedef struct tcavt_sample_args {
+  float* logits;                     /* fp32 [rows][V], modified in place */
+  const int32_t* slot_of_row;        /* rows form: device int32 [rows]; else NULL */
+  int64_t* history;
+  int32_t* hist_len;
+  const tcavt_sample_params* params;
+  int32_t* step;
+  const int32_t* max_new;            /* slots / rows forms; else NULL */
+  const int64_t* out_row;            /* slots / rows forms; else NULL */
+  int64_t* cur_tok;
+  int32_t* pos;
+  int32_t* finished;
+  int64_t* out_tokens;
+  void* workspace;                   /* optional: tcavt_sample_workspace_bytes(rows) */
+  const tcavt_stop_rules* stop;      /* optional */
+  int64_t workspace_bytes;
+  int32_t rows, V, n_state, hist_cap, out_cap, advance_pos;
+} tcavt_sample_args;
+
+int tcavt_sample_tokens(const tcavt_sample_args* args, tcavt_stream_t stream);
+
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 

@@ -9,7 +9,10 @@ Reported per configuration: wall time, useful tokens / s = sum of the budgets / 
 the mean number of live slots per step (tokens chosen in decode steps / steps).
 --admit-group: the widths G of the grouped admission (generate_pool(admit_group=G)) to run as further arms, 1 = one request per
 prefill; per arm also the group passes and the pad rows they carried, and after each repetition, per G, equal_across_pool_sizes = the
-requests whose tokens are identical at every pool size (the contract of a fixed G: all of them)."""
+requests whose tokens are identical at every pool size (the contract of a fixed G: all of them).
+--stop-fraction F: the token-driven workload instead (stop_workload below) -- sampling, one budget --max-new for every request, a stop
+bitmap over a seeded random fraction F of the vocabulary; arms: generate_batch with the rules off, on and unpolled (the baseline), with
+poll_every from --batch-poll, and generate_pool per --slots x --admit-group at poll_every = --poll[0]."""
 import argparse
 import json
 import os
@@ -34,6 +37,10 @@ ap.add_argument("--admit-group", type=int, nargs="+", default=[1])
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--preset", default="llama32_1b")
 ap.add_argument("--out", default=None, help="also write the result lines to this file")
+ap.add_argument("--stop-fraction", type=float, default=None,
+                help="run the token-driven workload instead: sampling on, every request has the budget --max-new and ends on a stop "
+                     "bitmap that covers this (seeded random) fraction of the vocabulary")
+ap.add_argument("--batch-poll", type=int, nargs="+", default=[1, 8], help="token-driven workload: poll_every arms of generate_batch")
 args = ap.parse_args()
 capi.init(0)
 dev = torch.device("cuda:0")
@@ -74,6 +81,84 @@ def report(**rec):
     lines.append(json.dumps(rec))
     print(lines[-1], flush=True)
 
+
+def stop_workload():
+    """Ends that depend on the tokens: sampling with the reference's settings, one budget (--max-new) for every request, and a stop
+    set = a seeded random fraction of the vocabulary, so that random weights give roughly geometric lengths.  Arms, alternating inside
+    a repetition: generate_batch with the rules off (the launch sequence of a call without the feature), with the rules on and no
+    polling (the baseline: the same number of steps), with poll_every from --batch-poll, and generate_pool per --slots x
+    --admit-group at poll_every = --poll[0].  Useful tokens of an arm = the sum of its own n_generated (rules off: the rows cut on
+    the host by StopRules.first_end)."""
+    from tcavt_amd.stopping import StopRules
+
+    V, N = cfg.llama.vocab, args.max_new
+    ids = torch.nonzero(torch.rand(V, generator=torch.Generator().manual_seed(11)) < args.stop_fraction).flatten().tolist()
+    rules = StopRules(V, stop_token_ids=ids)
+    skw = dict(do_sample=True, seed=5)
+    rk = dict(stop_token_ids=ids, return_info=True)
+
+    def batches(B, n=R, poll=None, on=True):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_gen, steps = [], 0
+        for i in range(0, n, B):
+            sl = slice(i, i + B)
+            res = m.mllm.generate_batch(g["vision_emb"][sl], None, max_new_tokens=N, input_ids=g["input_ids"][sl],
+                                        attention_mask=g["attention_mask"][sl], poll_every=poll, **skw, **(rk if on else {}))
+            if on:
+                n_gen += res[1]["n_generated"].tolist()
+                steps += res[1]["steps"]
+            else:
+                n_gen.append(res.clone())
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        if not on:  # (outside the timed window)
+            n_gen = [rules.first_end(row, None, budget=N)[0] for o in n_gen for row in o.tolist()]
+            steps = -(-n // B) * (N - 1)
+        return t, n_gen, steps
+
+    def pool(S, G, n=R):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, st = m.mllm.generate_pool(g["vision_emb"][:n], g["input_ids"][:n], g["attention_mask"][:n], max_new_tokens=N, slots=S,
+                                     poll_every=args.poll[0], admit_group=G, **skw, **rk)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, st["n_generated"].tolist(), st["steps"]
+
+    for S in args.slots:  # warm-up of every shape and capture path the timed windows use
+        for poll in [None] + args.batch_poll:
+            batches(S, n=S, poll=poll)
+        batches(S, n=S, on=False)
+        for G in args.admit_group:
+            if G <= S:
+                pool(S, G, n=min(R, 2 * S))
+    for rep in range(args.reps):
+        for S in args.slots:
+            arms = [("generate_batch, rules off", lambda: batches(S, on=False), {}),
+                    ("generate_batch", lambda: batches(S), dict(poll_every=None))]
+            arms += [("generate_batch", lambda p=p: batches(S, poll=p), dict(poll_every=p)) for p in args.batch_poll]
+            arms += [("generate_pool", lambda G=G: pool(S, G), dict(poll_every=args.poll[0], admit_group=G)) for G in args.admit_group if G <= S]
+            for path, fn, extra in arms:
+                t, n_gen, steps = fn()
+                tot = int(sum(n_gen))
+                rec = dict(path=path, rows=S, rep=rep, wall_s=round(t, 3), useful_tokens=tot, mean_length=round(tot / R, 1),
+                           useful_tokens_per_s=round(tot / t, 1), decode_steps=steps, **extra)
+                if rep == 0 and path == "generate_batch" and extra.get("poll_every") is None:
+                    hist = np.bincount(np.minimum((np.asarray(n_gen) - 1) // 16, N // 16 - 1), minlength=N // 16).tolist()
+                    rec.update(length_histogram_16=hist, ended_by_stop_token=int(sum(x < N for x in n_gen)))
+                report(**rec)
+
+
+if args.stop_fraction is not None:
+    report(workload=f"{R} requests, prompt {cfg.q_num_query_tokens}+{args.text_len} tokens (ragged), budget {args.max_new} each; sampling "
+                    f"(temperature 0.9, top-k 40, top-p 0.9, penalty 1.2, no-repeat 3-grams, seed 5); stop set = a random "
+                    f"{args.stop_fraction} of the vocabulary (seed 11); fp16 weights and cache; hipGraph replay", preset=args.preset)
+    stop_workload()
+    m.mllm.check_flags()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 report(workload=f"{R} requests, prompt {cfg.q_num_query_tokens}+{args.text_len} tokens (ragged), budgets uniform {args.min_new}..{args.max_new} "
                 f"(seed 7): {useful} useful tokens, mean {useful / R:.1f}; greedy, fp16 weights and cache; hipGraph replay",

@@ -222,6 +222,23 @@ class SampleParams(ctypes.Structure):
                 ("pad_token_id", c_int64), ("seed", ctypes.c_uint64)]
 
 
+class StopRules(ctypes.Structure):
+    """Mirror of ``tcavt_stop_rules`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("stop_bitmap", "stop_seqs", "stop_seq_len", "finish_reason", "n_generated")] + [
+        ("n_seqs", ctypes.c_int32), ("min_new_tokens", ctypes.c_int32)]
+
+
+class SampleArgs(ctypes.Structure):
+    """Mirror of ``tcavt_sample_args`` (include/tcavt.h)."""
+
+    _fields_ = [("logits", c_void_p), ("slot_of_row", c_void_p), ("history", c_void_p), ("hist_len", c_void_p),
+                ("params", ctypes.POINTER(SampleParams)), ("step", c_void_p), ("max_new", c_void_p), ("out_row", c_void_p),
+                ("cur_tok", c_void_p), ("pos", c_void_p), ("finished", c_void_p), ("out_tokens", c_void_p), ("workspace", c_void_p),
+                ("stop", ctypes.POINTER(StopRules)), ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in (
+                    "rows", "V", "n_state", "hist_cap", "out_cap", "advance_pos")]
+
+
 class SlotAdmitArgs(ctypes.Structure):
     """Mirror of ``tcavt_slot_admit_args`` (include/tcavt.h)."""
 
@@ -378,6 +395,7 @@ _SIGNATURES = {
     "tcavt_sample_logits_rows": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(SampleParams),
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_int64, c_void_p],
+    "tcavt_sample_tokens": [ctypes.POINTER(SampleArgs), c_void_p],
     "tcavt_sample_workspace_bytes": [c_int],
     "tcavt_gather_last": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "tcavt_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,

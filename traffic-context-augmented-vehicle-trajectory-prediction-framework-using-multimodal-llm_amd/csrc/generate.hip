@@ -508,6 +508,20 @@ struct SampleP {
   unsigned int seed_lo, seed_hi;
 };
 
+// Ending rules of a request (tcavt_stop_rules; sample kernels with STOP): a stop set as a bitmap over the vocabulary, up to
+// SMP_SEQS stop sequences of 1 .. SMP_SEQ_LEN ids, the ban of every ending token while step < min_new
+// (MinNewTokensLengthLogitsProcessor with eos_token_id given as a list), and the record of how and when a request ended.
+struct StopP {
+  const unsigned int* bitmap;  // [(V + 31) / 32], bit id & 31 of word id >> 5; or NULL
+  const long* seqs;            // [n_seqs][SMP_SEQ_LEN]
+  const int* seq_len;          // [n_seqs]; a length outside [1, SMP_SEQ_LEN] never matches
+  int* finish_reason;          // indexed like out_tokens' rows; or NULL
+  int* n_generated;            // likewise
+  int n_seqs, min_new;
+};
+constexpr int SMP_SEQS = 16, SMP_SEQ_LEN = 8;
+constexpr int FIN_EOS = 1, FIN_STOP_TOKEN = 2, FIN_STOP_SEQ = 3, FIN_BUDGET = 4;
+
 constexpr int SMP_T = 1024;   // threads
 constexpr int SMP_CAP = 256;  // candidate list capacity (top_k + ties)
 constexpr int SMP_BINS = 2048;  // histogram of (max - score) * 64: covers 32 units below the maximum
@@ -562,9 +576,16 @@ struct SliceWs {  // views into the caller's workspace (tcavt_sample_logits: lay
   int* cand_i;    // [B][G][SMP_LCAP]
 };
 
+// STOP: the ban of the ending tokens before the minimum (StopP) -- the workgroup that owns a token bans it, as with the other
+// processors: the four ids of a lane's f32x4 lie in one word of the bitmap, so one load serves all four, and the banned scores go
+// back to the row (the one-stage fallback of stage 2 reads them there).  The branch is uniform per row and nothing is loaded for
+// the ban once the minimum is reached.  step_p: the row's step word (per_slot: step_p[sb], else *step_p).
+template <bool STOP = false>
 __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__ logits, int V, const long* __restrict__ history,
                                                              int hist_cap, const int* __restrict__ hist_len, SampleP sp, SliceWs ws,
-                                                             const int* __restrict__ slot_of_row, int S) {
+                                                             const int* __restrict__ slot_of_row, int S, StopP sr,
+                                                             const int* __restrict__ step_p, int per_slot,
+                                                             const int* __restrict__ finished) {
   __shared__ int hist_bins[SMP_BINS];
   __shared__ float lv[SMP_LCAP];
   __shared__ __attribute__((aligned(16))) int li[SMP_LCAP];
@@ -622,10 +643,27 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
   const float sc = sp.do_sample ? 1.f / sp.temperature : 1.f;
   f32x4 v4[SMP_E4];
   const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+  bool min_ban = false;  // (uniform)
+  if constexpr (STOP) {
+    if (sr.min_new > 0) min_ban = (per_slot ? step_p[sb] : *step_p) < sr.min_new && finished[sb] == 0;
+  }
 #pragma unroll
   for (int e = 0; e < SMP_E4; ++e) {
     const int i4 = lo4 + tid + e * SMP_T;
-    v4[e] = i4 < hi4 ? x4[i4] * sc : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};  // (a padding -inf never precedes a real entry: its index is larger)
+    f32x4 t = i4 < hi4 ? x4[i4] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};  // (a padding -inf never precedes a real entry: its index is larger)
+    if constexpr (STOP) {
+      if (min_ban && i4 < hi4) {
+        unsigned int m = sr.bitmap ? (sr.bitmap[i4 >> 3] >> ((i4 & 7) * 4)) & 15u : 0u;
+        if (sp.eos >= 0 && (sp.eos >> 2) == (long)i4) m |= 1u << (int)(sp.eos & 3);
+        if (m) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if ((m >> c) & 1u) t[c] = -INFINITY;
+          reinterpret_cast<f32x4*>(x)[i4] = t;
+        }
+      }
+    }
+    v4[e] = t * sc;
   }
   // best (value desc, index asc) and smallest finite score of the slice
   float bv = -INFINITY, lmin = INFINITY;
@@ -756,8 +794,13 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
 // finished slot is inert: cur_tok[b] = pad and nothing else of its state is written.  The selection itself is the same code.
 // ROWS (tcavt_sample_logits_rows): SLOTS, with the logits row and the workspace indexed by the workgroup b and the state by the slot
 // sb = slot_of_row[b] of n_state slots; a row without a slot leaves before it has written anything.
+// STOP (tcavt_sample_tokens with rules): a live row -- finished == 0 -- also bans the ending tokens while step < min_new (here only
+// in the one-stage form; the slices have done it otherwise), ends on a token of the stop set (the token is kept) or when its last n
+// generated tokens equal a stop sequence of length n (never reaching into the prompt: step + 1 >= n), and the thread that sets
+// `finished` records finish_reason (EOS 1 > stop token 2 > stop sequence 3 > budget 4) and n_generated = step + 1 at the row's
+// out_tokens index.  Everything else of a row's step is as without STOP.
 constexpr int SMP_BATCH = 0, SMP_SLOTS = 1, SMP_ROWS = 2;
-template <int MODE>
+template <int MODE, bool STOP = false>
 __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logits, int V, long* __restrict__ history,
                                                        int hist_cap, int* __restrict__ hist_len, SampleP sp,
                                                        int* __restrict__ step_p, long* __restrict__ cur_tok,
@@ -765,7 +808,7 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
                                                        long* __restrict__ out_tokens, int out_cap, int advance_pos, SliceWs ws,
                                                        int n_samples, const int* __restrict__ max_new,
                                                        const long* __restrict__ out_row, const int* __restrict__ slot_of_row,
-                                                       int n_state) {
+                                                       int n_state, StopP sr) {
   constexpr bool SLOTS = MODE != SMP_BATCH;
   __shared__ float cv[SMP_CAP];
   __shared__ int ci[SMP_CAP];
@@ -796,6 +839,17 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
     if (tid == 0 && s_ovf) ws.ovf[b] = 0;  // (re-armed for the next call)
   }
   const bool pre_ok = pre && s_ovf == 0;  // (uniform) the slices' candidates are complete
+  // ---- before the minimum: no ending token (-inf absorbs the penalty, so the order against the processors below does not matter)
+  if constexpr (STOP) {
+    if (!pre && sr.min_new > 0 && step < sr.min_new && finished[sb] == 0) {  // (uniform)
+      if (sr.bitmap) {
+        for (int i = tid; i < V; i += SMP_T)
+          if ((sr.bitmap[i >> 5] >> (i & 31)) & 1u) x[i] = -INFINITY;
+      }
+      if (tid == 0 && sp.eos >= 0 && sp.eos < V) x[sp.eos] = -INFINITY;
+      __syncthreads();
+    }
+  }
   // ---- repetition penalty: once per distinct token of the history (scatter semantics of the reference processor)
   if (!pre && sp.rep_penalty != 1.f) {
     // (the history is staged in LDS when it fits: thread i compares its token with all earlier ones)
@@ -1069,6 +1123,45 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
     __syncthreads();
     tok = besti;
   }
+  // ---- stop sequences: thread (q, j) compares element j from the end of sequence q with the j-th newest generated token (the new
+  // token, then history elements hl - 1 ...); one predicated load each, no data-dependent trip count; a sequence matches when its
+  // eight lanes agree (lanes past its length agree by definition)
+  bool seq_hit = false;
+  if constexpr (STOP) {
+    __shared__ int s_seq[2];
+    static_assert(SMP_SEQS * SMP_SEQ_LEN == 128 && SMP_SEQ_LEN == 8, "two waves, one sequence per 8 lanes");
+    if (sr.n_seqs > 0) {  // (uniform)
+      if (tid < SMP_SEQS * SMP_SEQ_LEN) {
+        const int q = tid >> 3, j = tid & 7;
+        bool ok = false;
+        if (q < sr.n_seqs) {
+          const int len = sr.seq_len[q];
+          const bool len_ok = len >= 1 && len <= SMP_SEQ_LEN && step + 1 >= len;
+          const int lc = len_ok ? len : 1;
+          const bool mine = j < lc;
+          const long want = sr.seqs[q * SMP_SEQ_LEN + (mine ? lc - 1 - j : 0)];
+          const bool there = j == 0 || hl - j >= 0;  // (only history elements that exist)
+          const long have = j == 0 ? tok : (there ? hist[hl - j] : -1L);
+          ok = len_ok && (!mine || (there && have == want));
+        }
+        unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+        m &= m >> 1; m &= m >> 2; m &= m >> 4;
+        if (lane == 0) s_seq[wv] = (m & 0x0101010101010101ull) != 0ull;
+      }
+      __syncthreads();
+      seq_hit = (s_seq[0] | s_seq[1]) != 0;
+    }
+  }
+  // how a live row ends on `tok` (0: it does not), budget aside
+  auto end_reason = [&]() -> int {
+    if (sp.eos >= 0 && tok == sp.eos) return FIN_EOS;
+    if (sr.bitmap && tok >= 0 && tok < V && ((sr.bitmap[tok >> 5] >> (tok & 31)) & 1u)) return FIN_STOP_TOKEN;
+    return seq_hit ? FIN_STOP_SEQ : 0;
+  };
+  auto record = [&](long row, int reason) {
+    if (sr.finish_reason) sr.finish_reason[row] = reason;
+    if (sr.n_generated) sr.n_generated[row] = step + 1;
+  };
   if constexpr (SLOTS) {
     if (tid == 0) {
       if (finished[sb] != 0) {  // inert: the decode step keeps running this slot on the pad token at its frozen position
@@ -1081,7 +1174,16 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
           hist_len[sb] = hl + 1;
         }
         if (advance_pos) pos[sb] += 1;
-        if ((sp.eos >= 0 && tok == sp.eos) || step + 1 == max_new[sb]) finished[sb] = 1;
+        if constexpr (STOP) {
+          int reason = end_reason();
+          if (!reason && step + 1 == max_new[sb]) reason = FIN_BUDGET;
+          if (reason) {
+            finished[sb] = 1;
+            record(out_row[sb], reason);
+          }
+        } else {
+          if ((sp.eos >= 0 && tok == sp.eos) || step + 1 == max_new[sb]) finished[sb] = 1;
+        }
         step_p[sb] = step + 1;  // (the slot's own word: no ticket)
       }
     }
@@ -1092,7 +1194,15 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
     const bool fin = finished[b] != 0;
     const long outt = fin ? sp.pad : tok;
     if (step < out_cap) out_tokens[(long)b * out_cap + step] = outt;
-    if (!fin && sp.eos >= 0 && tok == sp.eos) finished[b] = 1;
+    if constexpr (STOP) {
+      const int reason = fin ? 0 : end_reason();
+      if (reason) {
+        finished[b] = 1;
+        record(b, reason);
+      }
+    } else {
+      if (!fin && sp.eos >= 0 && tok == sp.eos) finished[b] = 1;
+    }
     cur_tok[b] = outt;
     if (hl < hist_cap) {
       hist[hl] = outt;
@@ -1133,8 +1243,26 @@ extern "C" int64_t tcavt_sample_workspace_bytes(int B) {
 static int sample_logits_impl(const char* who, float* logits, int B, int V, const int32_t* slot_of_row, int n_state, int64_t* history,
                               int hist_cap, int32_t* hist_len, const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row, int64_t* cur_tok,
                               int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
-                              int64_t workspace_bytes, tcavt_stream_t stream) {
+                              int64_t workspace_bytes, tcavt_stream_t stream, const tcavt_stop_rules* rules = nullptr) {
   const bool slots = max_new || out_row;
+  // ending rules: with none set (or rules == NULL) the launches below are the instantiations without STOP, argument for argument
+  StopP sr = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+  bool stop = false;
+  if (rules) {
+    TCAVT_CHECK_ARG(rules->n_seqs >= 0 && rules->n_seqs <= SMP_SEQS, "%s: stop rules: n_seqs = %d outside [0, %d]", who, rules->n_seqs, SMP_SEQS);
+    TCAVT_CHECK_ARG(rules->n_seqs == 0 || rules->stop_seqs, "%s: stop rules: stop_seqs is a null pointer with n_seqs = %d", who, rules->n_seqs);
+    TCAVT_CHECK_ARG(rules->n_seqs == 0 || rules->stop_seq_len, "%s: stop rules: stop_seq_len is a null pointer with n_seqs = %d", who, rules->n_seqs);
+    TCAVT_CHECK_ARG(rules->min_new_tokens >= 0, "%s: stop rules: min_new_tokens = %d must be >= 0", who, rules->min_new_tokens);
+    TCAVT_CHECK_ARG(rules->min_new_tokens == 0 || sp->eos_token_id >= 0 || rules->stop_bitmap,
+                    "%s: stop rules: min_new_tokens = %d with neither eos_token_id nor stop_bitmap (nothing to ban)", who, rules->min_new_tokens);
+    TCAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(rules->stop_bitmap) & 3) == 0, "%s: stop rules: stop_bitmap must be 4-byte aligned", who);
+    sr.bitmap = rules->stop_bitmap;
+    sr.seqs = rules->n_seqs > 0 ? reinterpret_cast<const long*>(rules->stop_seqs) : nullptr;
+    sr.seq_len = rules->n_seqs > 0 ? rules->stop_seq_len : nullptr;
+    sr.finish_reason = rules->finish_reason; sr.n_generated = rules->n_generated;
+    sr.n_seqs = rules->n_seqs; sr.min_new = rules->min_new_tokens;
+    stop = sr.bitmap || sr.n_seqs > 0 || sr.min_new > 0 || sr.finish_reason || sr.n_generated;
+  }
   TCAVT_CHECK_ARG(!sp->do_sample || (sp->temperature > 0.f && sp->top_k >= 1 && sp->top_k <= SMP_CAP && sp->top_p > 0.f && sp->top_p <= 1.f),
                   "%s: sampling needs temperature > 0, 1 <= top_k <= %d, 0 < top_p <= 1", who, SMP_CAP);
   TCAVT_CHECK_ARG(sp->repetition_penalty > 0.f && sp->no_repeat_ngram_size >= 0, "%s: bad repetition_penalty / no_repeat_ngram_size", who);
@@ -1158,13 +1286,15 @@ static int sample_logits_impl(const char* who, float* logits, int B, int V, cons
     ws.lb = reinterpret_cast<float*>(w + off); off += (size_t)B * SMP_G * 4;
     ws.cand_v = reinterpret_cast<float*>(w + off); off += (size_t)B * SMP_G * SMP_LCAP * 4;
     ws.cand_i = reinterpret_cast<int*>(w + off);
-    hipLaunchKernelGGL(sample_slice_kernel, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V, reinterpret_cast<const long*>(history), hist_cap,
-                       hist_len, p, ws, slot_of_row, n_state);
+    hipLaunchKernelGGL(stop ? sample_slice_kernel<true> : sample_slice_kernel<false>, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V,
+                       reinterpret_cast<const long*>(history), hist_cap, hist_len, p, ws, slot_of_row, n_state, sr, step, slots ? 1 : 0, finished);
   }
-  hipLaunchKernelGGL(slot_of_row ? sample_kernel<SMP_ROWS> : slots ? sample_kernel<SMP_SLOTS> : sample_kernel<SMP_BATCH>, dim3(B), dim3(SMP_T),
+  auto* kern = slot_of_row ? sample_kernel<SMP_ROWS> : slots ? sample_kernel<SMP_SLOTS> : sample_kernel<SMP_BATCH>;
+  if (stop) kern = slot_of_row ? sample_kernel<SMP_ROWS, true> : slots ? sample_kernel<SMP_SLOTS, true> : sample_kernel<SMP_BATCH, true>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(SMP_T),
                      0, st, logits, V, reinterpret_cast<long*>(history), hist_cap, hist_len, p, step, reinterpret_cast<long*>(cur_tok), pos,
                      finished, reinterpret_cast<long*>(out_tokens), out_cap, advance_pos, ws, B, max_new,
-                     reinterpret_cast<const long*>(out_row), slot_of_row, n_state);
+                     reinterpret_cast<const long*>(out_row), slot_of_row, n_state, sr);
   if (!ws.cand_v && !slots) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
   TCAVT_CHECK_LAUNCH(who);
   return TCAVT_OK;
@@ -1212,6 +1342,24 @@ extern "C" int tcavt_sample_logits_rows(float* logits, int G, int V, const int32
   TCAVT_CHECK_ARG(out_cap > 0, "sample_logits_rows: out_cap = %d must be > 0", out_cap);
   return sample_logits_impl("sample_logits_rows", logits, G, V, slot_of_row, S, history, hist_cap, hist_len, sp, step, max_new, out_row,
                             cur_tok, pos, finished, out_tokens, out_cap, advance_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tcavt_sample_tokens(const tcavt_sample_args* a, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "sample_tokens: args is a null pointer");
+  const bool rows = a->slot_of_row != nullptr, slots = rows || a->max_new || a->out_row;
+  const struct { const void* p; const char* name; bool need; } ptrs[] = {
+      {a->logits, "logits", true}, {a->history, "history", true}, {a->hist_len, "hist_len", true}, {a->params, "params", true},
+      {a->step, "step", true}, {a->max_new, "max_new", slots}, {a->out_row, "out_row", slots}, {a->cur_tok, "cur_tok", true},
+      {a->pos, "pos", true}, {a->finished, "finished", true}, {a->out_tokens, "out_tokens", true}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p || !q.need, "sample_tokens: %s is a null pointer", q.name);
+  TCAVT_CHECK_ARG(a->rows > 0, "sample_tokens: rows = %d must be > 0", a->rows);
+  TCAVT_CHECK_ARG(a->V > 0, "sample_tokens: V = %d must be > 0", a->V);
+  TCAVT_CHECK_ARG(!rows || a->n_state > 0, "sample_tokens: n_state = %d must be > 0 with slot_of_row", a->n_state);
+  TCAVT_CHECK_ARG(a->hist_cap > 0, "sample_tokens: hist_cap = %d must be > 0", a->hist_cap);
+  TCAVT_CHECK_ARG(a->out_cap > 0, "sample_tokens: out_cap = %d must be > 0", a->out_cap);
+  return sample_logits_impl("sample_tokens", a->logits, a->rows, a->V, a->slot_of_row, rows ? a->n_state : a->rows, a->history, a->hist_cap,
+                            a->hist_len, a->params, a->step, a->max_new, a->out_row, a->cur_tok, a->pos, a->finished, a->out_tokens,
+                            a->out_cap, a->advance_pos, a->workspace, a->workspace_bytes, stream, a->stop);
 }
 
 extern "C" int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H,

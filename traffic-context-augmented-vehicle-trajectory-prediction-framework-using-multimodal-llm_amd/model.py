@@ -1344,7 +1344,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
     def generate_batch(self, vision_embs_batch, context_str_list=None, max_new_tokens=50, input_ids=None,
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
-                       kv_cache="fp16"):
+                       kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
+                       poll_every=None):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1366,11 +1367,25 @@ class LlamaMultiModal(nn.Module, _Prepared):
         quantises, tcavt_kv_store8), so the first generated token does not depend on the cache type; every decode step uses its
         own key / value at 16-bit precision, writes them quantised and sees every earlier row as code * 2^k (tcavt_attn_decode8).
         Any other value raises ValueError.
-        Returns int64 [B, max_new_tokens] token ids (pad_token_id after EOS), or a list of strings with a tokenizer."""
+        Ending rules ("ending rules"; stopping.StopRules validates them and raises ValueError): a row also ends
+        on a token of ``stop_token_ids`` (kept, like EOS) or when its last generated tokens equal one of ``stop_sequences`` (<= 16
+        of 1 .. 8 ids; never matched across the end of the prompt); while fewer than ``min_new_tokens`` tokens are out, EOS and the
+        stop tokens are banned (it needs one of the two).  With none of them set the sampler launches are those of a call without.
+        ``poll_every`` = k >= 1: after every k replayed steps the finished flags are read back ([B] int32 to pinned memory, an event
+        wait) and the loop ends once every row has: same tokens, fewer steps.  None: no host read, all max_new_tokens - 1 steps.
+        ``return_info``: returns (out, info) -- info["finish_reason"] / info["n_generated"]: host int32 [B] (1 EOS, 2 stop token,
+        3 stop sequence, 4 ran out at max_new_tokens), info["steps"]: decode steps run.
+        Returns int64 [B, max_new_tokens] token ids (pad_token_id after a row's end), or a list of strings with a tokenizer."""
         from . import capi
+        from .stopping import BUDGET, StopRules
 
         if kv_cache not in ("fp16", "fp8"):  # (before anything touches a device)
             raise ValueError(f"generate_batch: kv_cache must be 'fp16' or 'fp8', got {kv_cache!r}")
+        rules = StopRules(self.llama_wrapper.shape.vocab, stop_token_ids, stop_sequences, min_new_tokens)
+        if rules.min_new_tokens > 0 and eos_token_id is None and not rules.stop_token_ids:
+            raise ValueError("generate_batch: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
+        if poll_every is not None and int(poll_every) < 1:
+            raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
         if input_ids is None:
             if self.tokenizer is None or context_str_list is None:
                 raise NotImplementedError(
@@ -1445,35 +1460,73 @@ class LlamaMultiModal(nn.Module, _Prepared):
                 sws = None
                 if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1":
                     sws = ws.get("gen.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(B)),), torch.uint8, dev, zero=True)
-                ops.sample_logits(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=False, workspace=sws)
+                # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
+                drules = None
+                if return_info or not rules.empty:
+                    drules = rules.to(dev).records(B, dev)
+
+                def select(advance_pos):
+                    if drules is None:
+                        ops.sample_logits(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=advance_pos, workspace=sws)
+                    else:
+                        ops.sample_tokens(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=advance_pos,
+                                          workspace=sws, stop=drules)
+
+                select(False)
+                steps_run = 0
                 if N > 1:
                     a = self._decode_args("gen", "generate_batch", B, Lmax, decode_weights, cache, cur, pos, logits, flags)
 
                     def one_step():
                         ops.llama_decode_step(a)
-                        ops.sample_logits(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=True, workspace=sws)
+                        select(True)
 
                     one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)
+                    steps_run = 1
                     if N > 2:
+                        graph = None
                         if use_graph and dev.type == "cuda":
                             torch.cuda.synchronize()
                             graph = torch.cuda.CUDAGraph()
                             with torch.cuda.graph(graph):  # capture launches nothing: the N - 2 replays are tokens 3 .. N
                                 one_step()
+                        if poll_every is None:
                             for _ in range(N - 2):
-                                graph.replay()
+                                graph.replay() if graph is not None else one_step()
+                            steps_run = N - 1
                         else:
-                            for _ in range(N - 2):
-                                one_step()
+                            # every poll_every steps: the finished flags to pinned host memory, an event wait, and out once every row
+                            # has ended (out was filled with pad and a finished row only ever writes pad: the result is the same)
+                            fin_host = torch.empty(B, dtype=i32).pin_memory() if dev.type == "cuda" else torch.empty(B, dtype=i32)
+                            polled = torch.cuda.Event() if dev.type == "cuda" else None
+                            while steps_run < N - 1:
+                                n_now = min(int(poll_every), N - 1 - steps_run)
+                                for _ in range(n_now):
+                                    graph.replay() if graph is not None else one_step()
+                                steps_run += n_now
+                                fin_host.copy_(finished, non_blocking=True)
+                                if polled is not None:
+                                    polled.record()
+                                    polled.synchronize()
+                                if bool((fin_host != 0).all()):
+                                    break
+                info = None
+                if return_info:
+                    reason, n_gen = drules.finish_reason.cpu(), drules.n_generated.cpu()
+                    ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
+                    reason[ran_out], n_gen[ran_out] = BUDGET, N
+                    info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
             finally:
                 LW.dctx, LW.save_for_backward = was_dctx, was_saving
         if self.tokenizer is not None:
-            return [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
-        return out
+            texts = [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
+            return (texts, info) if return_info else texts
+        return (out, info) if return_info else out
 
     def generate_pool(self, vision_embs, input_ids, attention_mask, max_new_tokens=128, slots=8, poll_every=1, do_sample=True,
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
-                      pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1):
+                      pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1,
+                      stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False):
         """Text generation over a LIST of R requests on a fixed pool of ``slots`` decode slots ("slot
         pool"): request r is served exactly once, first in first out, and the moment a request ends (EOS, or its budget) the
         next one of the queue is prefilled into its slot -- no decode row computes pad tokens for longer than one poll interval.
@@ -1498,15 +1551,24 @@ class LlamaMultiModal(nn.Module, _Prepared):
         M.  Measured on 256 requests (profiles/generate_pool_groups.txt): at 32 slots G = 2 / 4 / 8 serve the list in 1.22 / 1.02 /
         0.99 s against 1.57 s at G = 1 and 1.23 s for generate_batch; at 8 slots in 2.75 / 2.83 / 3.43 s against 2.95 s (G = 8 loses).
         Recommended: admit_group=4 (it wins at both sizes); G = 2 for small pools, G = 8 from 32 slots on.  The default stays 1.
-        ``self.pool_stats["groups"]``: [(requests, slots, steps run by then)] per group pass, in row order (empty at G = 1)."""
+        ``self.pool_stats["groups"]``: [(requests, slots, steps run by then)] per group pass, in row order (empty at G = 1).
+        ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``: the ending rules of generate_batch, applied by all three sampler
+        uses (the decode loop, the G = 1 admission, the grouped admission); a request may end on its first token, at admission.
+        With none set the sampler launches are those of a call without.  With rules or ``return_info`` the stats gain
+        "finish_reason" / "n_generated": host int32 [R] (1 EOS, 2 stop token, 3 stop sequence, 4 budget); ``return_info`` returns
+        (out, stats)."""
         from . import capi
         from .pool import SlotScheduler
+        from .stopping import StopRules
 
         # ---- every illegal value is refused before anything touches a device
         if kv_cache not in ("fp16", "fp8"):
             raise ValueError(f"generate_pool: kv_cache must be 'fp16' or 'fp8', got {kv_cache!r}")
         if decode_weights not in ("fp16", "fp8"):
             raise ValueError(f"generate_pool: decode_weights must be 'fp16' or 'fp8', got {decode_weights!r}")
+        rules = StopRules(self.llama_wrapper.shape.vocab, stop_token_ids, stop_sequences, min_new_tokens)
+        if rules.min_new_tokens > 0 and eos_token_id is None and not rules.stop_token_ids:
+            raise ValueError("generate_pool: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
         S, poll_every = int(slots), int(poll_every)
         if S < 1:
             raise ValueError(f"generate_pool: slots must be >= 1, got {slots}")
@@ -1540,7 +1602,10 @@ class LlamaMultiModal(nn.Module, _Prepared):
         self.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
         self._pool_flag = None  # (the grouped admission's bad-slot flag: check_flags)
         if R == 0:
-            return [] if self.tokenizer is not None else out
+            if return_info or not rules.empty:
+                self.pool_stats.update(finish_reason=torch.zeros(0, dtype=i32), n_generated=torch.zeros(0, dtype=i32))
+            res = [] if self.tokenizer is not None else out
+            return (res, self.pool_stats) if return_info else res
         input_ids = input_ids.to(dev).contiguous()
         mask64 = attention_mask.to(dev).to(i64).contiguous()
         P, PL = self._prepared(), LW._prepared()
@@ -1592,11 +1657,19 @@ class LlamaMultiModal(nn.Module, _Prepared):
                     sws = ws.get("pool.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(S)),), torch.uint8, dev, zero=True)
                     sws1 = ws.get("pool.pf.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(1)),), torch.uint8, dev, zero=True)
                 a = self._decode_args("pool", "generate_pool", S, Lmax, decode_weights, cache + (Lmax,), cur, pos, logits, flags)
+                # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
+                drules = None
+                if return_info or not rules.empty:
+                    drules = rules.to(dev).records(R, dev)
 
                 def one_step():
                     ops.llama_decode_step(a)
-                    ops.sample_logits_slots(logits, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
-                                            advance_pos=True, workspace=sws)
+                    if drules is None:
+                        ops.sample_logits_slots(logits, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
+                                                advance_pos=True, workspace=sws)
+                    else:
+                        ops.sample_tokens(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=True, workspace=sws,
+                                          max_new=max_new, out_row=out_row, stop=drules)
 
                 def admit(s, r):
                     # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
@@ -1611,8 +1684,13 @@ class LlamaMultiModal(nn.Module, _Prepared):
                                    history, hist_len, step, max_new, out_row, pos, finished, cur)
                     ops.gather_last(final16, kv_len, x16, 1, L, H)
                     ops.gemm_bf16(x16, PL.table, out=logits1)  # lm_head, tied to embed_tokens
-                    ops.sample_logits_slots(logits1, history[s:s + 1], hist_len[s:], sp, step[s:], max_new[s:], out_row[s:], cur[s:],
-                                            pos[s:], finished[s:], out, advance_pos=False, workspace=sws1)
+                    if drules is None:
+                        ops.sample_logits_slots(logits1, history[s:s + 1], hist_len[s:], sp, step[s:], max_new[s:], out_row[s:], cur[s:],
+                                                pos[s:], finished[s:], out, advance_pos=False, workspace=sws1)
+                    else:
+                        ops.sample_tokens(logits1, history[s:s + 1], hist_len[s:s + 1], sp, step[s:s + 1], cur[s:s + 1], pos[s:s + 1],
+                                          finished[s:s + 1], out, advance_pos=False, workspace=sws1, max_new=max_new[s:s + 1],
+                                          out_row=out_row[s:s + 1], stop=drules)
 
                 if G > 1:
                     # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
@@ -1661,8 +1739,12 @@ class LlamaMultiModal(nn.Module, _Prepared):
                                              pg_outrow, bad_slot, history, hist_len, step, max_new, out_row, pos, finished, cur)
                         ops.gather_last(pg_final16, pg_kvlen, pg_x16, G, L, H)
                         ops.gemm_bf16(pg_x16, PL.table, out=pg_logits)  # lm_head, tied to embed_tokens
-                        ops.sample_logits_rows(pg_logits, pg_slot, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
-                                               advance_pos=False, workspace=pg_sws)
+                        if drules is None:
+                            ops.sample_logits_rows(pg_logits, pg_slot, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
+                                                   advance_pos=False, workspace=pg_sws)
+                        else:
+                            ops.sample_tokens(pg_logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=False,
+                                              workspace=pg_sws, max_new=max_new, out_row=out_row, slot_of_row=pg_slot, stop=drules)
 
                 sched, graph, stats = SlotScheduler(R, S, G), None, self.pool_stats
                 pg_graph = None
@@ -1707,11 +1789,14 @@ class LlamaMultiModal(nn.Module, _Prepared):
                     n_ret = len(sched.retired)
                     sched.retire(fin_host.tolist())
                     stats["retired"] += [(r, s, stats["steps"]) for r, s in sched.retired[n_ret:]]
+                if drules is not None:
+                    stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
             finally:
                 LW.dctx, LW.save_for_backward = was_dctx, was_saving
+        res = out
         if self.tokenizer is not None:
-            return [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
-        return out
+            res = [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
+        return (res, stats) if return_info else res
 
 
 # --------------------------------------------------------------------------------------

@@ -1186,6 +1186,45 @@ def sample_logits_rows(logits, slot_of_row, history, hist_len, params, step, max
           "tcavt_sample_logits_rows")
 
 
+def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finished, out_tokens, advance_pos, workspace=None,
+                  max_new=None, out_row=None, slot_of_row=None, stop=None):
+    """The three token-selection entries in one, with optional ending rules (tcavt_sample_tokens).  The form follows from the
+    arguments as in the C entry: slot_of_row -> sample_logits_rows, max_new / out_row -> sample_logits_slots, neither ->
+    sample_logits.  stop: a stopping.DeviceStopRules (or a capi.StopRules struct), or None -- then, and with nothing set in it,
+    the launches are those of the corresponding existing entry."""
+    who = "sample_tokens."
+    rows, V = logits.shape
+    if workspace is not None:
+        _req(workspace, torch.uint8, who + "workspace")
+    _req(logits, torch.float32, who + "logits")
+    if history.dim() != 2 or out_tokens.dim() != 2:
+        raise capi.TcavtError("sample_tokens: history needs one row per sample / slot, out_tokens one row per sample / request")
+    slots = slot_of_row is not None or max_new is not None or out_row is not None
+    n = history.shape[0] if slot_of_row is not None else rows
+    if history.shape[0] != n or (not slots and out_tokens.shape[0] != rows):
+        raise capi.TcavtError("sample_tokens: history / out_tokens need one row per sample")
+    if slot_of_row is not None:
+        _req(slot_of_row, torch.int32, who + "slot_of_row")
+        _need(slot_of_row, rows, who + "slot_of_row")
+    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), (step, torch.int32, n if slots else 1, "step"),
+                         (cur_tok, torch.int64, n, "cur_tok"), (pos, torch.int32, n, "pos"), (finished, torch.int32, n, "finished"),
+                         (out_tokens, torch.int64, 1, "out_tokens")) + (
+                             ((max_new, torch.int32, n, "max_new"), (out_row, torch.int64, n, "out_row")) if slots else ()):
+        if t is None:
+            raise capi.TcavtError(f"sample_tokens: {nm} is missing")
+        _req(t, dt, who + nm)
+        _need(t, k, who + nm)
+    a = capi.SampleArgs()
+    a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
+    a.params, a.step, a.max_new, a.out_row = ctypes.pointer(params), step.data_ptr(), ptr(max_new), ptr(out_row)
+    a.cur_tok, a.pos, a.finished, a.out_tokens = cur_tok.data_ptr(), pos.data_ptr(), finished.data_ptr(), out_tokens.data_ptr()
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() if workspace is not None else 0
+    if stop is not None:
+        a.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
+    a.rows, a.V, a.n_state, a.hist_cap, a.out_cap, a.advance_pos = rows, V, n, history.shape[1], out_tokens.shape[1], int(advance_pos)
+    check(lib().tcavt_sample_tokens(ctypes.byref(a), stream_ptr()), "tcavt_sample_tokens")
+
+
 def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value,
                      out_row_value, bad_slot_flag, history, hist_len, step, max_new, out_row, pos, finished, cur_tok):
     """The G samples of a grouped prefill move into their slots of an S-slot pool in one launch (tcavt_slot_admit_group).  src: the
