@@ -487,8 +487,9 @@ int tcavt_silu_mul_bwd(const void* gu_bf16, const void* g_act_bf16, void* g_gu_b
 int tcavt_rmsnorm_bwd(const void* x, const float* gamma, const void* gy_bf16, const void* gy2_bf16, float eps,
                       float* gx, void* gx_bf16, int accumulate, int M, int H, int gy_dtype, int out_dtype,
                       const float* gy_scale, int x_dtype, tcavt_stream_t stream);
-/* scale[0] = S = 2^k with max|g_a, g_b| * S in [target / 2, target], scale[1] = 1 / S, decided on the device (S = 1 for
-   all-zero or non-finite input); g_a, g_b (optional) 16-bit [n] of dtype16; scratch: one uint32, zero-initialised once.
+/* scale[0] = S = 2^k with max|g_a, g_b| * S in [target / 2, target], scale[1] = 1 / S, decided on the device (k clamped to
+   +-60; S = 1 for all-zero input and for input that holds an inf; a NaN is ignored by the maximum: S follows the finite
+   values beside it, S = 1 if there are none); g_a, g_b (optional) 16-bit [n] of dtype16; scratch: one uint32, zero-initialised once.
    backoff (optional device int32): S is divided by 2^*backoff -- dynamic loss scaling: tcavt_adamw_gated raises its ctl[6] by
    four when it skips an update for a non-finite gradient norm and gives one back per 256 applied updates */
 int tcavt_grad_scale_pick(const void* g_a, const void* g_b, int64_t n, int dtype16, float target, float* scale,

@@ -1839,8 +1839,9 @@ __global__ __launch_bounds__(256) void adapter_grads_out_kernel(float* __restric
 // Power-of-two scale of the fp16 backward: S = 2^k with  max|g| * S  in [target / 2, target]  (g = the 16-bit gradient(s) the
 // backward starts from; bf16, so they cannot overflow themselves).  The backward is linear in g: every 16-bit gradient
 // tensor downstream carries the factor S, the fp32 weight gradients are multiplied by 1 / S at the end.  Decided on the
-// device (no host synchronisation): scale[0] = S, scale[1] = 1 / S.  All-zero or non-finite g: S = 1 (a non-finite
-// gradient then reaches the gated optimizer as it did before).
+// device (no host synchronisation): scale[0] = S, scale[1] = 1 / S.  All-zero g, or an inf in g: S = 1.  A NaN is dropped by
+// the maximum (fmaxf), so S follows the finite values beside it (S = 1 if there are none).  Either way the non-finite
+// gradient itself walks on and reaches the gated optimizer as it did before.  The exponent of S is clamped to +-60.
 // ---------------------------------------------------------------------------
 template <bool F16>
 __global__ __launch_bounds__(256) void grad_amax_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, long n8,
@@ -1864,8 +1865,13 @@ __global__ void grad_scale_set_kernel(unsigned int* __restrict__ amax_bits, floa
   const float m = __uint_as_float(*amax_bits);
   float s = 1.f;
   if (m > 0.f && m < 3.0e38f) {
+    const float q = target / m;
     int e;
-    (void)frexpf(target / m, &e);       // target / m = f * 2^e, f in [0.5, 1)
+    // a quotient that left fp32 (bf16 gradients below ~2^-120: inf, for which frexpf leaves e = 0 and S came out as 1 / 2; or 0)
+    // ends at the clamp below, like every other quotient beyond 2^+-60
+    if (q > 3.0e38f) e = 200;
+    else if (q < 1.2e-38f) e = -200;
+    else (void)frexpf(q, &e);           // target / m = f * 2^e, f in [0.5, 1)
     // backoff (tcavt_adamw_gated's ctl[6]): binary orders of extra headroom, raised by four whenever an update was skipped for
     // a non-finite gradient norm -- the walk grew the gradient by more than the 2^8 the target leaves -- and given back slowly
     e = max(-60, min(60, e - 1 - (backoff ? *backoff : 0)));       // 2^(e-1) <= target / m
