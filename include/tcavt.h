@@ -233,7 +233,8 @@ int tcavt_gemm_bf16(const tcavt_gemm_args* args, tcavt_stream_t stream);
  * Llama RMSNorm: out = bf16( x * rsqrt(mean(x^2) + eps) * gamma ), x fp32 [M][H]
  * (modeling_llama.py:62-67; F1/F7 of SURVEY.md section 8a).
  * out_f32 (optional) receives the un-rounded fp32 result (final norm ->
- * hidden_states[-1], scripts/train.py:553).  H % 8 == 0, H <= 8192.
+ * hidden_states[-1], scripts/train.py:553).  H % 8 == 0, H <= 8192; x, gamma and out_f32 16-byte aligned, out_bf16 and
+ * out_drop_bf16 8-byte aligned (all checked: TCAVT_ERR_ARG before any launch).
  * out_drop_bf16 (optional, train mode) additionally receives dropout(out_bf16) with the Philox mask of
  * (dropout_seed, dropout_site, element m * H + n) -- the LoRA branch input (PEFT lora_dropout on x,
  * scripts/train.py:433-440); identical to tcavt_dropout applied to out_bf16.
@@ -248,7 +249,7 @@ int tcavt_rmsnorm(const float* x, const float* gamma, float eps, void* out_bf16,
  *   y = LN(x + residual) * gamma + beta      (post-LN blocks of
  * nn.TransformerEncoderLayer / DecoderLayer used at scripts/train.py:358,402,405
  * and LayerNorms at :662,672,760).  Writes fp32 and/or bf16 copies.
- * D % 4 == 0, D <= 4096.
+ * D % 4 == 0, D <= 4096; x, residual, gamma, beta and out_f32 16-byte aligned, out_bf16 8-byte aligned (checked).
  * ---------------------------------------------------------------------- */
 int tcavt_layernorm(const float* x, const float* residual, const float* gamma,
                     const float* beta, float eps, float* out_f32, void* out_bf16,
@@ -288,6 +289,8 @@ int tcavt_cast_f32_16(const float* x, void* out16, int64_t n, int dtype16, tcavt
  * in the others (npart = H / 64, the layout TCAVT_EPI_NORM_OUT writes).
  * h == NULL (h16 given): the 16-bit residual stream of tcavt_llama_stack_forward -- no fp32 copy is written and the sum
  * of squares is that of the ROUNDED values (the stream's own content).
+ * H % 8 == 0; 16-byte aligned: h, and what the rows read (img, vis_mod with Nq > 0; the table, txt_mod with Lt > 0); 8-byte
+ * aligned: h16, ids (checked).
  * ---------------------------------------------------------------------- */
 int tcavt_embed_fuse(const void* table_bf16, const int64_t* ids, const float* img,
                      const float* vis_mod, const float* txt_mod, float* h, int B,
@@ -393,7 +396,7 @@ int tcavt_masked_mean(const float* enc, const int32_t* len, float* emb, int B, i
  *   xp[b][c][t] = conv_w[c][0]*x[b][0][t] + conv_w[c][1]*x[b][1][t] + conv_b[c]
  *   enc[b][c][s] = sum_t enc_w[c][s][t]*(xp[b][c][t]-xp[b][c][T-1]) + enc_b[c][s]
  *                  + xp[b][c][T-1] + pos[c][s]
- * x [B][2][T]; out enc_tok token-major [B][T][C]
+ * x [B][2][T]; out enc_tok token-major [B][T][C].  x[b] is staged in LDS: 8 T bytes <= 64 KiB (checked).
  * ---------------------------------------------------------------------- */
 int tcavt_ltsf_front(const float* x, const float* conv_w, const float* conv_b,
                      const float* enc_w, const float* enc_b, const float* pos,
@@ -1091,7 +1094,8 @@ int tcavt_rownorm_prep(const float* x, void* x16, float* part, int64_t M, int H,
                        float stream_scale, tcavt_stream_t stream);
 
 /* RMSNorm of 16-bit rows x16 [M][H] (fp32 arithmetic; H % 256 == 0): out16 and / or out_f32 -- the final norm of the
- * 16-bit residual stream (HF modeling_llama.py:62-67 on the stream's stored values) */
+ * 16-bit residual stream (HF modeling_llama.py:62-67 on the stream's stored values).  x16, gamma, out16 and out_f32 16-byte
+ * aligned (checked). */
 int tcavt_rmsnorm16(const void* x16, const float* gamma, float eps, void* out16, float* out_f32, int M, int H, int dtype16,
                     tcavt_stream_t stream);
 

@@ -34,6 +34,7 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // ---- bf16 <-> f32 ---------------------------------------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {

@@ -447,8 +447,10 @@ extern "C" int tcavt_rmsnorm(const float* x, const float* gamma, float eps, void
                   "rmsnorm: out_drop needs 0 < dropout_p < 1");
   bf16_t* od = static_cast<bf16_t*>(out_drop_bf16);
   const DropoutP drop = make_dropout(dropout_p, dropout_seed, dropout_site);
-  TCAVT_CHECK_ARG(M > 0 && H > 0 && H % 8 == 0, "rmsnorm: H=%d must be a multiple of 8", H);
+  TCAVT_CHECK_ARG(M > 0 && H > 0 && H % 8 == 0 && H <= 8192, "rmsnorm: H=%d must be a multiple of 8 and <= 8192", H);
   TCAVT_CHECK_ARG(aligned16(x) && aligned16(gamma), "rmsnorm: unaligned input");
+  // (the rows are written with 8-byte (16-bit outputs) and 16-byte (fp32) stores; NULL passes)
+  TCAVT_CHECK_ARG(aligned8(out_bf16) && aligned16(out_f32) && aligned8(out_drop_bf16), "rmsnorm: unaligned output");
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid((M + 3) / 4), block(256);
   bf16_t* ob = static_cast<bf16_t*>(out_bf16);
@@ -477,6 +479,9 @@ extern "C" int tcavt_layernorm(const float* x, const float* residual, const floa
   TCAVT_CHECK_ARG(x && gamma && beta && (out_f32 || out_bf16), "layernorm: null pointer");
   TCAVT_CHECK_ARG(is16(dtype16), "layernorm: dtype16 must be TCAVT_BF16 or TCAVT_F16");
   TCAVT_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 4096, "layernorm: D=%d must be a multiple of 4 and <= 4096", D);
+  // (16-byte loads of x / residual / gamma / beta, 16-byte fp32 and 8-byte 16-bit stores; NULL passes)
+  TCAVT_CHECK_ARG(aligned16(x) && aligned16(residual) && aligned16(gamma) && aligned16(beta) && aligned16(out_f32) && aligned8(out_bf16),
+                  "layernorm: unaligned pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid((M + 3) / 4), block(256);
   bf16_t* ob = static_cast<bf16_t*>(out_bf16);
@@ -577,6 +582,11 @@ int tcavt::embed_fuse_impl(const void* table_bf16, const int64_t* ids, const flo
   TCAVT_CHECK_ARG(is16(table_dtype), "embed_fuse: table_dtype must be TCAVT_BF16 or TCAVT_F16");
   TCAVT_CHECK_ARG((h16 == nullptr) == (part == nullptr) && (!part || npart > 0), "embed_fuse: h16 and part go together (npart > 0)");
   TCAVT_CHECK_ARG(B > 0 && Nq >= 0 && Lt >= 0 && Nq + Lt > 0 && H % 8 == 0 && V > 0, "embed_fuse: bad shape");
+  // (16-byte loads of the operands a row reads -- img / vis_mod only with Nq > 0, table / txt_mod only with Lt > 0 --, 16-byte
+  // stores of h, 8-byte stores of h16; NULL passes)
+  TCAVT_CHECK_ARG((Nq == 0 || (aligned16(img) && aligned16(vis_mod))) && (Lt == 0 || (aligned16(table_bf16) && aligned16(txt_mod) && aligned8(ids))) &&
+                      aligned16(h) && aligned8(h16),
+                  "embed_fuse: unaligned pointer");
   const long rows = (long)B * (Nq + Lt);
   if (table_dtype == TCAVT_F16)
     hipLaunchKernelGGL(embed_fuse_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,

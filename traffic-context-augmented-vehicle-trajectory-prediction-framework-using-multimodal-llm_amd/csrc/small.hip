@@ -413,6 +413,7 @@ extern "C" int tcavt_ltsf_front(const float* x, const float* conv_w, const float
                                 float* enc_tok, float* xp_tok, int B, int C, int T, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(x && conv_w && conv_b && enc_w && enc_b && pos && enc_tok && B > 0 && C > 0 && T > 0,
                   "ltsf_front: bad args");
+  TCAVT_CHECK_ARG((long)2 * T * 4 <= 64 * 1024, "ltsf_front: T=%d too large for LDS (x[b] is staged there: 8 T bytes)", T);
   hipLaunchKernelGGL(ltsf_front_kernel, dim3(B), dim3(256), 2 * T * sizeof(float),
                      static_cast<hipStream_t>(stream), x, conv_w, conv_b, enc_w, enc_b, pos, enc_tok, xp_tok, B, C, T);
   TCAVT_CHECK_LAUNCH("ltsf_front");

@@ -459,6 +459,7 @@ int tcavt::rmsnorm16_impl(const void* x16, const float* gamma, float eps, void* 
   TCAVT_CHECK_ARG(x16 && gamma && (out16 || out_f32) && M > 0 && H > 0 && H % 256 == 0 && is16(dtype16),
                   "rmsnorm16: bad args (H %% 256 == 0)");
   TCAVT_CHECK_ARG(aligned16(x16) && aligned16(gamma), "rmsnorm16: unaligned input");
+  TCAVT_CHECK_ARG(aligned16(out16) && aligned16(out_f32), "rmsnorm16: unaligned output");  // (16-byte stores; NULL passes)
   const dim3 grid((unsigned)((M + 3) / 4)), block(256);
   if (dtype16 == TCAVT_F16)
     hipLaunchKernelGGL(rmsnorm16_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(x16), gamma,
