@@ -1,0 +1,502 @@
+"""Host side of text generation: what LlamaMultiModal.generate_batch and generate_pool run.  The user
+contract -- arguments, defaults, semantics -- is documented on those two methods (model.py); this module is the code behind them,
+one piece per job:
+
+  Prefill          image tokens + prompt through the decoder into a KV cache, last rows through the lm_head -> first logits
+  select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens)
+  capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
+  FinishedPoll     the finished flags to pinned host memory and an event wait
+  decode_args      the tcavt_decode_args of the decode step
+  sample_params, eval_arithmetic, the check_* / stop_rules argument checks, cache_buffers (with the KV8 plane table)
+
+Workspace names and the order in which they are first requested are part of what tests/test_generation_trace_cpu.py pins;
+``Prefill.reserve`` exists so that the pool can request a prefill's buffers where that order has them."""
+import contextlib
+import os
+from types import SimpleNamespace
+
+import torch
+
+from . import capi, ops
+from .pool import SlotScheduler
+from .stopping import BUDGET, StopRules
+
+I32, I64 = torch.int32, torch.int64
+KV8_PLANES = (("kc", 64), ("ks", 2), ("vc", 64), ("vs", 2))  # plane -> bytes per cached row and kv head (quant.kv8_quantize)
+
+
+# --------------------------------------------------------------------------------------
+# argument checks shared by both entries (each entry calls them in its own, fixed order; nothing here touches a device)
+# --------------------------------------------------------------------------------------
+def check_format(who, name, value):
+    if value not in ("fp16", "fp8"):
+        raise ValueError(f"{who}: {name} must be 'fp16' or 'fp8', got {value!r}")
+
+
+def stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id):
+    rules = StopRules(mllm.llama_wrapper.shape.vocab, stop_token_ids, stop_sequences, min_new_tokens)
+    if rules.min_new_tokens > 0 and eos_token_id is None and not rules.stop_token_ids:
+        raise ValueError(f"{who}: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
+    return rules
+
+
+def check_fp8_weights(who, decode_weights, rows, rows_name):
+    if decode_weights == "fp8":
+        if rows > 32:
+            raise ValueError(f"{who}: decode_weights='fp8' runs on the skinny decode path only ({rows_name} <= 32), "
+                             f"got {rows_name} = {rows}")
+        if os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") == "1":
+            raise ValueError(f"{who}: decode_weights='fp8' has no row-major form (TCAVT_DECODE_ROWMAJOR=1 is set)")
+
+
+# --------------------------------------------------------------------------------------
+# the pieces
+# --------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def eval_arithmetic(mllm):
+    """Generation runs eval arithmetic (model.eval() at train.py:581): no dropout context, no decoder tape, no autograd.  The
+    decoder's two settings are put back afterwards; the Q-Former's dropout context stays None."""
+    LW = mllm.llama_wrapper
+    with torch.no_grad():
+        was_dctx, LW.dctx, mllm.qformer.dctx = LW.dctx, None, None
+        was_saving, LW.save_for_backward = LW.save_for_backward, False
+        try:
+            yield
+        finally:
+            LW.dctx, LW.save_for_backward = was_dctx, was_saving
+
+
+def sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id, pad_token_id, seed):
+    return capi.SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k), int(no_repeat_ngram_size),
+                             int(bool(do_sample)), -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def sample_workspace(ws, name, rows, dev):
+    """Workspace of the two-stage token selection (rows x 16 workgroups + one per sample) for ``rows`` logits rows."""
+    return ws.get(name, (int(capi.lib().tcavt_sample_workspace_bytes(rows)),), torch.uint8, dev, zero=True)
+
+
+def cache_buffers(ws, tag, LW, kv_cache, B, rows, dev, zero=False):
+    """The KV cache of B samples x ``rows`` positions under ``tag``: the 16-bit pair (k, v), or the four KV8 planes."""
+    ll = LW.shape
+    if kv_cache == "fp8":
+        return tuple(ws.get(f"{tag}.kv8.{nm}", (ll.layers, B, ll.n_kv_heads, rows, per), torch.uint8, dev, zero=zero)
+                     for nm, per in KV8_PLANES)
+    return tuple(ws.get(f"{tag}.{nm}", (ll.layers, B, rows, ll.n_kv_heads * ll.head_dim), LW.storage, dev, zero=zero)
+                 for nm in ("kc", "vc"))
+
+
+class Prefill:
+    """The ordinary batched decoder pass over [image tokens | prompt] at B rows that writes a KV cache of ``cache_rows``
+    positions and ends in the logits of every row's last valid position.  Its buffers live in the workspace as ``{tag}.h``
+    (fp32 stream; not with the 16-bit stream), ``.kvlen``, ``.final16``, ``.x16``, ``.logits`` and the cache (``.kc`` / ``.vc`` or
+    ``.kv8.{kc,ks,vc,vs}``): ``buf(name)`` hands one out ("cache": the tuple), requesting it on first use."""
+
+    def __init__(self, mllm, tag, B, Lt, cache_rows, kv_cache, dev):
+        LW = mllm.llama_wrapper
+        self.mllm, self.tag, self.B, self.cache_rows, self.kv_cache, self.dev = mllm, tag, B, cache_rows, kv_cache, dev
+        self.L = mllm.qformer.num_query_tokens + Lt
+        self.P, self.PL = mllm._prepared(), LW._prepared()
+        H, M = mllm.llama_hidden_size, B * self.L
+        self.specs = dict(h=((M, H), torch.float32), kvlen=((B,), I32), final16=((M, H), LW.storage), x16=((B, H), LW.storage),
+                          logits=((B, LW.shape.vocab), torch.float32))
+        self.flags = None  # mm.flags of the last run
+
+    def buf(self, name):
+        m = self.mllm
+        if name == "cache":
+            return cache_buffers(m._ws, self.tag, m.llama_wrapper, self.kv_cache, self.B, self.cache_rows, self.dev)
+        if name == "h" and m.llama_wrapper.stream16:
+            return None
+        return m._ws.get(f"{self.tag}.{name}", *self.specs[name], self.dev)
+
+    def reserve(self, *names):
+        for name in names:
+            self.buf(name)
+
+    def run(self, vision, ids, mask64, after_stack=None):
+        """vision [B, ...], ids int64 [B, Lt], mask64 int64 [B, Lt] (right padded) -> fp32 logits [B, vocab] of the first new
+        token.  ``after_stack`` runs between the decoder stack and the gather of the last rows (the pool's admission launch)."""
+        m, B, L, dev = self.mllm, self.B, self.L, self.dev
+        LW, P, PL = m.llama_wrapper, self.P, self.PL
+        H, Nq = m.llama_hidden_size, m.qformer.num_query_tokens
+        img = m._image_tokens(vision)
+        h = self.buf("h")
+        flags = self.flags = m._last_flags = m._ws.get("mm.flags", (3,), I32, dev, zero=True)
+        h16, part = LW.norm_inputs(B * L, dev)
+        ops.embed_fuse(PL.table, ids, img, P.vis, P.txt, h, flags[0:1], h16=h16, part=part, npart=LW.norm_npart(B * L),
+                       stream_scale=LW.stream_scale)
+        kv_len = self.buf("kvlen")
+        ops.mask_to_kvlen(mask64, Nq, kv_len, flags[1:2])
+        cache, final16 = self.buf("cache"), self.buf("final16")
+        LW.decoder_stack(h, kv_len, B, L, out_bf16=final16, kv_cache=cache + (self.cache_rows,), nonfinite_flag=flags[2:3])
+        if after_stack is not None:
+            after_stack()
+        x16 = self.buf("x16")
+        ops.gather_last(final16, kv_len, x16, B, L, H)
+        logits = self.buf("logits")
+        ops.gemm_bf16(x16, PL.table, out=logits)  # lm_head, tied to embed_tokens
+        return logits
+
+
+def slot_state(history, hist_len, step, cur, pos, finished, max_new=None, out_row=None):
+    """The device-resident generation state the samplers advance: one row / entry per sample (step: one word), or -- with
+    max_new and out_row -- per decode slot."""
+    return SimpleNamespace(history=history, hist_len=hist_len, step=step, cur=cur, pos=pos, finished=finished, max_new=max_new,
+                           out_row=out_row)
+
+
+def slot_view(st, s):
+    """The state of slot s alone, as views (the one-row logits of a request being admitted)."""
+    return slot_state(*(t[s:s + 1] for t in (st.history, st.hist_len, st.step, st.cur, st.pos, st.finished, st.max_new, st.out_row)))
+
+
+def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None):
+    """Logits processors + token selection on the state ``st``.  The form follows from the arguments: ``slot_of_row`` -> the rows
+    of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
+    (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens."""
+    if drules is not None:
+        ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
+                          workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules)
+    elif slot_of_row is not None:
+        ops.sample_logits_rows(logits, slot_of_row, st.history, st.hist_len, sp, st.step, st.max_new, st.out_row, st.cur, st.pos,
+                               st.finished, out, advance_pos=advance_pos, workspace=workspace)
+    elif st.max_new is not None:
+        ops.sample_logits_slots(logits, st.history, st.hist_len, sp, st.step, st.max_new, st.out_row, st.cur, st.pos, st.finished,
+                                out, advance_pos=advance_pos, workspace=workspace)
+    else:
+        ops.sample_logits(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
+                          workspace=workspace)
+
+
+def capture(fn, dev, use_graph):
+    """``fn`` has run eagerly once -- the warm-up of its workspaces and of every kernel form it uses.  -> the callable for its
+    later runs: the replay of a hipGraph captured here (the capture launches nothing), or ``fn`` itself without graphs."""
+    if not (use_graph and dev.type == "cuda"):
+        return fn
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return graph.replay
+
+
+class FinishedPoll:
+    """Reads the finished flags back: [n] int32 to pinned host memory, then an event wait."""
+
+    def __init__(self, n, dev):
+        cuda = dev.type == "cuda"
+        self.host = torch.empty(n, dtype=I32).pin_memory() if cuda else torch.empty(n, dtype=I32)
+        self.event = torch.cuda.Event() if cuda else None
+
+    def read(self, finished):
+        self.host.copy_(finished, non_blocking=True)
+        if self.event is not None:
+            self.event.record()
+            self.event.synchronize()
+        return self.host
+
+
+def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits, flags):
+    """tcavt_decode_args of a decode step at B rows on the cache `cache` = (k, v, Lmax) or (k_codes, k_scales, v_codes,
+    v_scales, Lmax); scratch buffers come from the workspace under ``tag``; ``who`` names the caller in errors."""
+    LW, ws, P = mllm.llama_wrapper, mllm._ws, mllm._prepared()
+    ll, PL, dev = LW.shape, LW._prepared(), logits.device
+    H, st = mllm.llama_hidden_size, LW.storage
+    nqkv = (ll.n_q_heads + 2 * ll.n_kv_heads) * ll.head_dim
+    cos, sin = LW._rope_tables(Lmax, dev)
+    a = capi.DecodeArgs()
+    # fragment-major weight copies for the step's weight streams and, on the 16-bit stream, fragment-major
+    # activations between its kernels (16 or 32 whole rows per buffer); TCAVT_DECODE_ROWMAJOR=1 /
+    # TCAVT_DECODE_ACT_ROWMAJOR=1: the row-major forms (A/B, tests)
+    DW = LW.decode_weights(decode_weights) if (B <= 32 and os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") != "1") else None
+    if DW is None and decode_weights == "fp8":
+        raise ValueError(f"{who}: decode_weights='fp8': this decoder shape has no skinny form "
+                         "(hidden, inter and n_q_heads * head_dim must be multiples of 256, vocab of 16)")
+    # (B <= 8: row-major activation rows are HALF the bytes of a 16-token fragment -- lanes of the empty token slots
+    #  repeat the last row -- and the step is 0.89 vs 0.91 ms; B = 16: 0.98 vs 1.05, B = 32: 1.09 vs 1.21 ms)
+    frag_act = DW is not None and LW.stream16 and os.environ.get("TCAVT_DECODE_ACT_ROWMAJOR", "0") != "1"
+    # up to 8 samples: ONE block of 8 tokens (a k-step of activations = 512 consecutive bytes); blocks of 16 beyond
+    # (TCAVT_DECODE_ACT_FRAG=16: blocks of 16 at any B, A/B)
+    act_mode = 0 if not frag_act else (2 if B <= 8 and os.environ.get("TCAVT_DECODE_ACT_FRAG", "") != "16" else 1)
+    Br = B if not frag_act else (8 if act_mode == 2 else 16 if B <= 16 else 32)
+    bufs = dict(h16=ws.get(f"{tag}.dh16", (Br, H), st, dev, zero=True),
+                part=ws.get(f"{tag}.dpart", (B, H // 16), torch.float32, dev),
+                qkv=ws.get(f"{tag}.dqkv", (B, nqkv), st, dev),
+                att=ws.get(f"{tag}.datt", (Br, ll.n_q_heads * ll.head_dim), st, dev, zero=True),
+                act=ws.get(f"{tag}.dact", (Br, ll.inter), st, dev, zero=True), t=ws.get(f"{tag}.dt", (B, 64), st, dev, zero=True))
+    if not LW.stream16:
+        bufs["h"] = ws.get(f"{tag}.dh", (B, H), torch.float32, dev)
+    for k_, v_ in bufs.items():
+        setattr(a, k_, v_.data_ptr())
+    a.layers, a.gamma_final = PL.carr, PL.g_final.data_ptr()
+    if DW is not None:
+        a.layers, a.table_packed = DW.carr, DW.table.data_ptr()
+        a.w_layout = capi.W_FRAG8 if decode_weights == "fp8" else capi.W_FRAG16
+    a.act_layout = act_mode
+    a.rope_cos, a.rope_sin, a.rope_L = cos.data_ptr(), sin.data_ptr(), Lmax
+    a.table, a.txt_mod = PL.table.data_ptr(), P.txt.data_ptr()
+    a.cur_tok, a.pos = cur.data_ptr(), pos.data_ptr()
+    if len(cache) == 5:  # the four KV8 planes
+        a.kv8_k_codes, a.kv8_k_scales, a.kv8_v_codes, a.kv8_v_scales = (t_.data_ptr() for t_ in cache[:4])
+        a.kv_lmax = Lmax
+    else:
+        a.k_cache, a.v_cache, a.kv_lmax = cache[0].data_ptr(), cache[1].data_ptr(), Lmax
+    dx16 = ws.get(f"{tag}.dx16", (Br, H), st, dev, zero=True) if frag_act else ws.get(f"{tag}.x16", (B, H), st, dev)
+    a.x16, a.logits, a.bad_id_flag = dx16.data_ptr(), logits.data_ptr(), flags.data_ptr()
+    a.nonfinite_flag = flags[2:3].data_ptr()
+    if LW.use_lora and LW.lora_r <= 8 and os.environ.get("TCAVT_DECODE_LORA_LAUNCH", "0") != "1":  # (A/B switch)
+        a.lora_part, a.lora_rank = ws.get(f"{tag}.lpart", (B * H,), torch.float32, dev).data_ptr(), LW.lora_r
+    # K split across workgroups (tcavt_gemm_args.splitk_ws): off by default -- measured 1.30 vs 1.22 ms per step
+    # at B = 8 and 1.84 vs 1.87 at B = 32 (the hand-off costs what the split gains)
+    if os.environ.get("TCAVT_DECODE_SPLITK", "0") == "1":
+        skws = ws.get(f"{tag}.splitk", (9 << 20,), torch.uint8, dev, zero=True)  # tickets zeroed once, slabs behind
+        a.splitk_ws, a.splitk_ws_bytes = skws.data_ptr(), skws.numel()
+    a.n_layers, a.B, a.H, a.I, a.nq, a.nkv, a.V = ll.layers, B, H, ll.inter, ll.n_q_heads, ll.n_kv_heads, ll.vocab
+    a.dtype16 = capi.F16 if st == torch.float16 else capi.BF16
+    a.rms_eps, a.lora_scale = ll.rms_eps, (LW.lora_alpha / LW.lora_r) if LW.use_lora else 0.0
+    a.stream_scale = float(LW.stream_scale)
+    return a
+
+
+# --------------------------------------------------------------------------------------
+# LlamaMultiModal.generate_batch
+# --------------------------------------------------------------------------------------
+def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
+                   top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
+                   decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every):
+    """-> (out int64 [B, max_new_tokens] on the device, info or None)."""
+    who = "generate_batch"
+    check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
+    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
+    if poll_every is not None and int(poll_every) < 1:
+        raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
+    if input_ids is None:
+        if mllm.tokenizer is None or context_str_list is None:
+            raise NotImplementedError(
+                "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
+        enc = mllm.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
+                             return_tensors="pt")
+        input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
+    B, Lt = input_ids.shape
+    N = int(max_new_tokens)
+    if N < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    check_format(who, "decode_weights", decode_weights)
+    check_fp8_weights(who, decode_weights, B, "B")
+    dev = vision_embs_batch.device
+    input_ids = input_ids.to(dev).contiguous()
+    attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
+    Lmax = mllm.qformer.num_query_tokens + Lt + N
+    pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev)
+    with eval_arithmetic(mllm):
+        # ---- prefill: image tokens + prompt through the decoder, keys / values of every layer into the cache
+        logits = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
+        kv_len = pf.buf("kvlen")
+        # ---- device-resident generation state
+        history = torch.zeros(B, Lt + N, dtype=I64, device=dev)
+        history[:, :Lt] = input_ids
+        st = slot_state(history, (kv_len - mllm.qformer.num_query_tokens).to(I32), torch.zeros(1, dtype=I32, device=dev),
+                        torch.zeros(B, dtype=I64, device=dev), kv_len.clone(), torch.zeros(B, dtype=I32, device=dev))
+        out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
+        sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
+                           pad_token_id, seed)
+        # two-stage token selection (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form, A/B)
+        sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
+        # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
+        drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
+        select(logits, st, sp, out, False, sws, drules)
+        steps_run = 0
+        if N > 1:
+            a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, pf.buf("cache") + (Lmax,), st.cur, st.pos, logits, pf.flags)
+
+            def one_step():
+                ops.llama_decode_step(a)
+                select(logits, st, sp, out, True, sws, drules)
+
+            one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)
+            steps_run = 1
+            if N > 2:
+                step = capture(one_step, dev, use_graph)  # the N - 2 replays are tokens 3 .. N
+                if poll_every is None:
+                    for _ in range(N - 2):
+                        step()
+                    steps_run = N - 1
+                else:
+                    # every poll_every steps: read the finished flags, and out once every row has ended (out was filled with
+                    # pad and a finished row only ever writes pad: the result is the same)
+                    poll = FinishedPoll(B, dev)
+                    while steps_run < N - 1:
+                        n_now = min(int(poll_every), N - 1 - steps_run)
+                        for _ in range(n_now):
+                            step()
+                        steps_run += n_now
+                        if bool((poll.read(st.finished) != 0).all()):
+                            break
+        info = None
+        if return_info:
+            reason, n_gen = drules.finish_reason.cpu(), drules.n_generated.cpu()
+            ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
+            reason[ran_out], n_gen[ran_out] = BUDGET, N
+            info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
+    return out, info
+
+
+# --------------------------------------------------------------------------------------
+# LlamaMultiModal.generate_pool
+# --------------------------------------------------------------------------------------
+def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k,
+                  top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights,
+                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info):
+    """-> (out int64 [R, max budget] on the device, mllm.pool_stats)."""
+    who = "generate_pool"
+    # ---- every illegal value is refused before anything touches a device
+    check_format(who, "kv_cache", kv_cache)
+    check_format(who, "decode_weights", decode_weights)
+    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
+    S, poll_every = int(slots), int(poll_every)
+    if S < 1:
+        raise ValueError(f"generate_pool: slots must be >= 1, got {slots}")
+    if poll_every < 1:
+        raise ValueError(f"generate_pool: poll_every must be >= 1, got {poll_every}")
+    G = int(admit_group)
+    if not 1 <= G <= S:
+        raise ValueError(f"generate_pool: admit_group must be in [1, slots = {S}], got {admit_group}")
+    if input_ids.dim() != 2 or attention_mask.shape != input_ids.shape or vision_embs.shape[0] != input_ids.shape[0]:
+        raise ValueError("generate_pool: vision_embs [R, ...], input_ids [R, Lt] and attention_mask [R, Lt] must agree")
+    R, Lt = input_ids.shape
+    scalar = not hasattr(max_new_tokens, "__len__")
+    budgets = [int(max_new_tokens)] * R if scalar else [int(n) for n in max_new_tokens]
+    if len(budgets) != R:
+        raise ValueError(f"generate_pool: max_new_tokens has {len(budgets)} budgets for {R} requests")
+    if (scalar and int(max_new_tokens) < 1) or any(n < 1 for n in budgets):
+        raise ValueError("generate_pool: every budget in max_new_tokens must be >= 1")
+    Nmax = int(max_new_tokens) if scalar else max(budgets, default=0)
+    LW, ws = mllm.llama_wrapper, mllm._ws
+    ll = LW.shape
+    if not 0 <= int(pad_token_id) < ll.vocab:  # (idle and finished slots feed the pad token to the decode step)
+        raise ValueError(f"generate_pool: pad_token_id = {pad_token_id} outside [0, vocab = {ll.vocab})")
+    check_fp8_weights(who, decode_weights, S, "slots")
+    dev = vision_embs.device
+    out = torch.full((R, Nmax), int(pad_token_id), dtype=I64, device=dev)
+    stats = mllm.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
+    mllm._pool_flag = None  # (the grouped admission's bad-slot flag: check_flags)
+    if R == 0:
+        if return_info or not rules.empty:
+            stats.update(finish_reason=torch.zeros(0, dtype=I32), n_generated=torch.zeros(0, dtype=I32))
+        return out, stats
+    input_ids = input_ids.to(dev).contiguous()
+    mask64 = attention_mask.to(dev).to(I64).contiguous()
+    Nq = mllm.qformer.num_query_tokens
+    L = Nq + Lt
+    Lmax = L + Nmax  # 16 + Lt + max budget
+    pf = Prefill(mllm, "pool.pf", 1, Lt, L, kv_cache, dev)  # a request on its own, into a one-sample cache
+    with eval_arithmetic(mllm):
+        flags = mllm._last_flags = ws.get("mm.flags", (3,), I32, dev, zero=True)
+        # ---- the pool: S-slot cache and per-slot state
+        cache = cache_buffers(ws, "pool", LW, kv_cache, S, Lmax, dev, zero=True)
+        pf.reserve("cache")
+        for t_ in cache:
+            t_.select(-2, 0).zero_()
+        # idle state: zeroed cache row 0, pos = 0, finished = 1, cur_tok = pad
+        st = slot_state(history=ws.get("pool.history", (S, Lt + Nmax), I64, dev, zero=True),
+                        hist_len=ws.get("pool.hist_len", (S,), I32, dev).zero_(),
+                        step=ws.get("pool.step", (S,), I32, dev).zero_(),
+                        max_new=ws.get("pool.max_new", (S,), I32, dev).fill_(1),
+                        out_row=ws.get("pool.out_row", (S,), I64, dev).zero_(),
+                        pos=ws.get("pool.pos", (S,), I32, dev).zero_(),
+                        finished=ws.get("pool.finished", (S,), I32, dev).fill_(1),
+                        cur=ws.get("pool.cur", (S,), I64, dev).fill_(int(pad_token_id)))
+        logits = ws.get("pool.logits", (S, ll.vocab), torch.float32, dev)
+        pf.reserve("logits", "kvlen", "final16", "x16", "h")
+        poll = FinishedPoll(S, dev)
+        sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
+                           pad_token_id, seed)
+        # two-stage token selection, as generate_batch (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form)
+        two_stage = os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1"
+        sws = sample_workspace(ws, "pool.sample_ws", S, dev) if two_stage else None
+        sws1 = sample_workspace(ws, "pool.pf.sample_ws", 1, dev) if two_stage else None
+        a = decode_args(mllm, "pool", who, S, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, flags)
+        # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
+        drules = rules.to(dev).records(R, dev) if return_info or not rules.empty else None
+        # what both admission launches share: rows, src_lmax, kv_lmax, n_layers, S, nkv ... and the eight state arrays
+        geometry = (L, L, Lmax, ll.layers, S, ll.n_kv_heads)
+        state = (st.history, st.hist_len, st.step, st.max_new, st.out_row, st.pos, st.finished, st.cur)
+
+        def one_step():
+            ops.llama_decode_step(a)
+            select(logits, st, sp, out, True, sws, drules)
+
+        def admit(s, r):
+            # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
+            # and the first token from the one-row logits with the slot's state (views that start at slot s)
+            logits1 = pf.run(vision_embs[r:r + 1], input_ids[r:r + 1], mask64[r:r + 1], after_stack=lambda: ops.slot_admit(
+                pf.buf("cache"), cache, s, *geometry, input_ids[r], pf.buf("kvlen"), Nq, budgets[r], r, *state))
+            select(logits1, slot_view(st, s), sp, out, False, sws1, drules)
+
+        if G > 1:
+            # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
+            # with pad rows (its first request again, slot -1), so M = G * L and with it every kernel form is constant
+            pg = Prefill(mllm, "pool.pg", G, Lt, L, kv_cache, dev)
+            pg_vis = ws.get("pool.pg.vis", (G,) + tuple(vision_embs.shape[1:]), vision_embs.dtype, dev)
+            pg_ids = ws.get("pool.pg.ids", (G, Lt), I64, dev)
+            pg_mask = ws.get("pool.pg.mask", (G, Lt), I64, dev)
+            pg_slot = ws.get("pool.pg.slot", (G,), I32, dev)
+            pg_budget = ws.get("pool.pg.budget", (G,), I32, dev)
+            pg_outrow = ws.get("pool.pg.outrow", (G,), I64, dev)
+            pg.reserve("cache", "logits", "kvlen", "final16", "x16", "h")
+            pg_sws = sample_workspace(ws, "pool.pg.sample_ws", G, dev) if two_stage else None
+            bad_slot = mllm._pool_flag = ws.get("pool.pg.bad_slot", (1,), I32, dev, zero=True)
+            vis_all = vision_embs.contiguous()
+            budgets_dev = torch.tensor(budgets, dtype=I32, device=dev)
+
+            def stage(group):
+                # the group's rows of the request list -> the staging buffers (device-side gathers; two small uploads)
+                reqs = [r for _, r in group] + [group[0][1]] * (G - len(group))
+                idx = torch.tensor(reqs, dtype=I64, device=dev)
+                torch.index_select(vis_all, 0, idx, out=pg_vis)
+                torch.index_select(input_ids, 0, idx, out=pg_ids)
+                torch.index_select(mask64, 0, idx, out=pg_mask)
+                torch.index_select(budgets_dev, 0, idx, out=pg_budget)
+                pg_outrow.copy_(idx)
+                pg_slot.copy_(torch.tensor([s for s, _ in group] + [-1] * (G - len(group)), dtype=I32, device=dev))
+
+            def group_pass():
+                logits_g = pg.run(pg_vis, pg_ids, pg_mask, after_stack=lambda: ops.slot_admit_group(
+                    pg.buf("cache"), cache, pg_slot, *geometry, pg_ids, pg.buf("kvlen"), Nq, pg_budget, pg_outrow, bad_slot, *state))
+                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot)
+
+        sched = SlotScheduler(R, S, G)
+        step = later_pass = None
+        while True:
+            for group in (sched.admission_groups() if G > 1 else ()):
+                stage(group)
+                if not stats["groups"]:
+                    group_pass()  # the first pass runs eagerly: the warm-up of the workspaces and of every kernel form
+                else:
+                    if later_pass is None:  # captured once, before the second pass; only the staging buffers change
+                        later_pass = capture(group_pass, dev, use_graph)
+                    later_pass()
+                stats["groups"].append((tuple(r for _, r in group), tuple(s for s, _ in group), stats["steps"]))
+                stats["admitted"] += [(r, s, stats["steps"]) for s, r in group]
+            for s, r in (sched.admissions() if G == 1 else ()):
+                admit(s, r)
+                stats["admitted"].append((r, s, stats["steps"]))
+            if not sched.busy():
+                break
+            if step is None:
+                # the first step runs eagerly and unpolled, as in generate_batch: it is the warm-up of every kernel form
+                # the step uses; then the capture
+                one_step()
+                stats["steps"] = 1
+                step = capture(one_step, dev, use_graph)
+            for _ in range(poll_every):
+                step()
+            stats["steps"] += poll_every
+            n_ret = len(sched.retired)
+            sched.retire(poll.read(st.finished).tolist())
+            stats["retired"] += [(r, s, stats["steps"]) for r, s in sched.retired[n_ret:]]
+        if drules is not None:
+            stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
+    return out, stats

@@ -28,7 +28,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from . import ops, streams
+from . import generation, ops, streams
 from .config import LlamaShape, ModelConfig
 from .layout import interleave_gate_up
 from .rope import rope_tables
@@ -1278,69 +1278,6 @@ class LlamaMultiModal(nn.Module, _Prepared):
                 f"operand left the range of {self.storage} (|x| > {torch.finfo(self.storage).max:g}) at or before that layer, or the "
                 "inputs were not finite (DESIGN.md, precision contract)")
 
-    def _decode_args(self, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits, flags):
-        """tcavt_decode_args of a decode step at B rows on the cache `cache` = (k, v, Lmax) or (k_codes, k_scales, v_codes,
-        v_scales, Lmax); scratch buffers come from the workspace under ``tag``; ``who`` names the caller in errors."""
-        from . import capi
-
-        LW, ws, P = self.llama_wrapper, self._ws, self._prepared()
-        ll, PL, dev = LW.shape, LW._prepared(), logits.device
-        H, st = self.llama_hidden_size, LW.storage
-        nqkv = (ll.n_q_heads + 2 * ll.n_kv_heads) * ll.head_dim
-        cos, sin = LW._rope_tables(Lmax, dev)
-        a = capi.DecodeArgs()
-        # fragment-major weight copies for the step's weight streams and, on the 16-bit stream, fragment-major
-        # activations between its kernels (16 or 32 whole rows per buffer); TCAVT_DECODE_ROWMAJOR=1 /
-        # TCAVT_DECODE_ACT_ROWMAJOR=1: the row-major forms (A/B, tests)
-        DW = LW.decode_weights(decode_weights) if (B <= 32 and os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") != "1") else None
-        if DW is None and decode_weights == "fp8":
-            raise ValueError(f"{who}: decode_weights='fp8': this decoder shape has no skinny form "
-                             "(hidden, inter and n_q_heads * head_dim must be multiples of 256, vocab of 16)")
-        # (B <= 8: row-major activation rows are HALF the bytes of a 16-token fragment -- lanes of the empty token slots
-        #  repeat the last row -- and the step is 0.89 vs 0.91 ms; B = 16: 0.98 vs 1.05, B = 32: 1.09 vs 1.21 ms)
-        frag_act = DW is not None and LW.stream16 and os.environ.get("TCAVT_DECODE_ACT_ROWMAJOR", "0") != "1"
-        # up to 8 samples: ONE block of 8 tokens (a k-step of activations = 512 consecutive bytes); blocks of 16 beyond
-        # (TCAVT_DECODE_ACT_FRAG=16: blocks of 16 at any B, A/B)
-        act_mode = 0 if not frag_act else (2 if B <= 8 and os.environ.get("TCAVT_DECODE_ACT_FRAG", "") != "16" else 1)
-        Br = B if not frag_act else (8 if act_mode == 2 else 16 if B <= 16 else 32)
-        bufs = dict(h16=ws.get(f"{tag}.dh16", (Br, H), st, dev, zero=True),
-                    part=ws.get(f"{tag}.dpart", (B, H // 16), torch.float32, dev),
-                    qkv=ws.get(f"{tag}.dqkv", (B, nqkv), st, dev),
-                    att=ws.get(f"{tag}.datt", (Br, ll.n_q_heads * ll.head_dim), st, dev, zero=True),
-                    act=ws.get(f"{tag}.dact", (Br, ll.inter), st, dev, zero=True), t=ws.get(f"{tag}.dt", (B, 64), st, dev, zero=True))
-        if not LW.stream16:
-            bufs["h"] = ws.get(f"{tag}.dh", (B, H), torch.float32, dev)
-        for k_, v_ in bufs.items():
-            setattr(a, k_, v_.data_ptr())
-        a.layers, a.gamma_final = PL.carr, PL.g_final.data_ptr()
-        if DW is not None:
-            a.layers, a.table_packed = DW.carr, DW.table.data_ptr()
-            a.w_layout = capi.W_FRAG8 if decode_weights == "fp8" else capi.W_FRAG16
-        a.act_layout = act_mode
-        a.rope_cos, a.rope_sin, a.rope_L = cos.data_ptr(), sin.data_ptr(), Lmax
-        a.table, a.txt_mod = PL.table.data_ptr(), P.txt.data_ptr()
-        a.cur_tok, a.pos = cur.data_ptr(), pos.data_ptr()
-        if len(cache) == 5:  # the four KV8 planes
-            a.kv8_k_codes, a.kv8_k_scales, a.kv8_v_codes, a.kv8_v_scales = (t_.data_ptr() for t_ in cache[:4])
-            a.kv_lmax = Lmax
-        else:
-            a.k_cache, a.v_cache, a.kv_lmax = cache[0].data_ptr(), cache[1].data_ptr(), Lmax
-        dx16 = ws.get(f"{tag}.dx16", (Br, H), st, dev, zero=True) if frag_act else ws.get(f"{tag}.x16", (B, H), st, dev)
-        a.x16, a.logits, a.bad_id_flag = dx16.data_ptr(), logits.data_ptr(), flags.data_ptr()
-        a.nonfinite_flag = flags[2:3].data_ptr()
-        if LW.use_lora and LW.lora_r <= 8 and os.environ.get("TCAVT_DECODE_LORA_LAUNCH", "0") != "1":  # (A/B switch)
-            a.lora_part, a.lora_rank = ws.get(f"{tag}.lpart", (B * H,), torch.float32, dev).data_ptr(), LW.lora_r
-        # K split across workgroups (tcavt_gemm_args.splitk_ws): off by default -- measured 1.30 vs 1.22 ms per step
-        # at B = 8 and 1.84 vs 1.87 at B = 32 (DESIGN.md section 7: the hand-off costs what the split gains)
-        if os.environ.get("TCAVT_DECODE_SPLITK", "0") == "1":
-            skws = ws.get(f"{tag}.splitk", (9 << 20,), torch.uint8, dev, zero=True)  # tickets zeroed once, slabs behind
-            a.splitk_ws, a.splitk_ws_bytes = skws.data_ptr(), skws.numel()
-        a.n_layers, a.B, a.H, a.I, a.nq, a.nkv, a.V = ll.layers, B, H, ll.inter, ll.n_q_heads, ll.n_kv_heads, ll.vocab
-        a.dtype16 = capi.F16 if st == torch.float16 else capi.BF16
-        a.rms_eps, a.lora_scale = ll.rms_eps, (LW.lora_alpha / LW.lora_r) if LW.use_lora else 0.0
-        a.stream_scale = float(LW.stream_scale)
-        return a
-
     def generate_batch(self, vision_embs_batch, context_str_list=None, max_new_tokens=50, input_ids=None,
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
@@ -1376,152 +1313,18 @@ class LlamaMultiModal(nn.Module, _Prepared):
         ``return_info``: returns (out, info) -- info["finish_reason"] / info["n_generated"]: host int32 [B] (1 EOS, 2 stop token,
         3 stop sequence, 4 ran out at max_new_tokens), info["steps"]: decode steps run.
         Returns int64 [B, max_new_tokens] token ids (pad_token_id after a row's end), or a list of strings with a tokenizer."""
-        from . import capi
-        from .stopping import BUDGET, StopRules
+        out, info = generation.generate_batch(
+            self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
+            top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
+            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every)
+        res = self._generated_texts(out)
+        return (res, info) if return_info else res
 
-        if kv_cache not in ("fp16", "fp8"):  # (before anything touches a device)
-            raise ValueError(f"generate_batch: kv_cache must be 'fp16' or 'fp8', got {kv_cache!r}")
-        rules = StopRules(self.llama_wrapper.shape.vocab, stop_token_ids, stop_sequences, min_new_tokens)
-        if rules.min_new_tokens > 0 and eos_token_id is None and not rules.stop_token_ids:
-            raise ValueError("generate_batch: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
-        if poll_every is not None and int(poll_every) < 1:
-            raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
-        if input_ids is None:
-            if self.tokenizer is None or context_str_list is None:
-                raise NotImplementedError(
-                    "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
-            enc = self.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
-                                 return_tensors="pt")
-            input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
-        dev = vision_embs_batch.device
-        input_ids = input_ids.to(dev).contiguous()
-        attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
-        B, Lt = input_ids.shape
-        LW, ws, P = self.llama_wrapper, self._ws, self._prepared()
-        ll, PL = LW.shape, LW._prepared()
-        H, Nq, N = self.llama_hidden_size, self.qformer.num_query_tokens, int(max_new_tokens)
-        if N < 1:
-            raise ValueError("max_new_tokens must be >= 1")
-        if decode_weights not in ("fp16", "fp8"):
-            raise ValueError(f"generate_batch: decode_weights must be 'fp16' or 'fp8', got {decode_weights!r}")
-        if decode_weights == "fp8":
-            if B > 32:
-                raise ValueError(f"generate_batch: decode_weights='fp8' runs on the skinny decode path only (B <= 32), got B = {B}")
-            if os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") == "1":
-                raise ValueError("generate_batch: decode_weights='fp8' has no row-major form (TCAVT_DECODE_ROWMAJOR=1 is set)")
-        L = Nq + Lt
-        Lmax = L + N
-        nkvw = ll.n_kv_heads * ll.head_dim
-        nqkv = (ll.n_q_heads + 2 * ll.n_kv_heads) * ll.head_dim
-        st = LW.storage
-        i32, i64 = torch.int32, torch.int64
-        with torch.no_grad():
-            was_dctx, LW.dctx, self.qformer.dctx = LW.dctx, None, None  # generation runs eval arithmetic (model.eval() at train.py:581)
-            was_saving, LW.save_for_backward = LW.save_for_backward, False
-            try:
-                # ---- prefill: image tokens + prompt through the decoder, keys / values of every layer into the cache
-                img = self._image_tokens(vision_embs_batch)
-                h = None if LW.stream16 else ws.get("gen.h", (B * L, H), torch.float32, dev)
-                flags = ws.get("mm.flags", (3,), i32, dev, zero=True)
-                h16, part = LW.norm_inputs(B * L, dev)
-                ops.embed_fuse(PL.table, input_ids, img, P.vis, P.txt, h, flags[0:1], h16=h16, part=part, npart=LW.norm_npart(B * L),
-                               stream_scale=LW.stream_scale)
-                kv_len = ws.get("gen.kvlen", (B,), i32, dev)
-                ops.mask_to_kvlen(attention_mask.to(i64).contiguous(), Nq, kv_len, flags[1:2])
-                self._last_flags = flags
-                if kv_cache == "fp8":  # the four KV8 planes; no 16-bit cache exists
-                    kv8 = tuple(ws.get(f"gen.kv8.{nm}", (ll.layers, B, ll.n_kv_heads, Lmax, per), torch.uint8, dev)
-                                for nm, per in (("kc", 64), ("ks", 2), ("vc", 64), ("vs", 2)))
-                    cache = kv8 + (Lmax,)
-                else:
-                    kc = ws.get("gen.kc", (ll.layers, B, Lmax, nkvw), st, dev)
-                    vc = ws.get("gen.vc", (ll.layers, B, Lmax, nkvw), st, dev)
-                    cache = (kc, vc, Lmax)
-                final16 = ws.get("gen.final16", (B * L, H), st, dev)
-                LW.decoder_stack(h, kv_len, B, L, out_bf16=final16, kv_cache=cache, nonfinite_flag=flags[2:3])
-                x16 = ws.get("gen.x16", (B, H), st, dev)
-                ops.gather_last(final16, kv_len, x16, B, L, H)
-                logits = ws.get("gen.logits", (B, ll.vocab), torch.float32, dev)
-                ops.gemm_bf16(x16, PL.table, out=logits)  # lm_head, tied to embed_tokens
-                # ---- device-resident generation state
-                history = torch.zeros(B, Lt + N, dtype=i64, device=dev)
-                history[:, :Lt] = input_ids
-                hist_len = (kv_len - Nq).to(i32)
-                step = torch.zeros(1, dtype=i32, device=dev)
-                cur = torch.zeros(B, dtype=i64, device=dev)
-                pos = kv_len.clone()
-                finished = torch.zeros(B, dtype=i32, device=dev)
-                out = torch.full((B, N), int(pad_token_id), dtype=i64, device=dev)
-                sp = capi.SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k),
-                                       int(no_repeat_ngram_size), int(bool(do_sample)),
-                                       -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id),
-                                       int(seed) & 0xFFFFFFFFFFFFFFFF)
-                # two-stage token selection (B x 16 workgroups + one per sample; TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form, A/B)
-                sws = None
-                if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1":
-                    sws = ws.get("gen.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(B)),), torch.uint8, dev, zero=True)
-                # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
-                drules = None
-                if return_info or not rules.empty:
-                    drules = rules.to(dev).records(B, dev)
-
-                def select(advance_pos):
-                    if drules is None:
-                        ops.sample_logits(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=advance_pos, workspace=sws)
-                    else:
-                        ops.sample_tokens(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=advance_pos,
-                                          workspace=sws, stop=drules)
-
-                select(False)
-                steps_run = 0
-                if N > 1:
-                    a = self._decode_args("gen", "generate_batch", B, Lmax, decode_weights, cache, cur, pos, logits, flags)
-
-                    def one_step():
-                        ops.llama_decode_step(a)
-                        select(True)
-
-                    one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)
-                    steps_run = 1
-                    if N > 2:
-                        graph = None
-                        if use_graph and dev.type == "cuda":
-                            torch.cuda.synchronize()
-                            graph = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(graph):  # capture launches nothing: the N - 2 replays are tokens 3 .. N
-                                one_step()
-                        if poll_every is None:
-                            for _ in range(N - 2):
-                                graph.replay() if graph is not None else one_step()
-                            steps_run = N - 1
-                        else:
-                            # every poll_every steps: the finished flags to pinned host memory, an event wait, and out once every row
-                            # has ended (out was filled with pad and a finished row only ever writes pad: the result is the same)
-                            fin_host = torch.empty(B, dtype=i32).pin_memory() if dev.type == "cuda" else torch.empty(B, dtype=i32)
-                            polled = torch.cuda.Event() if dev.type == "cuda" else None
-                            while steps_run < N - 1:
-                                n_now = min(int(poll_every), N - 1 - steps_run)
-                                for _ in range(n_now):
-                                    graph.replay() if graph is not None else one_step()
-                                steps_run += n_now
-                                fin_host.copy_(finished, non_blocking=True)
-                                if polled is not None:
-                                    polled.record()
-                                    polled.synchronize()
-                                if bool((fin_host != 0).all()):
-                                    break
-                info = None
-                if return_info:
-                    reason, n_gen = drules.finish_reason.cpu(), drules.n_generated.cpu()
-                    ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
-                    reason[ran_out], n_gen[ran_out] = BUDGET, N
-                    info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
-            finally:
-                LW.dctx, LW.save_for_backward = was_dctx, was_saving
-        if self.tokenizer is not None:
-            texts = [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
-            return (texts, info) if return_info else texts
-        return (out, info) if return_info else out
+    def _generated_texts(self, out):
+        """Token ids as they are without a tokenizer; with one, the decoded strings, cut as the reference cuts them."""
+        if self.tokenizer is None:
+            return out
+        return [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
 
     def generate_pool(self, vision_embs, input_ids, attention_mask, max_new_tokens=128, slots=8, poll_every=1, do_sample=True,
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
@@ -1557,245 +1360,11 @@ class LlamaMultiModal(nn.Module, _Prepared):
         With none set the sampler launches are those of a call without.  With rules or ``return_info`` the stats gain
         "finish_reason" / "n_generated": host int32 [R] (1 EOS, 2 stop token, 3 stop sequence, 4 budget); ``return_info`` returns
         (out, stats)."""
-        from . import capi
-        from .pool import SlotScheduler
-        from .stopping import StopRules
-
-        # ---- every illegal value is refused before anything touches a device
-        if kv_cache not in ("fp16", "fp8"):
-            raise ValueError(f"generate_pool: kv_cache must be 'fp16' or 'fp8', got {kv_cache!r}")
-        if decode_weights not in ("fp16", "fp8"):
-            raise ValueError(f"generate_pool: decode_weights must be 'fp16' or 'fp8', got {decode_weights!r}")
-        rules = StopRules(self.llama_wrapper.shape.vocab, stop_token_ids, stop_sequences, min_new_tokens)
-        if rules.min_new_tokens > 0 and eos_token_id is None and not rules.stop_token_ids:
-            raise ValueError("generate_pool: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
-        S, poll_every = int(slots), int(poll_every)
-        if S < 1:
-            raise ValueError(f"generate_pool: slots must be >= 1, got {slots}")
-        if poll_every < 1:
-            raise ValueError(f"generate_pool: poll_every must be >= 1, got {poll_every}")
-        G = int(admit_group)
-        if not 1 <= G <= S:
-            raise ValueError(f"generate_pool: admit_group must be in [1, slots = {S}], got {admit_group}")
-        if input_ids.dim() != 2 or attention_mask.shape != input_ids.shape or vision_embs.shape[0] != input_ids.shape[0]:
-            raise ValueError("generate_pool: vision_embs [R, ...], input_ids [R, Lt] and attention_mask [R, Lt] must agree")
-        R, Lt = input_ids.shape
-        scalar = not hasattr(max_new_tokens, "__len__")
-        budgets = [int(max_new_tokens)] * R if scalar else [int(n) for n in max_new_tokens]
-        if len(budgets) != R:
-            raise ValueError(f"generate_pool: max_new_tokens has {len(budgets)} budgets for {R} requests")
-        if (scalar and int(max_new_tokens) < 1) or any(n < 1 for n in budgets):
-            raise ValueError("generate_pool: every budget in max_new_tokens must be >= 1")
-        Nmax = int(max_new_tokens) if scalar else max(budgets, default=0)
-        LW, ws = self.llama_wrapper, self._ws
-        ll = LW.shape
-        if not 0 <= int(pad_token_id) < ll.vocab:  # (idle and finished slots feed the pad token to the decode step)
-            raise ValueError(f"generate_pool: pad_token_id = {pad_token_id} outside [0, vocab = {ll.vocab})")
-        if decode_weights == "fp8":
-            if S > 32:
-                raise ValueError(f"generate_pool: decode_weights='fp8' runs on the skinny decode path only (slots <= 32), got slots = {S}")
-            if os.environ.get("TCAVT_DECODE_ROWMAJOR", "0") == "1":
-                raise ValueError("generate_pool: decode_weights='fp8' has no row-major form (TCAVT_DECODE_ROWMAJOR=1 is set)")
-        dev = vision_embs.device
-        i32, i64 = torch.int32, torch.int64
-        out = torch.full((R, Nmax), int(pad_token_id), dtype=i64, device=dev)
-        self.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
-        self._pool_flag = None  # (the grouped admission's bad-slot flag: check_flags)
-        if R == 0:
-            if return_info or not rules.empty:
-                self.pool_stats.update(finish_reason=torch.zeros(0, dtype=i32), n_generated=torch.zeros(0, dtype=i32))
-            res = [] if self.tokenizer is not None else out
-            return (res, self.pool_stats) if return_info else res
-        input_ids = input_ids.to(dev).contiguous()
-        mask64 = attention_mask.to(dev).to(i64).contiguous()
-        P, PL = self._prepared(), LW._prepared()
-        H, Nq, st = self.llama_hidden_size, self.qformer.num_query_tokens, LW.storage
-        L = Nq + Lt
-        Lmax = L + Nmax  # 16 + Lt + max budget
-        nkv, nkvw = ll.n_kv_heads, ll.n_kv_heads * ll.head_dim
-        with torch.no_grad():
-            was_dctx, LW.dctx, self.qformer.dctx = LW.dctx, None, None  # eval arithmetic, as generate_batch
-            was_saving, LW.save_for_backward = LW.save_for_backward, False
-            try:
-                flags = ws.get("mm.flags", (3,), i32, dev, zero=True)
-                self._last_flags = flags
-                # ---- the pool: S-slot cache and per-slot state; the one-sample cache a prefill writes (pool.pf.*)
-                if kv_cache == "fp8":
-                    planes = (("kc", 64), ("ks", 2), ("vc", 64), ("vs", 2))
-                    cache = tuple(ws.get(f"pool.kv8.{nm}", (ll.layers, S, nkv, Lmax, per), torch.uint8, dev, zero=True) for nm, per in planes)
-                    pf_cache = tuple(ws.get(f"pool.pf.kv8.{nm}", (ll.layers, 1, nkv, L, per), torch.uint8, dev) for nm, per in planes)
-                    for t_ in cache:
-                        t_[:, :, :, 0].zero_()
-                else:
-                    cache = tuple(ws.get(f"pool.{nm}", (ll.layers, S, Lmax, nkvw), st, dev, zero=True) for nm in ("kc", "vc"))
-                    pf_cache = tuple(ws.get(f"pool.pf.{nm}", (ll.layers, 1, L, nkvw), st, dev) for nm in ("kc", "vc"))
-                    for t_ in cache:
-                        t_[:, :, 0].zero_()
-                # idle state: zeroed cache row 0, pos = 0, finished = 1, cur_tok = pad
-                history = ws.get("pool.history", (S, Lt + Nmax), i64, dev, zero=True)
-                hist_len = ws.get("pool.hist_len", (S,), i32, dev).zero_()
-                step = ws.get("pool.step", (S,), i32, dev).zero_()
-                max_new = ws.get("pool.max_new", (S,), i32, dev).fill_(1)
-                out_row = ws.get("pool.out_row", (S,), i64, dev).zero_()
-                pos = ws.get("pool.pos", (S,), i32, dev).zero_()
-                finished = ws.get("pool.finished", (S,), i32, dev).fill_(1)
-                cur = ws.get("pool.cur", (S,), i64, dev).fill_(int(pad_token_id))
-                logits = ws.get("pool.logits", (S, ll.vocab), torch.float32, dev)
-                logits1 = ws.get("pool.pf.logits", (1, ll.vocab), torch.float32, dev)
-                kv_len = ws.get("pool.pf.kvlen", (1,), i32, dev)
-                final16 = ws.get("pool.pf.final16", (L, H), st, dev)
-                x16 = ws.get("pool.pf.x16", (1, H), st, dev)
-                h = None if LW.stream16 else ws.get("pool.pf.h", (L, H), torch.float32, dev)
-                fin_host = torch.empty(S, dtype=i32).pin_memory() if dev.type == "cuda" else torch.empty(S, dtype=i32)
-                polled = torch.cuda.Event() if dev.type == "cuda" else None
-                sp = capi.SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k),
-                                       int(no_repeat_ngram_size), int(bool(do_sample)),
-                                       -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id),
-                                       int(seed) & 0xFFFFFFFFFFFFFFFF)
-                sws = sws1 = None  # two-stage token selection, as generate_batch (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form)
-                if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1":
-                    sws = ws.get("pool.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(S)),), torch.uint8, dev, zero=True)
-                    sws1 = ws.get("pool.pf.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(1)),), torch.uint8, dev, zero=True)
-                a = self._decode_args("pool", "generate_pool", S, Lmax, decode_weights, cache + (Lmax,), cur, pos, logits, flags)
-                # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
-                drules = None
-                if return_info or not rules.empty:
-                    drules = rules.to(dev).records(R, dev)
-
-                def one_step():
-                    ops.llama_decode_step(a)
-                    if drules is None:
-                        ops.sample_logits_slots(logits, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
-                                                advance_pos=True, workspace=sws)
-                    else:
-                        ops.sample_tokens(logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=True, workspace=sws,
-                                          max_new=max_new, out_row=out_row, stop=drules)
-
-                def admit(s, r):
-                    # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
-                    # and the first token from the one-row logits with the slot's state (views that start at slot s)
-                    img = self._image_tokens(vision_embs[r:r + 1])
-                    h16, part = LW.norm_inputs(L, dev)
-                    ops.embed_fuse(PL.table, input_ids[r:r + 1], img, P.vis, P.txt, h, flags[0:1], h16=h16, part=part,
-                                   npart=LW.norm_npart(L), stream_scale=LW.stream_scale)
-                    ops.mask_to_kvlen(mask64[r:r + 1], Nq, kv_len, flags[1:2])
-                    LW.decoder_stack(h, kv_len, 1, L, out_bf16=final16, kv_cache=pf_cache + (L,), nonfinite_flag=flags[2:3])
-                    ops.slot_admit(pf_cache, cache, s, L, L, Lmax, ll.layers, S, nkv, input_ids[r], kv_len, Nq, budgets[r], r,
-                                   history, hist_len, step, max_new, out_row, pos, finished, cur)
-                    ops.gather_last(final16, kv_len, x16, 1, L, H)
-                    ops.gemm_bf16(x16, PL.table, out=logits1)  # lm_head, tied to embed_tokens
-                    if drules is None:
-                        ops.sample_logits_slots(logits1, history[s:s + 1], hist_len[s:], sp, step[s:], max_new[s:], out_row[s:], cur[s:],
-                                                pos[s:], finished[s:], out, advance_pos=False, workspace=sws1)
-                    else:
-                        ops.sample_tokens(logits1, history[s:s + 1], hist_len[s:s + 1], sp, step[s:s + 1], cur[s:s + 1], pos[s:s + 1],
-                                          finished[s:s + 1], out, advance_pos=False, workspace=sws1, max_new=max_new[s:s + 1],
-                                          out_row=out_row[s:s + 1], stop=drules)
-
-                if G > 1:
-                    # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
-                    # with pad rows (its first request again, slot -1), so M = G * L and with it every kernel form is constant
-                    pg_vis = ws.get("pool.pg.vis", (G,) + tuple(vision_embs.shape[1:]), vision_embs.dtype, dev)
-                    pg_ids = ws.get("pool.pg.ids", (G, Lt), i64, dev)
-                    pg_mask = ws.get("pool.pg.mask", (G, Lt), i64, dev)
-                    pg_slot = ws.get("pool.pg.slot", (G,), i32, dev)
-                    pg_budget = ws.get("pool.pg.budget", (G,), i32, dev)
-                    pg_outrow = ws.get("pool.pg.outrow", (G,), i64, dev)
-                    if kv_cache == "fp8":
-                        pg_cache = tuple(ws.get(f"pool.pg.kv8.{nm}", (ll.layers, G, nkv, L, per), torch.uint8, dev) for nm, per in planes)
-                    else:
-                        pg_cache = tuple(ws.get(f"pool.pg.{nm}", (ll.layers, G, L, nkvw), st, dev) for nm in ("kc", "vc"))
-                    pg_logits = ws.get("pool.pg.logits", (G, ll.vocab), torch.float32, dev)
-                    pg_kvlen = ws.get("pool.pg.kvlen", (G,), i32, dev)
-                    pg_final16 = ws.get("pool.pg.final16", (G * L, H), st, dev)
-                    pg_x16 = ws.get("pool.pg.x16", (G, H), st, dev)
-                    pg_h = None if LW.stream16 else ws.get("pool.pg.h", (G * L, H), torch.float32, dev)
-                    pg_sws = None
-                    if sws is not None:
-                        pg_sws = ws.get("pool.pg.sample_ws", (int(capi.lib().tcavt_sample_workspace_bytes(G)),), torch.uint8, dev, zero=True)
-                    bad_slot = self._pool_flag = ws.get("pool.pg.bad_slot", (1,), i32, dev, zero=True)
-                    vis_all = vision_embs.contiguous()
-                    budgets_dev = torch.tensor(budgets, dtype=i32, device=dev)
-
-                    def stage(group):
-                        # the group's rows of the request list -> the staging buffers (device-side gathers; two small uploads)
-                        reqs = [r for _, r in group] + [group[0][1]] * (G - len(group))
-                        idx = torch.tensor(reqs, dtype=i64, device=dev)
-                        torch.index_select(vis_all, 0, idx, out=pg_vis)
-                        torch.index_select(input_ids, 0, idx, out=pg_ids)
-                        torch.index_select(mask64, 0, idx, out=pg_mask)
-                        torch.index_select(budgets_dev, 0, idx, out=pg_budget)
-                        pg_outrow.copy_(idx)
-                        pg_slot.copy_(torch.tensor([s for s, _ in group] + [-1] * (G - len(group)), dtype=i32, device=dev))
-
-                    def group_pass():
-                        img = self._image_tokens(pg_vis)
-                        h16, part = LW.norm_inputs(G * L, dev)
-                        ops.embed_fuse(PL.table, pg_ids, img, P.vis, P.txt, pg_h, flags[0:1], h16=h16, part=part,
-                                       npart=LW.norm_npart(G * L), stream_scale=LW.stream_scale)
-                        ops.mask_to_kvlen(pg_mask, Nq, pg_kvlen, flags[1:2])
-                        LW.decoder_stack(pg_h, pg_kvlen, G, L, out_bf16=pg_final16, kv_cache=pg_cache + (L,), nonfinite_flag=flags[2:3])
-                        ops.slot_admit_group(pg_cache, cache, pg_slot, L, L, Lmax, ll.layers, S, nkv, pg_ids, pg_kvlen, Nq, pg_budget,
-                                             pg_outrow, bad_slot, history, hist_len, step, max_new, out_row, pos, finished, cur)
-                        ops.gather_last(pg_final16, pg_kvlen, pg_x16, G, L, H)
-                        ops.gemm_bf16(pg_x16, PL.table, out=pg_logits)  # lm_head, tied to embed_tokens
-                        if drules is None:
-                            ops.sample_logits_rows(pg_logits, pg_slot, history, hist_len, sp, step, max_new, out_row, cur, pos, finished, out,
-                                                   advance_pos=False, workspace=pg_sws)
-                        else:
-                            ops.sample_tokens(pg_logits, history, hist_len, sp, step, cur, pos, finished, out, advance_pos=False,
-                                              workspace=pg_sws, max_new=max_new, out_row=out_row, slot_of_row=pg_slot, stop=drules)
-
-                sched, graph, stats = SlotScheduler(R, S, G), None, self.pool_stats
-                pg_graph = None
-                while True:
-                    for group in (sched.admission_groups() if G > 1 else ()):
-                        stage(group)
-                        if not stats["groups"]:
-                            group_pass()  # the first pass runs eagerly: the warm-up of the workspaces and of every kernel form
-                        elif use_graph and dev.type == "cuda":
-                            if pg_graph is None:  # captured once (the capture launches nothing); only the staging buffers change
-                                torch.cuda.synchronize()
-                                pg_graph = torch.cuda.CUDAGraph()
-                                with torch.cuda.graph(pg_graph):
-                                    group_pass()
-                            pg_graph.replay()
-                        else:
-                            group_pass()
-                        stats["groups"].append((tuple(r for _, r in group), tuple(s for s, _ in group), stats["steps"]))
-                        stats["admitted"] += [(r, s, stats["steps"]) for s, r in group]
-                    for s, r in (sched.admissions() if G == 1 else ()):
-                        admit(s, r)
-                        stats["admitted"].append((r, s, stats["steps"]))
-                    if not sched.busy():
-                        break
-                    if stats["steps"] == 0:
-                        # the first step runs eagerly and unpolled, as in generate_batch: it is the warm-up of every kernel form
-                        # the step uses; then the capture (which launches nothing)
-                        one_step()
-                        stats["steps"] = 1
-                        if use_graph and dev.type == "cuda":
-                            torch.cuda.synchronize()
-                            graph = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(graph):
-                                one_step()
-                    for _ in range(poll_every):
-                        graph.replay() if graph is not None else one_step()
-                    stats["steps"] += poll_every
-                    fin_host.copy_(finished, non_blocking=True)
-                    if polled is not None:
-                        polled.record()
-                        polled.synchronize()
-                    n_ret = len(sched.retired)
-                    sched.retire(fin_host.tolist())
-                    stats["retired"] += [(r, s, stats["steps"]) for r, s in sched.retired[n_ret:]]
-                if drules is not None:
-                    stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
-            finally:
-                LW.dctx, LW.save_for_backward = was_dctx, was_saving
-        res = out
-        if self.tokenizer is not None:
-            res = [cut_generated_text(self.tokenizer.decode(row, skip_special_tokens=True)) for row in out.tolist()]
+        out, stats = generation.generate_pool(
+            self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
+            repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
+            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info)
+        res = self._generated_texts(out)
         return (res, stats) if return_info else res
 
 

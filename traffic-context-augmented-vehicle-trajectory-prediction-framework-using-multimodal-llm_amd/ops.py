@@ -1076,18 +1076,27 @@ def sample_workspace(B, device):
     return torch.zeros(int(lib().tcavt_sample_workspace_bytes(int(B))), dtype=torch.uint8, device=device)
 
 
+def _sampler_guard(who, logits, workspace, n, step_n, out_n, history, hist_len, step, cur_tok, pos, finished, out_tokens, slots=None):
+    """Host guard shared by the sampler wrappers: dtype, contiguity and minimal size of the logits, the workspace and the state
+    -- ``n`` entries per state array, ``step_n`` step words, ``out_n`` output ids; slots = (max_new, out_row) in the per-slot forms."""
+    if workspace is not None:
+        _req(workspace, torch.uint8, f"{who}.workspace")
+    _req(logits, torch.float32, f"{who}.logits")
+    per_slot = () if slots is None else ((slots[0], torch.int32, n, "max_new"), (slots[1], torch.int64, n, "out_row"))
+    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), (step, torch.int32, step_n, "step"),
+                         *per_slot, (cur_tok, torch.int64, n, "cur_tok"), (pos, torch.int32, n, "pos"),
+                         (finished, torch.int32, n, "finished"), (out_tokens, torch.int64, out_n, "out_tokens")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+
+
 def sample_logits(logits, history, hist_len, params, step, cur_tok, pos, finished, out_tokens, advance_pos, workspace=None):
     """Logits processors + token selection (tcavt_sample_logits); every tensor is device state that the call advances.
     workspace (sample_workspace(B, device)): the two-stage form -- B x 16 workgroups instead of B; same tokens."""
     B, V = logits.shape
-    if workspace is not None:
-        _req(workspace, torch.uint8, "sample_logits.workspace")
-    _req(logits, torch.float32, "sample_logits.logits")
-    for t, dt, n, nm in ((history, torch.int64, B, "history"), (hist_len, torch.int32, B, "hist_len"), (step, torch.int32, 1, "step"),
-                         (cur_tok, torch.int64, B, "cur_tok"), (pos, torch.int32, B, "pos"), (finished, torch.int32, B, "finished"),
-                         (out_tokens, torch.int64, B, "out_tokens")):
-        _req(t, dt, "sample_logits." + nm)
-        _need(t, n, "sample_logits." + nm)
+    _sampler_guard("sample_logits", logits, workspace, B, 1, B, history, hist_len, step, cur_tok, pos, finished, out_tokens)
     if history.shape[0] != B or out_tokens.shape[0] != B:
         raise capi.TcavtError("sample_logits: history / out_tokens need one row per sample")
     check(lib().tcavt_sample_logits(ptr(logits), B, V, ptr(history), history.shape[1], ptr(hist_len), ctypes.byref(params),
@@ -1102,14 +1111,8 @@ def sample_logits_slots(logits, history, hist_len, params, step, max_new, out_ro
     chooses token step[s] of out_tokens[out_row[s]] (its Philox row too), ends on EOS or at its budget, and is inert once finished.
     The state tensors may be views that start at a slot (one-row logits of a request being admitted)."""
     S, V = logits.shape
-    if workspace is not None:
-        _req(workspace, torch.uint8, "sample_logits_slots.workspace")
-    _req(logits, torch.float32, "sample_logits_slots.logits")
-    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (step, torch.int32, S, "step"),
-                         (max_new, torch.int32, S, "max_new"), (out_row, torch.int64, S, "out_row"), (cur_tok, torch.int64, S, "cur_tok"),
-                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (out_tokens, torch.int64, 1, "out_tokens")):
-        _req(t, dt, "sample_logits_slots." + nm)
-        _need(t, n, "sample_logits_slots." + nm)
+    _sampler_guard("sample_logits_slots", logits, workspace, S, S, 1, history, hist_len, step, cur_tok, pos, finished, out_tokens,
+                   slots=(max_new, out_row))
     if history.dim() != 2 or history.shape[0] != S or out_tokens.dim() != 2:
         raise capi.TcavtError("sample_logits_slots: history needs one row per slot, out_tokens one row per request")
     check(lib().tcavt_sample_logits_slots(ptr(logits), S, V, ptr(history), history.shape[1], ptr(hist_len), ctypes.byref(params),
@@ -1117,6 +1120,37 @@ def sample_logits_slots(logits, history, hist_len, params, step, max_new, out_ro
                                           ptr(out_tokens), out_tokens.shape[1], int(advance_pos), ptr(workspace),
                                           workspace.numel() if workspace is not None else 0, stream_ptr()),
           "tcavt_sample_logits_slots")
+
+
+def _bind_admit(a, who, src, dst, n_src, src_lmax, kv_lmax, n_layers, S, nkv, history, hist_len, step, max_new, out_row, pos, finished,
+                cur_tok):
+    """Into the tcavt_slot_admit[_group]_args ``a``: the caches of the n_src-sample source and of the S-slot pool -- both the
+    16-bit pair or both the four KV8 planes -- and the pool's eight slot-state arrays, each checked first (``who`` in the errors)."""
+    if len(src) != len(dst) or len(src) not in (2, 4):
+        raise capi.TcavtError(f"{who}: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
+    if len(src) == 2:
+        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, n_src), (src[1], "src_v", src_lmax, n_src), (dst[0], "dst_k", kv_lmax, S),
+                               (dst[1], "dst_v", kv_lmax, S)):
+            _req16(t, f"{who}.{nm}", like=src[0])
+            _need(t, n_layers * n * lmax * nkv * 64, f"{who}.{nm}")
+            setattr(a, nm, t.data_ptr())
+        a.dtype16 = _DT[src[0].dtype]
+    else:
+        _kv8_planes(src, n_layers * n_src * nkv * src_lmax, f"{who}.src")
+        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, f"{who}.dst")
+        for side, planes in (("src", src), ("dst", dst)):
+            for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
+                setattr(a, f"{side}_{nm}", t.data_ptr())
+        a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+    for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
+                      (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
+                      (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, S, f"{who}.{nm}")
+        setattr(a, nm, t.data_ptr())
+    if history.dim() != 2 or history.shape[0] != S:
+        raise capi.TcavtError(f"{who}: history needs one row per slot")
+    a.n_layers, a.S, a.src_lmax, a.kv_lmax, a.nkv, a.hist_cap = n_layers, S, src_lmax, kv_lmax, nkv, history.shape[1]
 
 
 def slot_admit(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value, out_row_value,
@@ -1127,35 +1161,13 @@ def slot_admit(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt
     The slot's state: history row = prompt_ids, hist_len = *kv_len - n_image, pos = *kv_len, step = 0, finished = 0, max_new and
     out_row as given; cur_tok is left for the sampler."""
     a = capi.SlotAdmitArgs()
-    if len(src) != len(dst) or len(src) not in (2, 4):
-        raise capi.TcavtError("slot_admit: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
-    if len(src) == 2:
-        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, 1), (src[1], "src_v", src_lmax, 1), (dst[0], "dst_k", kv_lmax, S), (dst[1], "dst_v", kv_lmax, S)):
-            _req16(t, "slot_admit." + nm, like=src[0])
-            _need(t, n_layers * n * lmax * nkv * 64, "slot_admit." + nm)
-            setattr(a, nm, t.data_ptr())
-        a.dtype16 = _DT[src[0].dtype]
-    else:
-        _kv8_planes(src, n_layers * nkv * src_lmax, "slot_admit.src")
-        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, "slot_admit.dst")
-        for side, planes in (("src", src), ("dst", dst)):
-            for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
-                setattr(a, f"{side}_{nm}", t.data_ptr())
-        a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+    _bind_admit(a, "slot_admit", src, dst, 1, src_lmax, kv_lmax, n_layers, S, nkv, history, hist_len, step, max_new, out_row, pos,
+                finished, cur_tok)
     _req(prompt_ids, torch.int64, "slot_admit.prompt_ids")
     _req(kv_len, torch.int32, "slot_admit.kv_len")
     _need(kv_len, 1, "slot_admit.kv_len")
-    for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
-                      (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
-                      (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
-        _req(t, dt, "slot_admit." + nm)
-        _need(t, S, "slot_admit." + nm)
-        setattr(a, nm, t.data_ptr())
-    if history.dim() != 2 or history.shape[0] != S:
-        raise capi.TcavtError("slot_admit: history needs one row per slot")
     a.prompt_ids, a.kv_len = prompt_ids.data_ptr(), kv_len.data_ptr()
-    a.n_layers, a.S, a.slot, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, S, int(slot), int(rows), src_lmax, kv_lmax, nkv
-    a.n_ids, a.hist_cap, a.n_image = prompt_ids.numel(), history.shape[1], int(n_image)
+    a.slot, a.rows, a.n_ids, a.n_image = int(slot), int(rows), prompt_ids.numel(), int(n_image)
     a.max_new_value, a.out_row_value = int(max_new_value), int(out_row_value)
     check(lib().tcavt_slot_admit(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit")
 
@@ -1166,19 +1178,13 @@ def sample_logits_rows(logits, slot_of_row, history, hist_len, params, step, max
     [G] on the device; row g chooses the token of slot slot_of_row[g] of the S-slot state (history [S, cap] and the [S] arrays);
     a row whose entry is negative or >= S is skipped.  workspace: sample_workspace(G, device)."""
     G, V = logits.shape
-    if workspace is not None:
-        _req(workspace, torch.uint8, "sample_logits_rows.workspace")
-    _req(logits, torch.float32, "sample_logits_rows.logits")
     _req(slot_of_row, torch.int32, "sample_logits_rows.slot_of_row")
     _need(slot_of_row, G, "sample_logits_rows.slot_of_row")
     if history.dim() != 2 or out_tokens.dim() != 2:
         raise capi.TcavtError("sample_logits_rows: history needs one row per slot, out_tokens one row per request")
     S = history.shape[0]
-    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (step, torch.int32, S, "step"),
-                         (max_new, torch.int32, S, "max_new"), (out_row, torch.int64, S, "out_row"), (cur_tok, torch.int64, S, "cur_tok"),
-                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (out_tokens, torch.int64, 1, "out_tokens")):
-        _req(t, dt, "sample_logits_rows." + nm)
-        _need(t, n, "sample_logits_rows." + nm)
+    _sampler_guard("sample_logits_rows", logits, workspace, S, S, 1, history, hist_len, step, cur_tok, pos, finished, out_tokens,
+                   slots=(max_new, out_row))
     check(lib().tcavt_sample_logits_rows(ptr(logits), G, V, ptr(slot_of_row), S, ptr(history), history.shape[1], ptr(hist_len),
                                          ctypes.byref(params), ptr(step), ptr(max_new), ptr(out_row), ptr(cur_tok), ptr(pos),
                                          ptr(finished), ptr(out_tokens), out_tokens.shape[1], int(advance_pos), ptr(workspace),
@@ -1192,11 +1198,7 @@ def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finishe
     arguments as in the C entry: slot_of_row -> sample_logits_rows, max_new / out_row -> sample_logits_slots, neither ->
     sample_logits.  stop: a stopping.DeviceStopRules (or a capi.StopRules struct), or None -- then, and with nothing set in it,
     the launches are those of the corresponding existing entry."""
-    who = "sample_tokens."
     rows, V = logits.shape
-    if workspace is not None:
-        _req(workspace, torch.uint8, who + "workspace")
-    _req(logits, torch.float32, who + "logits")
     if history.dim() != 2 or out_tokens.dim() != 2:
         raise capi.TcavtError("sample_tokens: history needs one row per sample / slot, out_tokens one row per sample / request")
     slots = slot_of_row is not None or max_new is not None or out_row is not None
@@ -1204,16 +1206,10 @@ def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finishe
     if history.shape[0] != n or (not slots and out_tokens.shape[0] != rows):
         raise capi.TcavtError("sample_tokens: history / out_tokens need one row per sample")
     if slot_of_row is not None:
-        _req(slot_of_row, torch.int32, who + "slot_of_row")
-        _need(slot_of_row, rows, who + "slot_of_row")
-    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), (step, torch.int32, n if slots else 1, "step"),
-                         (cur_tok, torch.int64, n, "cur_tok"), (pos, torch.int32, n, "pos"), (finished, torch.int32, n, "finished"),
-                         (out_tokens, torch.int64, 1, "out_tokens")) + (
-                             ((max_new, torch.int32, n, "max_new"), (out_row, torch.int64, n, "out_row")) if slots else ()):
-        if t is None:
-            raise capi.TcavtError(f"sample_tokens: {nm} is missing")
-        _req(t, dt, who + nm)
-        _need(t, k, who + nm)
+        _req(slot_of_row, torch.int32, "sample_tokens.slot_of_row")
+        _need(slot_of_row, rows, "sample_tokens.slot_of_row")
+    _sampler_guard("sample_tokens", logits, workspace, n, n if slots else 1, 1, history, hist_len, step, cur_tok, pos, finished,
+                   out_tokens, slots=(max_new, out_row) if slots else None)
     a = capi.SampleArgs()
     a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
     a.params, a.step, a.max_new, a.out_row = ctypes.pointer(params), step.data_ptr(), ptr(max_new), ptr(out_row)
@@ -1233,25 +1229,12 @@ def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, 
     bad_slot_flag int32 [1] set; the slots of a group are distinct), kv_len int32 [G], max_new_value int32 [G], out_row_value int64
     [G], prompt_ids int64 [G, n_ids].  State of an admitted slot as slot_admit."""
     a = capi.SlotAdmitGroupArgs()
-    if len(src) != len(dst) or len(src) not in (2, 4):
-        raise capi.TcavtError("slot_admit_group: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
     _req(slot, torch.int32, "slot_admit_group.slot")
     G = slot.numel()
     if G < 1:
         raise capi.TcavtError("slot_admit_group: slot needs one entry per row of the group")
-    if len(src) == 2:
-        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, G), (src[1], "src_v", src_lmax, G), (dst[0], "dst_k", kv_lmax, S), (dst[1], "dst_v", kv_lmax, S)):
-            _req16(t, "slot_admit_group." + nm, like=src[0])
-            _need(t, n_layers * n * lmax * nkv * 64, "slot_admit_group." + nm)
-            setattr(a, nm, t.data_ptr())
-        a.dtype16 = _DT[src[0].dtype]
-    else:
-        _kv8_planes(src, n_layers * G * nkv * src_lmax, "slot_admit_group.src")
-        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, "slot_admit_group.dst")
-        for side, planes in (("src", src), ("dst", dst)):
-            for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
-                setattr(a, f"{side}_{nm}", t.data_ptr())
-        a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+    _bind_admit(a, "slot_admit_group", src, dst, G, src_lmax, kv_lmax, n_layers, S, nkv, history, hist_len, step, max_new, out_row,
+                pos, finished, cur_tok)
     if prompt_ids.dim() != 2 or prompt_ids.shape[0] != G:
         raise capi.TcavtError("slot_admit_group: prompt_ids needs one row per row of the group")
     for t, dt, n, nm in ((kv_len, torch.int32, G, "kv_len"), (max_new_value, torch.int32, G, "max_new_value"),
@@ -1260,17 +1243,7 @@ def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, 
         _req(t, dt, "slot_admit_group." + nm)
         _need(t, n, "slot_admit_group." + nm)
         setattr(a, nm, t.data_ptr())
-    a.slot = slot.data_ptr()
-    for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
-                      (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
-                      (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
-        _req(t, dt, "slot_admit_group." + nm)
-        _need(t, S, "slot_admit_group." + nm)
-        setattr(a, nm, t.data_ptr())
-    if history.dim() != 2 or history.shape[0] != S:
-        raise capi.TcavtError("slot_admit_group: history needs one row per slot")
-    a.n_layers, a.S, a.G, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, S, G, int(rows), src_lmax, kv_lmax, nkv
-    a.n_ids, a.hist_cap, a.n_image = prompt_ids.shape[1], history.shape[1], int(n_image)
+    a.slot, a.G, a.rows, a.n_ids, a.n_image = slot.data_ptr(), G, int(rows), prompt_ids.shape[1], int(n_image)
     check(lib().tcavt_slot_admit_group(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit_group")
 
 
