@@ -1250,6 +1250,56 @@ typedef struct tcavt_slot_admit_group_args {
 
 int tcavt_slot_admit_group(const tcavt_slot_admit_group_args* args, tcavt_stream_t stream);
 
+/* n continuations per prompt: ONE launch turns a B-sample prefill (what tcavt_llama_stack_forward wrote at B rows, and its first
+ * logits) into the state of a decode batch of B * n rows for tcavt_sample_logits / tcavt_sample_tokens and
+ * tcavt_llama_decode_step.  Destination sample b * n + j (j = 0 .. n - 1) receives source sample b -- the order of
+ * repeat_interleave.  The caches come in ONE of two forms -- all pointers of one form, none of the other's; mixing is refused,
+ * as in tcavt_slot_admit:
+ *   16-bit: src_k / src_v [n_layers][B][src_lmax][nkv * 64]  ->  dst_k / dst_v [n_layers][B * n][kv_lmax][nkv * 64]
+ *   KV8:    the four planes [n_layers][B][nkv][src_lmax][64 | 2]  ->  [n_layers][B * n][nkv][kv_lmax][64 | 2]
+ * Rows 0 .. rows - 1 (a host scalar) of every layer and kv head of every destination sample become the source's rows of its
+ * prompt, byte for byte, and no other byte of the destination is written (rows >= rows, everything outside the planes).  Every
+ * 16-byte piece of the source (the scale planes: every 2-byte piece) is loaded ONCE and stored n times from registers: the
+ * source is read once, where n launches of tcavt_slot_admit_group would read it n times.  The source is not written.
+ *   prompt_ids  int64 [B][n_ids]: the prompt rows (right padded)
+ *   kv_len      int32 [B]: the prefill's kv_len per prompt (n_image + valid prompt tokens)
+ *   logits_src  fp32 [B][V]: the prefill's logits of the first new token;  logits_dst fp32 [B * n][V]
+ * State and first logits, written by trailing workgroups of the same launch, for r = b * n + j:
+ *   history[r][0 .. n_ids) = prompt_ids[b]; hist_len[r] = kv_len[b] - n_image; pos[r] = kv_len[b]; finished[r] = 0;
+ *   logits_dst[r][0 .. V) = logits_src[b][0 .. V), bit for bit (16-byte pieces when V % 4 == 0, else 4-byte pieces).
+ * history[r][n_ids .. hist_cap) is not written.  cur_tok and the one-word step of tcavt_sample_logits belong to the sampler
+ * and are no arguments: with n > 1 a generation adds exactly this launch to its prefill.  n = 1 is a plain copy.
+ * The grid follows from the byte count alone, not from the device.
+ * Refused before the launch (tcavt_last_error names the argument): null or mixed pointers, caches / code planes that are not
+ * 16-byte aligned (scale planes: 2-byte; logits_src / logits_dst: 16-byte), rows outside [1, min(src_lmax, kv_lmax)], B < 1,
+ * n < 1, n_ids outside [0, hist_cap], V < 1, n_image < 0, a non-positive n_layers / nkv / src_lmax / kv_lmax / hist_cap. */
+typedef struct tcavt_kv_fanout_args {
+  const void* src_k;               /* 16-bit form (all four, or none) */
+  const void* src_v;
+  void* dst_k;
+  void* dst_v;
+  const void* src_k_codes;         /* KV8 form (all eight, or none) */
+  const void* src_k_scales;
+  const void* src_v_codes;
+  const void* src_v_scales;
+  void* dst_k_codes;
+  void* dst_k_scales;
+  void* dst_v_codes;
+  void* dst_v_scales;
+  const int64_t* prompt_ids;       /* device int64 [B][n_ids] */
+  const int32_t* kv_len;           /* device int32 [B] */
+  const float* logits_src;         /* device fp32 [B][V] */
+  float* logits_dst;               /* device fp32 [B * n][V] */
+  int64_t* history;                /* int64 [B * n][hist_cap] */
+  int32_t* hist_len;               /* int32 [B * n], as pos and finished */
+  int32_t* pos;
+  int32_t* finished;
+  int32_t n_layers, B, n, rows, src_lmax, kv_lmax, nkv, dtype16;
+  int32_t n_ids, hist_cap, n_image, V;
+} tcavt_kv_fanout_args;
+
+int tcavt_kv_fanout(const tcavt_kv_fanout_args* args, tcavt_stream_t stream);
+
 /* tcavt_sample_logits_slots for the G logits rows of a grouped admission: logits fp32 [G][V]; slot_of_row device int32 [G]; logits
  * row g chooses a token for slot s = slot_of_row[g] of the S-slot state arrays (history [S][hist_cap], hist_len, step, max_new,
  * out_row, cur_tok, pos, finished: all [S]) -- exactly the token tcavt_sample_logits_slots chooses for that logits row and that

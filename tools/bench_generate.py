@@ -22,6 +22,10 @@ ap.add_argument("--greedy", action="store_true")
 ap.add_argument("--preset", default="llama32_1b")
 ap.add_argument("--decode-weights", choices=["fp16", "fp8"], default="fp16", help="what the decode step streams (generate_batch)")
 ap.add_argument("--kv-cache", choices=["fp16", "fp8"], default="fp16", help="what the KV cache holds (generate_batch): 16-bit rows or KV8")
+ap.add_argument("--num-return-sequences", type=int, default=1,
+                help="n > 1: A/B of generate_batch(num_return_sequences=n) on --batch prompts against generate_batch on the prompts "
+                     "repeated to batch * n rows, arms alternating; and the tcavt_kv_fanout launch on its own")
+ap.add_argument("--reps", type=int, default=7, help="timed pairs of the n > 1 A/B")
 args = ap.parse_args()
 capi.init(0)
 dev = torch.device("cuda:0")
@@ -42,6 +46,77 @@ def run(n):
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
 
+
+def nsamples_ab(n):
+    """(a) the prompts once, n continuations each; (b) the prompts repeated n times (repeat_interleave: the same row order).  Each
+    timed call is a whole generation -- prefill, fan-out or not, args.new tokens -- ending in a device synchronise."""
+    from tcavt_amd import generation, ops
+
+    rep = {k: g[k].repeat_interleave(n, 0).contiguous() for k in ("vision_emb", "input_ids", "attention_mask")}
+    kw_b = dict(kw, input_ids=rep["input_ids"], attention_mask=rep["attention_mask"])
+
+    def arm(which, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if which == "a":
+            out = m.mllm.generate_batch(g["vision_emb"], None, max_new_tokens=new, num_return_sequences=n, **kw)
+        else:
+            out = m.mllm.generate_batch(rep["vision_emb"], None, max_new_tokens=new, **kw_b)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    for which in "ab":  # packed weights, workspaces, every kernel form, the clocks
+        arm(which, 4)
+        arm(which, args.new)
+    times = {"a": [], "b": []}
+    for _ in range(args.reps):
+        for which in "ab":
+            t, out = arm(which, args.new)
+            times[which].append(t * 1e3)
+    m.mllm.check_flags()
+    stat = lambda v: dict(median=round(sorted(v)[len(v) // 2], 2), min=round(min(v), 2), max=round(max(v), 2))
+    # the fan-out launch on its own, on the buffers the last (a) call left in the workspace
+    LW, ws = m.mllm.llama_wrapper, m.mllm._ws
+    ll, Nq, Lt, B = LW.shape, cfg.q_num_query_tokens, args.text_len, args.batch
+    src = generation.cache_buffers(ws, "gen.src", LW, args.kv_cache, B, Nq + Lt, dev)
+    dst = generation.cache_buffers(ws, "gen", LW, args.kv_cache, B * n, Nq + Lt + args.new, dev)
+    lsrc = ws.get("gen.src.logits", (B, ll.vocab), torch.float32, dev)
+    ldst = ws.get("gen.logits", (B * n, ll.vocab), torch.float32, dev)
+    hist = torch.zeros(B * n, Lt + args.new, dtype=torch.int64, device=dev)
+    i32 = lambda: torch.zeros(B * n, dtype=torch.int32, device=dev)
+
+    def fan():
+        ops.kv_fanout(src, dst, n, Nq + Lt, Nq + Lt, Nq + Lt + args.new, ll.layers, ll.n_kv_heads, g["input_ids"],
+                      ws.get("gen.src.kvlen", (B,), torch.int32, dev), Nq, lsrc, ldst, hist, i32(), i32(), i32())
+
+    fan()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    fan_ms = []
+    for _ in range(20):
+        ev[0].record()
+        fan()
+        ev[1].record()
+        ev[1].synchronize()
+        fan_ms.append(ev[0].elapsed_time(ev[1]))
+    row = (66 if args.kv_cache == "fp8" else 2 * ll.head_dim) * ll.n_kv_heads * 2 * ll.layers  # cache bytes of one position
+    rd = B * ((Nq + Lt) * row + 4 * ll.vocab + 8 * Lt)
+    moved = rd * (1 + n)  # read once, written n times
+    fmed = sorted(fan_ms)[len(fan_ms) // 2]
+    print(json.dumps({
+        "workload": f"generate_batch: {B} prompts x {n} continuations, prompt {Nq}+{Lt} tokens (ragged), {args.new} new tokens, "
+                    f"{'greedy' if args.greedy else 'sampling'}, {'eager' if args.no_graph else 'hipGraph replay'}, "
+                    f"decode_weights={args.decode_weights}, kv_cache={args.kv_cache}; {args.reps} alternating pairs",
+        "a_num_return_sequences_ms": stat(times["a"]), "b_repeated_prompts_ms": stat(times["b"]),
+        "a_over_b_median": round(stat(times["a"])["median"] / stat(times["b"])["median"], 4),
+        "fanout_ms": dict(median=round(fmed, 4), min=round(min(fan_ms), 4), max=round(max(fan_ms), 4)),
+        "fanout_bytes_read": rd, "fanout_bytes_moved": moved, "fanout_TBps": round(moved / (fmed * 1e-3) / 1e12, 3),
+        "fanout_frac_of_6.29TBps_copy": round(moved / (fmed * 1e-3) / 6.29e12, 3),
+        "finite": bool(((out >= 0) & (out < ll.vocab)).all().item())}))
+
+
+if args.num_return_sequences > 1:
+    nsamples_ab(args.num_return_sequences)
+    sys.exit(0)
 
 run(4)  # packed weights, workspaces
 run(args.new)  # clocks, graph capture path

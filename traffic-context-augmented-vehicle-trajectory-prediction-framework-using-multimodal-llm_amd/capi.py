@@ -260,6 +260,16 @@ class SlotAdmitGroupArgs(ctypes.Structure):
                                           "n_image", "reserved")]
 
 
+class KvFanoutArgs(ctypes.Structure):
+    """Mirror of ``tcavt_kv_fanout_args`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in (
+        "src_k", "src_v", "dst_k", "dst_v", "src_k_codes", "src_k_scales", "src_v_codes", "src_v_scales", "dst_k_codes",
+        "dst_k_scales", "dst_v_codes", "dst_v_scales", "prompt_ids", "kv_len", "logits_src", "logits_dst", "history", "hist_len",
+        "pos", "finished")] + [(n, ctypes.c_int32) for n in (
+            "n_layers", "B", "n", "rows", "src_lmax", "kv_lmax", "nkv", "dtype16", "n_ids", "hist_cap", "n_image", "V")]
+
+
 class DecodeArgs(ctypes.Structure):
     """Mirror of ``tcavt_decode_args`` (include/tcavt.h)."""
 
@@ -392,6 +402,7 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p],
     "tcavt_slot_admit": [ctypes.POINTER(SlotAdmitArgs), c_void_p],
     "tcavt_slot_admit_group": [ctypes.POINTER(SlotAdmitGroupArgs), c_void_p],
+    "tcavt_kv_fanout": [ctypes.POINTER(KvFanoutArgs), c_void_p],
     "tcavt_sample_logits_rows": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(SampleParams),
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_int64, c_void_p],

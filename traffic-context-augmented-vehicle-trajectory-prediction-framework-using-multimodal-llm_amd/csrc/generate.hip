@@ -494,6 +494,90 @@ __global__ __launch_bounds__(256) void slot_admit_group_kernel(AdmitGroupP a) {
   }
 }
 
+// tcavt_kv_fanout: a B-sample prefill becomes the state of a decode batch of B * n rows, in one launch.  The cache is cut into the
+// segments of slot_admit_group_kernel -- source segment sg = (layer * B + b) * inner + i starts at source row sg * src_lmax -- and
+// destination sample b * n + j of a layer is sample (layer * B + b) * n + j of the whole destination, so copy j of the segment
+// starts at row (((sg / inner) * n + j) * inner + sg % inner) * kv_lmax.  A thread LOADS one 16-byte piece (or one row's two scale
+// bytes, or one 16- or 4-byte piece of a logits row) once and STORES it n times from registers: consecutive lanes hold consecutive
+// pieces on both sides, the n stores of a wave are n runs of up to 1 KiB.  Behind the copying workgroups, workgroup b of the last
+// B writes the state of rows b * n .. b * n + n - 1 (each prompt id read once, stored n times).
+struct FanoutP {
+  const unsigned char* src[4];  // 16-bit: k, v; KV8: k codes, v codes, k scales, v scales
+  unsigned char* dst[4];
+  long pieces;   // 16-byte pieces of a segment: rows * row_bytes / 16
+  long n_wide;   // threads that copy a 16-byte piece: 2 * segs * pieces; behind them (KV8) 2 * segs * rows copy a scale pair,
+  long n_cache;  // and behind those B * log_per copy a piece of a logits row
+  long n_copy;
+  long log_per;  // pieces of a logits row: V / 4 of 16 bytes (log_wide), or V of 4 bytes
+  int segs, inner, B, n, rows, src_lmax, kv_lmax, row_bytes, log_wide, V;
+  const float* logits_src;
+  float* logits_dst;
+  const long* prompt_ids;
+  const int* kv_len;
+  long* history;
+  int *hist_len, *pos, *finished;
+  int n_ids, hist_cap, n_image;
+};
+
+__global__ __launch_bounds__(256) void kv_fanout_kernel(FanoutP a) {
+  const int n = a.n;
+  const long first_state = (long)gridDim.x - a.B;
+  if (blockIdx.x >= first_state) {  // the state of prompt b's n rows (cur_tok and step are the sampler's)
+    const int b = (int)(blockIdx.x - first_state);
+    const long* ids = a.prompt_ids + (long)b * a.n_ids;
+    long* h = a.history + (long)b * n * a.hist_cap;
+    for (int i = threadIdx.x; i < a.n_ids; i += 256) {
+      const long id = ids[i];
+      for (int j = 0; j < n; ++j) h[(long)j * a.hist_cap + i] = id;
+    }
+    const int kl = a.kv_len[b];
+    for (int j = threadIdx.x; j < n; j += 256) {
+      const long r = (long)b * n + j;
+      a.hist_len[r] = kl - a.n_image;
+      a.pos[r] = kl;
+      a.finished[r] = 0;
+    }
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_copy) return;
+  if (i >= a.n_cache) {  // first logits: piece e of source row b -> rows b * n .. b * n + n - 1
+    const long r = i - a.n_cache;
+    const long b = r / a.log_per, e = r - b * a.log_per;
+    const float* s = a.logits_src + b * a.V;
+    float* d = a.logits_dst + b * n * a.V;
+    if (a.log_wide) {
+      const u32x4 v = reinterpret_cast<const u32x4*>(s)[e];
+      for (int j = 0; j < n; ++j) reinterpret_cast<u32x4*>(d + (long)j * a.V)[e] = v;
+    } else {
+      const unsigned int v = reinterpret_cast<const unsigned int*>(s)[e];
+      for (int j = 0; j < n; ++j) reinterpret_cast<unsigned int*>(d + (long)j * a.V)[e] = v;
+    }
+    return;
+  }
+  const bool wide = i < a.n_wide;
+  const long t = wide ? i : i - a.n_wide;
+  const long per = wide ? a.pieces : (long)a.rows;  // units of a segment
+  const long per_plane = a.segs * per;
+  const int kv = (int)(t / per_plane);
+  const long r = t - kv * per_plane;
+  const long sg = r / per, e = r - sg * per;
+  const long sample = sg / a.inner, in = sg - sample * a.inner;  // sample = layer * B + b
+  const long srow = sg * a.src_lmax;
+  const long drow = (sample * n * a.inner + in) * a.kv_lmax;  // copy 0; copy j lies j * dstep rows on
+  const long dstep = (long)a.inner * a.kv_lmax;
+  if (wide) {
+    const u32x4 v = reinterpret_cast<const u32x4*>(a.src[kv] + srow * a.row_bytes)[e];
+    u32x4* d = reinterpret_cast<u32x4*>(a.dst[kv] + drow * a.row_bytes) + e;
+    const long step = dstep * a.row_bytes / 16;
+    for (int j = 0; j < n; ++j) d[j * step] = v;
+  } else {
+    const unsigned short v = reinterpret_cast<const unsigned short*>(a.src[2 + kv] + srow * 2)[e];
+    unsigned short* d = reinterpret_cast<unsigned short*>(a.dst[2 + kv] + drow * 2) + e;
+    for (int j = 0; j < n; ++j) d[j * dstep] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Logits processors + token selection, one workgroup per sample (HF generation: RepetitionPenaltyLogitsProcessor,
 // NoRepeatNGramLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, in that order; the warpers
@@ -1562,6 +1646,73 @@ extern "C" int tcavt_slot_admit_group(const tcavt_slot_admit_group_args* a, tcav
   p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image;
   hipLaunchKernelGGL(slot_admit_group_kernel, dim3((unsigned)blocks, (unsigned)a->G), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   TCAVT_CHECK_LAUNCH("slot_admit_group");
+  return TCAVT_OK;
+}
+
+extern "C" int tcavt_kv_fanout(const tcavt_kv_fanout_args* a, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "kv_fanout: args is a null pointer");
+  const bool f16 = a->src_k || a->src_v || a->dst_k || a->dst_v;
+  const bool kv8 = a->src_k_codes || a->src_k_scales || a->src_v_codes || a->src_v_scales || a->dst_k_codes || a->dst_k_scales ||
+                   a->dst_v_codes || a->dst_v_scales;
+  TCAVT_CHECK_ARG(!(f16 && kv8), "kv_fanout: the 16-bit caches (src_k .. dst_v) and the kv8 planes exclude each other");
+  TCAVT_CHECK_ARG(f16 || kv8, "kv_fanout: null pointer (src_k / src_v / dst_k / dst_v, or the eight kv8 planes)");
+  TCAVT_CHECK_ARG(!f16 || (a->src_k && a->src_v && a->dst_k && a->dst_v), "kv_fanout: null pointer: src_k, src_v, dst_k and dst_v come together");
+  TCAVT_CHECK_ARG(!kv8 || (a->src_k_codes && a->src_k_scales && a->src_v_codes && a->src_v_scales && a->dst_k_codes && a->dst_k_scales &&
+                           a->dst_v_codes && a->dst_v_scales),
+                  "kv_fanout: null pointer: the eight kv8 planes come together");
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {a->prompt_ids, "prompt_ids"}, {a->kv_len, "kv_len"}, {a->logits_src, "logits_src"}, {a->logits_dst, "logits_dst"},
+      {a->history, "history"}, {a->hist_len, "hist_len"}, {a->pos, "pos"}, {a->finished, "finished"}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p, "kv_fanout: %s is a null pointer", q.name);
+  TCAVT_CHECK_ARG(is16(a->dtype16), "kv_fanout: dtype16 must be TCAVT_F16 or TCAVT_BF16");
+  TCAVT_CHECK_ARG(a->B >= 1, "kv_fanout: B = %d must be >= 1", a->B);
+  TCAVT_CHECK_ARG(a->n >= 1, "kv_fanout: n = %d must be >= 1", a->n);
+  TCAVT_CHECK_ARG((long)a->B * a->n <= 0x7fffffffL, "kv_fanout: B * n = %ld rows are too many", (long)a->B * a->n);
+  TCAVT_CHECK_ARG(a->n_layers > 0 && a->nkv > 0 && a->src_lmax > 0 && a->kv_lmax > 0,
+                  "kv_fanout: bad shape (n_layers, nkv, src_lmax, kv_lmax > 0)");
+  TCAVT_CHECK_ARG(a->rows >= 1 && a->rows <= std::min(a->src_lmax, a->kv_lmax), "kv_fanout: rows = %d must be in [1, min(src_lmax = %d, kv_lmax = %d)]",
+                  a->rows, a->src_lmax, a->kv_lmax);
+  TCAVT_CHECK_ARG(a->hist_cap > 0 && a->n_ids >= 0 && a->n_ids <= a->hist_cap, "kv_fanout: n_ids = %d must be in [0, hist_cap = %d]", a->n_ids,
+                  a->hist_cap);
+  TCAVT_CHECK_ARG(a->n_image >= 0, "kv_fanout: n_image = %d must be >= 0", a->n_image);
+  TCAVT_CHECK_ARG(a->V >= 1, "kv_fanout: V = %d must be >= 1", a->V);
+  TCAVT_CHECK_ARG(aligned16(a->logits_src) && aligned16(a->logits_dst), "kv_fanout: logits_src and logits_dst must be 16-byte aligned");
+  FanoutP p = {};
+  if (kv8) {
+    TCAVT_CHECK_ARG(aligned16(a->src_k_codes) && aligned16(a->src_v_codes) && aligned16(a->dst_k_codes) && aligned16(a->dst_v_codes),
+                    "kv_fanout: the code planes must be 16-byte aligned");
+    TCAVT_CHECK_ARG(((reinterpret_cast<uintptr_t>(a->src_k_scales) | reinterpret_cast<uintptr_t>(a->src_v_scales) |
+                      reinterpret_cast<uintptr_t>(a->dst_k_scales) | reinterpret_cast<uintptr_t>(a->dst_v_scales)) & 1) == 0,
+                    "kv_fanout: the scale planes must be 2-byte aligned");
+    const void* src[4] = {a->src_k_codes, a->src_v_codes, a->src_k_scales, a->src_v_scales};
+    void* dst[4] = {a->dst_k_codes, a->dst_v_codes, a->dst_k_scales, a->dst_v_scales};
+    for (int i = 0; i < 4; ++i) { p.src[i] = static_cast<const unsigned char*>(src[i]); p.dst[i] = static_cast<unsigned char*>(dst[i]); }
+    p.inner = a->nkv; p.row_bytes = 64;
+  } else {
+    TCAVT_CHECK_ARG(aligned16(a->src_k) && aligned16(a->src_v) && aligned16(a->dst_k) && aligned16(a->dst_v),
+                    "kv_fanout: the caches must be 16-byte aligned");
+    p.src[0] = static_cast<const unsigned char*>(a->src_k); p.src[1] = static_cast<const unsigned char*>(a->src_v);
+    p.dst[0] = static_cast<unsigned char*>(a->dst_k); p.dst[1] = static_cast<unsigned char*>(a->dst_v);
+    p.inner = 1; p.row_bytes = a->nkv * 128;
+  }
+  const long segs = (long)a->n_layers * a->B * p.inner;
+  TCAVT_CHECK_ARG(segs <= 0x7fffffffL, "kv_fanout: n_layers * B * nkv is too large");
+  p.segs = (int)segs;
+  p.B = a->B; p.n = a->n; p.rows = a->rows; p.src_lmax = a->src_lmax; p.kv_lmax = a->kv_lmax; p.V = a->V;
+  p.pieces = (long)a->rows * (p.row_bytes / 16);
+  p.n_wide = 2L * p.segs * p.pieces;
+  p.n_cache = p.n_wide + (kv8 ? 2L * p.segs * a->rows : 0L);
+  p.log_wide = a->V % 4 == 0;  // (every logits row then starts 16-byte aligned)
+  p.log_per = p.log_wide ? a->V / 4 : a->V;
+  p.n_copy = p.n_cache + (long)a->B * p.log_per;
+  const long blocks = (p.n_copy + 255) / 256 + a->B;
+  TCAVT_CHECK_ARG(blocks <= 0x7fffffffL, "kv_fanout: too many rows");
+  p.logits_src = a->logits_src; p.logits_dst = a->logits_dst;
+  p.prompt_ids = reinterpret_cast<const long*>(a->prompt_ids); p.kv_len = a->kv_len; p.history = reinterpret_cast<long*>(a->history);
+  p.hist_len = a->hist_len; p.pos = a->pos; p.finished = a->finished;
+  p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image;
+  hipLaunchKernelGGL(kv_fanout_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  TCAVT_CHECK_LAUNCH("kv_fanout");
   return TCAVT_OK;
 }
 

@@ -12,6 +12,7 @@ one piece per job:
 Workspace names and the order in which they are first requested are part of what tests/test_generation_trace_cpu.py pins;
 ``Prefill.reserve`` exists so that the pool can request a prefill's buffers where that order has them."""
 import contextlib
+import numbers
 import os
 from types import SimpleNamespace
 
@@ -265,13 +266,20 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
 # --------------------------------------------------------------------------------------
 def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
-                   decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every):
-    """-> (out int64 [B, max_new_tokens] on the device, info or None)."""
+                   decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
+                   num_return_sequences=1):
+    """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
+    the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
+    everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument."""
     who = "generate_batch"
     check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
     rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
     if poll_every is not None and int(poll_every) < 1:
         raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
+    n = num_return_sequences
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"generate_batch: num_return_sequences must be an int >= 1, got {num_return_sequences!r}")
+    n = int(n)
     if input_ids is None:
         if mllm.tokenizer is None or context_str_list is None:
             raise NotImplementedError(
@@ -284,21 +292,36 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     if N < 1:
         raise ValueError("max_new_tokens must be >= 1")
     check_format(who, "decode_weights", decode_weights)
-    check_fp8_weights(who, decode_weights, B, "B")
+    src_B, B = B, B * n  # the prefill's rows; from here on B counts decode rows (n continuations per prompt, prompt-major)
+    check_fp8_weights(who, decode_weights, B, "B" if n == 1 else "B * num_return_sequences")
     dev = vision_embs_batch.device
     input_ids = input_ids.to(dev).contiguous()
     attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
-    Lmax = mllm.qformer.num_query_tokens + Lt + N
-    pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev)
+    Nq = mllm.qformer.num_query_tokens
+    Lmax = Nq + Lt + N
+    # n > 1: the prompts alone, into a cache of the prompt's own 16 + Lt rows (the width of the pool's one-sample prefill)
+    pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev) if n == 1 else Prefill(mllm, "gen.src", src_B, Lt, Nq + Lt, kv_cache, dev)
     with eval_arithmetic(mllm):
         # ---- prefill: image tokens + prompt through the decoder, keys / values of every layer into the cache
         logits = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
         kv_len = pf.buf("kvlen")
         # ---- device-resident generation state
         history = torch.zeros(B, Lt + N, dtype=I64, device=dev)
-        history[:, :Lt] = input_ids
-        st = slot_state(history, (kv_len - mllm.qformer.num_query_tokens).to(I32), torch.zeros(1, dtype=I32, device=dev),
-                        torch.zeros(B, dtype=I64, device=dev), kv_len.clone(), torch.zeros(B, dtype=I32, device=dev))
+        if n == 1:
+            cache = pf.buf("cache")
+            history[:, :Lt] = input_ids
+            st = slot_state(history, (kv_len - Nq).to(I32), torch.zeros(1, dtype=I32, device=dev),
+                            torch.zeros(B, dtype=I64, device=dev), kv_len.clone(), torch.zeros(B, dtype=I32, device=dev))
+        else:
+            # one launch: every prompt's cache rows, first logits, history, hist_len, pos and finished to its n decode rows
+            LW = mllm.llama_wrapper
+            cache = cache_buffers(mllm._ws, "gen", LW, kv_cache, B, Lmax, dev)
+            st = slot_state(history, torch.empty(B, dtype=I32, device=dev), torch.zeros(1, dtype=I32, device=dev),
+                            torch.zeros(B, dtype=I64, device=dev), torch.empty(B, dtype=I32, device=dev),
+                            torch.zeros(B, dtype=I32, device=dev))
+            logits_src, logits = logits, mllm._ws.get("gen.logits", (B, LW.shape.vocab), torch.float32, dev)
+            ops.kv_fanout(pf.buf("cache"), cache, n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids, kv_len,
+                          Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
         out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
         sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
                            pad_token_id, seed)
@@ -309,7 +332,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         select(logits, st, sp, out, False, sws, drules)
         steps_run = 0
         if N > 1:
-            a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, pf.buf("cache") + (Lmax,), st.cur, st.pos, logits, pf.flags)
+            a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, pf.flags)
 
             def one_step():
                 ops.llama_decode_step(a)

@@ -1282,7 +1282,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
-                       poll_every=None):
+                       poll_every=None, num_return_sequences=1):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1312,11 +1312,21 @@ class LlamaMultiModal(nn.Module, _Prepared):
         wait) and the loop ends once every row has: same tokens, fewer steps.  None: no host read, all max_new_tokens - 1 steps.
         ``return_info``: returns (out, info) -- info["finish_reason"] / info["n_generated"]: host int32 [B] (1 EOS, 2 stop token,
         3 stop sequence, 4 ran out at max_new_tokens), info["steps"]: decode steps run.
-        Returns int64 [B, max_new_tokens] token ids (pad_token_id after a row's end), or a list of strings with a tokenizer."""
+        ``num_return_sequences`` = n (an int >= 1; anything else raises ValueError): n continuations per prompt from ONE prefill
+        ("n continuations per prompt").  The Q-Former, the embedding, the decoder stack and the lm_head run at
+        B rows into a cache of the prompt's own 16 + Lt rows; one tcavt_kv_fanout launch copies every prompt's cache rows and first
+        logits to its n decode rows and sets their state; token selection and the decode loop then run at B * n rows exactly as
+        above (graph, poll_every, ending rules, return_info).  The result has B * n rows, row b * n + j being continuation j of
+        prompt b -- the order of ``repeat_interleave(n)`` -- and the info arrays have length B * n.  Row b * n + j draws from Philox
+        sample index b * n + j, the index the same row has in a call on the prompts repeated n times.  ``do_sample=False`` with
+        n > 1 is allowed and yields n identical rows per prompt.  ``decode_weights="fp8"`` needs B * n <= 32.  n = 1, the default,
+        is launch for launch the call without the argument.  generate_pool does not take it.
+        Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
+        order with a tokenizer."""
         out, info = generation.generate_batch(
             self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every)
+            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences)
         res = self._generated_texts(out)
         return (res, info) if return_info else res
 

@@ -1122,26 +1122,32 @@ def sample_logits_slots(logits, history, hist_len, params, step, max_new, out_ro
           "tcavt_sample_logits_slots")
 
 
-def _bind_admit(a, who, src, dst, n_src, src_lmax, kv_lmax, n_layers, S, nkv, history, hist_len, step, max_new, out_row, pos, finished,
-                cur_tok):
-    """Into the tcavt_slot_admit[_group]_args ``a``: the caches of the n_src-sample source and of the S-slot pool -- both the
-    16-bit pair or both the four KV8 planes -- and the pool's eight slot-state arrays, each checked first (``who`` in the errors)."""
+def _bind_caches(a, who, src, dst, n_src, n_dst, src_lmax, kv_lmax, n_layers, nkv):
+    """Into the args struct ``a`` (tcavt_slot_admit[_group]_args, tcavt_kv_fanout_args): the caches of the n_src-sample source and
+    of the n_dst-sample destination -- both the 16-bit pair or both the four KV8 planes -- each checked first (``who`` in the errors)."""
     if len(src) != len(dst) or len(src) not in (2, 4):
         raise capi.TcavtError(f"{who}: src and dst are both (k, v) or both (k_codes, k_scales, v_codes, v_scales)")
     if len(src) == 2:
-        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, n_src), (src[1], "src_v", src_lmax, n_src), (dst[0], "dst_k", kv_lmax, S),
-                               (dst[1], "dst_v", kv_lmax, S)):
+        for t, nm, lmax, n in ((src[0], "src_k", src_lmax, n_src), (src[1], "src_v", src_lmax, n_src), (dst[0], "dst_k", kv_lmax, n_dst),
+                               (dst[1], "dst_v", kv_lmax, n_dst)):
             _req16(t, f"{who}.{nm}", like=src[0])
             _need(t, n_layers * n * lmax * nkv * 64, f"{who}.{nm}")
             setattr(a, nm, t.data_ptr())
         a.dtype16 = _DT[src[0].dtype]
     else:
         _kv8_planes(src, n_layers * n_src * nkv * src_lmax, f"{who}.src")
-        _kv8_planes(dst, n_layers * S * nkv * kv_lmax, f"{who}.dst")
+        _kv8_planes(dst, n_layers * n_dst * nkv * kv_lmax, f"{who}.dst")
         for side, planes in (("src", src), ("dst", dst)):
             for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
                 setattr(a, f"{side}_{nm}", t.data_ptr())
         a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
+
+
+def _bind_admit(a, who, src, dst, n_src, src_lmax, kv_lmax, n_layers, S, nkv, history, hist_len, step, max_new, out_row, pos, finished,
+                cur_tok):
+    """Into the tcavt_slot_admit[_group]_args ``a``: the caches of the n_src-sample source and of the S-slot pool (_bind_caches) and
+    the pool's eight slot-state arrays, each checked first (``who`` in the errors)."""
+    _bind_caches(a, who, src, dst, n_src, S, src_lmax, kv_lmax, n_layers, nkv)
     for t, dt, nm in ((history, torch.int64, "history"), (hist_len, torch.int32, "hist_len"), (step, torch.int32, "step"),
                       (max_new, torch.int32, "max_new"), (out_row, torch.int64, "out_row"), (pos, torch.int32, "pos"),
                       (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
@@ -1245,6 +1251,36 @@ def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, 
         setattr(a, nm, t.data_ptr())
     a.slot, a.G, a.rows, a.n_ids, a.n_image = slot.data_ptr(), G, int(rows), prompt_ids.shape[1], int(n_image)
     check(lib().tcavt_slot_admit_group(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit_group")
+
+
+def kv_fanout(src, dst, n, rows, src_lmax, kv_lmax, n_layers, nkv, prompt_ids, kv_len, n_image, logits_src, logits_dst, history,
+              hist_len, pos, finished):
+    """A B-sample prefill becomes the state of a decode batch of B * n rows in one launch (tcavt_kv_fanout): row b * n + j is
+    continuation j of prompt b.  src: the B-sample cache, dst: the cache of B * n samples, both (k, v) 16-bit [n_layers, B | B * n,
+    lmax, nkv * 64] or both the four KV8 planes [n_layers, B | B * n, nkv, lmax, 64 | 2]; rows 0 .. rows - 1 are copied byte for
+    byte, each piece of the source read once.  prompt_ids int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst
+    [B * n, V], history int64 [B * n, cap] (its first n_ids columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0."""
+    who = "kv_fanout"
+    a = capi.KvFanoutArgs()
+    if prompt_ids.dim() != 2 or logits_src.dim() != 2 or logits_dst.dim() != 2 or history.dim() != 2:
+        raise capi.TcavtError(f"{who}: prompt_ids, logits_src, logits_dst and history are 2-D, one row per prompt / per decode row")
+    B, n = prompt_ids.shape[0], int(n)
+    if B < 1 or n < 1:
+        raise capi.TcavtError(f"{who}: B = {B} and n = {n} must be >= 1")
+    R, V = B * n, logits_src.shape[1]
+    if logits_src.shape[0] != B or tuple(logits_dst.shape) != (R, V) or history.shape[0] != R:
+        raise capi.TcavtError(f"{who}: logits_src needs B = {B} rows, logits_dst [{R}, {V}] and history {R} rows")
+    _bind_caches(a, who, src, dst, B, R, src_lmax, kv_lmax, n_layers, nkv)
+    for t, dt, k, nm in ((prompt_ids, torch.int64, B, "prompt_ids"), (kv_len, torch.int32, B, "kv_len"),
+                         (logits_src, torch.float32, B * V, "logits_src"), (logits_dst, torch.float32, R * V, "logits_dst"),
+                         (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"), (pos, torch.int32, R, "pos"),
+                         (finished, torch.int32, R, "finished")):
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+        setattr(a, nm, t.data_ptr())
+    a.n_layers, a.B, a.n, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, B, n, int(rows), src_lmax, kv_lmax, nkv
+    a.n_ids, a.hist_cap, a.n_image, a.V = prompt_ids.shape[1], history.shape[1], int(n_image), V
+    check(lib().tcavt_kv_fanout(ctypes.byref(a), stream_ptr()), "tcavt_kv_fanout")
 
 
 def gather_last(src16, kv_len, out16, B, L, H):
