@@ -1300,6 +1300,27 @@ typedef struct tcavt_kv_fanout_args {
 
 int tcavt_kv_fanout(const tcavt_kv_fanout_args* args, tcavt_stream_t stream);
 
+/* tcavt_kv_fanout without a cache to copy, for a decode batch whose rows read their prompt's cache in place
+ * (tcavt_attn_decode_shared): the trailing state workgroups and the first logits of tcavt_kv_fanout, the same device code, in
+ * one launch.  The fields are the non-cache fields of tcavt_kv_fanout_args under their meaning there; for r = b * n + j:
+ *   history[r][0 .. n_ids) = prompt_ids[b]; hist_len[r] = kv_len[b] - n_image; pos[r] = kv_len[b]; finished[r] = 0;
+ *   logits_dst[r][0 .. V) = logits_src[b][0 .. V), bit for bit (16-byte pieces when V % 4 == 0, else 4-byte pieces).
+ * Nothing else is written.  Refused before the launch (tcavt_last_error names the argument): a null pointer, logits_src /
+ * logits_dst that are not 16-byte aligned, B < 1, n < 1, n_ids outside [0, hist_cap], hist_cap < 1, V < 1, n_image < 0. */
+typedef struct tcavt_state_fanout_args {
+  const int64_t* prompt_ids;       /* device int64 [B][n_ids] */
+  const int32_t* kv_len;           /* device int32 [B] */
+  const float* logits_src;         /* device fp32 [B][V] */
+  float* logits_dst;               /* device fp32 [B * n][V] */
+  int64_t* history;                /* int64 [B * n][hist_cap] */
+  int32_t* hist_len;               /* int32 [B * n], as pos and finished */
+  int32_t* pos;
+  int32_t* finished;
+  int32_t B, n, n_ids, hist_cap, n_image, V;
+} tcavt_state_fanout_args;
+
+int tcavt_state_fanout(const tcavt_state_fanout_args* args, tcavt_stream_t stream);
+
 /* tcavt_sample_logits_slots for the G logits rows of a grouped admission: logits fp32 [G][V]; slot_of_row device int32 [G]; logits
  * row g chooses a token for slot s = slot_of_row[g] of the S-slot state arrays (history [S][hist_cap], hist_len, step, max_new,
  * out_row, cur_tok, pos, finished: all [S]) -- exactly the token tcavt_sample_logits_slots chooses for that logits row and that
@@ -1388,6 +1409,44 @@ int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int
 int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos, void* out, int B, int nq, int nkv,
                       int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
 
+/* tcavt_attn_decode for R = B * n rows, n continuations per prompt (row r = b * n + j), that read their prompt's keys and values
+ * in place: ONE layer, one launch, no workspace.
+ *   qkv        16-bit [R][(nq + 2 nkv) * 64]: q | k | v of the rows' new tokens, already rotated
+ *   prefix_k / prefix_v  const 16-bit [B][prefix_lmax][nkv * 64]: what the prefill wrote; NEVER written here
+ *   prefix_len int32 [B]: rows >= prefix_len[b] (the prefill's pad rows) are never read; values outside [0, prefix_lmax] are clamped
+ *   suffix_k / suffix_v  16-bit [R][suffix_lmax][nkv * 64]: the rows' own generated tokens
+ *   pos        int32 [R]: absolute position.  Row r's suffix slot is t = pos[r] - prefix_len[r / n]; the caller keeps it in
+ *              [0, suffix_lmax - 1] (a value outside is clamped into the range, so that no address leaves the buffers)
+ *   out        16-bit [R][nq * 64] in the three out_layouts of tcavt_attn_decode, with R in the place of its B: 0 row-major,
+ *              1 (R <= 32, nq * 64 % 256 == 0), 2 (R <= 8); token slots >= R are not written
+ * Head dimension 64, nq % nkv == 0, nq / nkv <= 8, TCAVT_F16 or TCAVT_BF16.
+ * Row r, head h attends to prefix rows 0 .. prefix_len[b] - 1, its own suffix rows 0 .. t - 1 and its own new key / value taken
+ * from qkv.  The qkv row's k | v bits are written to suffix row t of every kv head; no other byte of any cache is written, and
+ * no suffix row at or beyond t, no other row's suffix and no prefix row at or beyond prefix_len[b] is read.
+ * A prefix row is fetched once per (prompt, kv head, block of 32 queries) -- the n * (nq / nkv) queries of a prompt's kv head
+ * form blocks of 32, the last one padded -- and goes through the MFMA arithmetic of tcavt_attn_causal_gqa_stream per 32-key
+ * tile (online softmax, probabilities rounded to fp16 relative to the running maximum, fp32 accumulation); the suffix is a VALU
+ * pass per continuation (a key row loaded once for the group's heads, probabilities carried the same way), merged with the
+ * prefix partial by log-sum-exp in fp32.  Scores and sums fp32.  A launch repeats bit for bit.
+ * The suffix pass keeps a round's scores in registers (no score buffer); it is a per-row VALU pass meant for generated tokens, not
+ * for prompts, and the entry accepts suffix_lmax up to TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX.
+ * Refused before the launch (tcavt_last_error names the argument): null pointers, buffers that are not 16-byte aligned (qkv,
+ * the four caches, out), bad shapes, n < 1, prefix_lmax or suffix_lmax < 1, suffix_lmax beyond
+ * TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX, an out_layout beyond its row limit at R. */
+#define TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX 1152
+int tcavt_attn_decode_shared(const void* qkv, const void* prefix_k, const void* prefix_v, const int32_t* prefix_len, void* suffix_k,
+                             void* suffix_v, const int32_t* pos, void* out, int B, int n, int nq, int nkv, int prefix_lmax,
+                             int suffix_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
+
+/* The shared prompt cache of a decode step (tcavt_llama_decode_step_shared): all layers of what the prefill of B / n prompts
+ * wrote, read in place by the n rows of each prompt through tcavt_attn_decode_shared. */
+typedef struct tcavt_kv_prefix {
+  const void* k;                   /* 16-bit [n_layers][B / n][lmax][nkv * 64]; never written */
+  const void* v;
+  const int32_t* len;              /* device int32 [B / n]: valid rows per prompt */
+  int32_t n, lmax;                 /* continuations per prompt; rows per prompt of k / v */
+} tcavt_kv_prefix;
+
 /* ---- "KV8": the opt-in FP8 KV cache of the decode step ------------------------------------------------------------------
  * A cached key or value row of one kv head (64 elements) is stored as the OCP MXFP8-E4M3 image of that row, exactly
  * quant.quantize_mx: 64 e4m3fn codes and 2 E8M0 scale bytes, one per block of 32 along the head dimension (byte = k + 127, k the
@@ -1463,6 +1522,15 @@ typedef struct tcavt_decode_args {
 } tcavt_decode_args;
 
 int tcavt_llama_decode_step(const tcavt_decode_args* args, tcavt_stream_t stream);
+
+/* tcavt_llama_decode_step for B rows that are n continuations of each of B / n prompts whose cache stays where the prefill wrote
+ * it.  args is the struct of tcavt_llama_decode_step, unchanged in layout, read as follows: k_cache / v_cache are the SUFFIX
+ * caches [n_layers][B][kv_lmax][nkv * 64], kv_lmax counting suffix rows; pos stays the absolute position (suffix slot =
+ * pos[r] - prefix->len[r / n]).  Every layer's attention is tcavt_attn_decode_shared; every other launch of the step is that of
+ * tcavt_llama_decode_step.  The prefix is a second argument and no field of tcavt_decode_args, whose layout callers rely on.
+ * Refused before anything is launched, beyond what tcavt_llama_decode_step refuses: a null prefix, k, v or len; the kv8 planes
+ * together with a prefix; n or lmax < 1; B % n != 0; rope_L < lmax + kv_lmax; kv_lmax > TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX. */
+int tcavt_llama_decode_step_shared(const tcavt_decode_args* args, const tcavt_kv_prefix* prefix, tcavt_stream_t stream);
 
 /* Fragment-major copy of a 16-bit weight matrix W [N][ldw] (N % 16 == 0, K % 32 == 0) for the skinny form of tcavt_gemm_bf16
  * (tcavt_gemm_args.w_layout = TCAVT_W_FRAG16): out holds N * K elements; block b (rows 16 b .. 16 b + 15), k-step j (columns

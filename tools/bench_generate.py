@@ -1,6 +1,7 @@
 """Text-generation throughput at the full model size (Llama-3.2-1B shape): prefill + hipGraph-replayed decode steps
 (BASELINE.json configs[4] "hipGraph-captured decode"; reference: scripts/train.py:577-654).  One MI355X.
-    python tools/bench_generate.py [--batch 32] [--new 64] [--text-len 240] [--no-graph] [--greedy] [--decode-weights fp8] [--kv-cache fp8]"""
+    python tools/bench_generate.py [--batch 32] [--new 64] [--text-len 240] [--no-graph] [--greedy] [--decode-weights fp8] [--kv-cache fp8]
+        [--num-return-sequences 8 [--share-prefix]]"""
 import argparse
 import json
 import os
@@ -26,6 +27,9 @@ ap.add_argument("--num-return-sequences", type=int, default=1,
                 help="n > 1: A/B of generate_batch(num_return_sequences=n) on --batch prompts against generate_batch on the prompts "
                      "repeated to batch * n rows, arms alternating; and the tcavt_kv_fanout launch on its own")
 ap.add_argument("--reps", type=int, default=7, help="timed pairs of the n > 1 A/B")
+ap.add_argument("--share-prefix", action="store_true",
+                help="with --num-return-sequences n: A/B of arm (a) num_return_sequences=n against arm (c) = (a) + share_prefix=True, "
+                     "arms alternating in one process; and one layer's attention launch, both kernels, on the buffers the calls left")
 args = ap.parse_args()
 capi.init(0)
 dev = torch.device("cuda:0")
@@ -114,8 +118,83 @@ def nsamples_ab(n):
         "finite": bool(((out >= 0) & (out < ll.vocab)).all().item())}))
 
 
-if args.num_return_sequences > 1:
-    nsamples_ab(args.num_return_sequences)
+def share_prefix_ab(n):
+    """(a) num_return_sequences = n: every decode row owns a copy of its prompt's cache; (c) the same call with share_prefix=True.
+    Each timed call is a whole generation ending in a device synchronise.  Then one layer's decode attention on its own, device
+    events around single launches: tcavt_attn_decode on (a)'s cache, tcavt_attn_decode_shared on (c)'s, at the last step's positions."""
+    from tcavt_amd import generation, ops
+
+    def arm(which, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = m.mllm.generate_batch(g["vision_emb"], None, max_new_tokens=new, num_return_sequences=n, share_prefix=which == "c", **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    for which in "ac":  # packed weights, workspaces, every kernel form, the clocks
+        arm(which, 4)
+        arm(which, args.new)
+    times, outs = {"a": [], "c": []}, {}
+    for _ in range(args.reps):
+        for which in "ac":
+            t, outs[which] = arm(which, args.new)
+            times[which].append(t * 1e3)
+    m.mllm.check_flags()
+    stat = lambda v: dict(median=round(sorted(v)[len(v) // 2], 2), min=round(min(v), 2), max=round(max(v), 2))
+    sa, sc = stat(times["a"]), stat(times["c"])
+    LW, ws = m.mllm.llama_wrapper, m.mllm._ws
+    ll, Nq, Lt, B, N = LW.shape, cfg.q_num_query_tokens, args.text_len, args.batch, args.new
+    R, nq, nkv, st = B * n, ll.n_q_heads, ll.n_kv_heads, LW.storage
+    w = nkv * ll.head_dim
+    kc, vc = generation.cache_buffers(ws, "gen", LW, "fp16", R, Nq + Lt + N, dev)
+    pk, pv = generation.cache_buffers(ws, "gen.src", LW, "fp16", B, Nq + Lt, dev)
+    sk, sv = generation.cache_buffers(ws, "gen.sfx", LW, "fp16", R, max(N - 1, 1), dev)
+    kv_len = ws.get("gen.src.kvlen", (B,), torch.int32, dev)
+    pos = (kv_len.repeat_interleave(n) + (N - 2)).to(torch.int32).contiguous()  # the last decode step
+    qkv = (torch.randn(R, (nq + 2 * nkv) * ll.head_dim, device=dev) * 0.5).to(st)
+    layout = 1 if R <= 32 and (nq * 64) % 256 == 0 else 0
+    att = torch.zeros(32 if layout else R, nq * ll.head_dim, dtype=st, device=dev)
+    scale = ll.head_dim ** -0.5
+    launches = {"unshared": lambda: ops.attn_decode(qkv, kc[0], vc[0], pos, att, R, nq, nkv, Nq + Lt + N, scale, out_layout=layout),
+                "shared": lambda: ops.attn_decode_shared(qkv, pk[0], pv[0], kv_len, sk[0], sv[0], pos, att, B, n, nq, nkv, Nq + Lt,
+                                                         max(N - 1, 1), scale, out_layout=layout)}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    attn = {}
+    for name, fn in launches.items():
+        for _ in range(5):
+            fn()
+        ms = []
+        for _ in range(50):
+            ev[0].record()
+            fn()
+            ev[1].record()
+            ev[1].synchronize()
+            ms.append(ev[0].elapsed_time(ev[1]))
+        attn[name] = sorted(ms)
+    plen = kv_len.cpu().long()
+    row = 2 * w * 2  # bytes of one cached position of one layer: keys + values
+    by = {"unshared": int((plen.repeat_interleave(n) + N - 1).sum()) * row, "shared": (int(plen.sum()) + R * (N - 1)) * row}
+    rep = lambda name: dict(median_us=round(attn[name][25] * 1e3, 2), min_us=round(attn[name][0] * 1e3, 2), max_us=round(attn[name][-1] * 1e3, 2),
+                            cache_bytes=by[name], TBps=round(by[name] / (attn[name][25] * 1e-3) / 1e12, 3))
+    spread_a = round(sa["max"] - sa["min"], 2)
+    print(json.dumps({
+        "workload": f"generate_batch: {B} prompts x {n} continuations, prompt {Nq}+{Lt} tokens (ragged), {N} new tokens, "
+                    f"{'greedy' if args.greedy else 'sampling'}, {'eager' if args.no_graph else 'hipGraph replay'}, "
+                    f"decode_weights={args.decode_weights}; {args.reps} alternating pairs",
+        "a_num_return_sequences_ms": sa, "c_share_prefix_ms": sc, "c_over_a_median": round(sc["median"] / sa["median"], 4),
+        "c_minus_a_median_ms": round(sc["median"] - sa["median"], 2), "a_spread_ms": spread_a,
+        "c_not_slower_than_a_by_more_than_a_spread": bool(sc["median"] - sa["median"] <= spread_a),
+        "per_step_gain_ms": round((sa["median"] - sc["median"]) / max(N - 1, 1), 4),
+        "attention_one_layer_last_step": {k: rep(k) for k in launches},
+        "rows_equal_between_arms": int((outs["a"] == outs["c"]).all(1).sum().item()), "rows": R,
+        "finite": bool(((outs["c"] >= 0) & (outs["c"] < ll.vocab)).all().item())}))
+
+
+if args.num_return_sequences > 1 or args.share_prefix:
+    if args.share_prefix:
+        share_prefix_ab(args.num_return_sequences)
+    else:
+        nsamples_ab(args.num_return_sequences)
     sys.exit(0)
 
 run(4)  # packed weights, workspaces

@@ -270,6 +270,19 @@ class KvFanoutArgs(ctypes.Structure):
             "n_layers", "B", "n", "rows", "src_lmax", "kv_lmax", "nkv", "dtype16", "n_ids", "hist_cap", "n_image", "V")]
 
 
+class StateFanoutArgs(ctypes.Structure):
+    """Mirror of ``tcavt_state_fanout_args`` (include/tcavt.h): the non-cache fields of ``tcavt_kv_fanout_args``."""
+
+    _fields_ = [(n, c_void_p) for n in ("prompt_ids", "kv_len", "logits_src", "logits_dst", "history", "hist_len", "pos", "finished")] + [
+        (n, ctypes.c_int32) for n in ("B", "n", "n_ids", "hist_cap", "n_image", "V")]
+
+
+class KvPrefix(ctypes.Structure):
+    """Mirror of ``tcavt_kv_prefix`` (include/tcavt.h): the shared prompt cache of a decode step."""
+
+    _fields_ = [("k", c_void_p), ("v", c_void_p), ("len", c_void_p), ("n", ctypes.c_int32), ("lmax", ctypes.c_int32)]
+
+
 class DecodeArgs(ctypes.Structure):
     """Mirror of ``tcavt_decode_args`` (include/tcavt.h)."""
 
@@ -403,6 +416,7 @@ _SIGNATURES = {
     "tcavt_slot_admit": [ctypes.POINTER(SlotAdmitArgs), c_void_p],
     "tcavt_slot_admit_group": [ctypes.POINTER(SlotAdmitGroupArgs), c_void_p],
     "tcavt_kv_fanout": [ctypes.POINTER(KvFanoutArgs), c_void_p],
+    "tcavt_state_fanout": [ctypes.POINTER(StateFanoutArgs), c_void_p],
     "tcavt_sample_logits_rows": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(SampleParams),
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_int64, c_void_p],
@@ -411,10 +425,13 @@ _SIGNATURES = {
     "tcavt_gather_last": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "tcavt_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
                           c_void_p],
+    "tcavt_attn_decode_shared": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, c_float, c_int, c_int, c_void_p],
     "tcavt_kv_store8": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tcavt_attn_decode8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                            c_int, c_int, c_void_p],
     "tcavt_llama_decode_step": [ctypes.POINTER(DecodeArgs), c_void_p],
+    "tcavt_llama_decode_step_shared": [ctypes.POINTER(DecodeArgs), ctypes.POINTER(KvPrefix), c_void_p],
     "tcavt_norm_npart": [c_int, c_int, c_int],
     "tcavt_pack_weight16": [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p],
     "tcavt_pack_weight8_bytes": [c_int, c_int],

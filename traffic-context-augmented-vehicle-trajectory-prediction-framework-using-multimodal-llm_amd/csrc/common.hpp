@@ -153,6 +153,31 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- MFMA attention helpers (csrc/attention.hip, csrc/attn_decode_shared.hip) ----
+__device__ __forceinline__ f16x8 cvt8_f16(const float* v) {
+  f16x8 o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = static_cast<_Float16>(v[i]);  // RNE
+  return o;
+}
+
+// the two half-waves' copies of x (lanes l and l ^ 32) in every lane, through v_permlane32_swap (gfx950): a register
+// permute, where __shfl_xor(x, 32) is a ds_bpermute round trip through the LDS crossbar with an lgkmcnt wait
+__device__ __forceinline__ void halves(float x, float& lo, float& hi) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  lo = __uint_as_float(r[0]);
+  hi = __uint_as_float(r[1]);
+}
+
+// two bf16 (same feature, keys r0 and r1) -> packed fp16 pair, clamped to the fp16 range
+__device__ __forceinline__ unsigned int bf16pair_to_f16pair(unsigned int k0_bits, unsigned int k1_bits) {
+  const float a = fminf(fmaxf(__uint_as_float(k0_bits << 16), -65504.f), 65504.f);
+  const float b = fminf(fmaxf(__uint_as_float(k1_bits << 16), -65504.f), 65504.f);
+  const unsigned short ha = __builtin_bit_cast(unsigned short, static_cast<_Float16>(a));
+  const unsigned short hb = __builtin_bit_cast(unsigned short, static_cast<_Float16>(b));
+  return static_cast<unsigned int>(ha) | (static_cast<unsigned int>(hb) << 16);
+}
+
 // csrc-internal forms of tcavt_embed_fuse / tcavt_rmsnorm16 with a layout switch for their 16-bit rows (frag16 != 0: the rows
 // are written / read through frag16_off; B * (Nq + Lt) resp. M <= 32).  The exported entry points call them with 0.
 int embed_fuse_impl(const void* table16, const int64_t* ids, const float* img, const float* vis_mod, const float* txt_mod, float* h,

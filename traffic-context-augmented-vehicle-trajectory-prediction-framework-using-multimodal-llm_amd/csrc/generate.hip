@@ -519,40 +519,50 @@ struct FanoutP {
   int n_ids, hist_cap, n_image;
 };
 
+// The state of prompt b's n rows, by one workgroup (cur_tok and step are the sampler's) ...
+__device__ __forceinline__ void fanout_state(const FanoutP& a, int b) {
+  const int n = a.n;
+  const long* ids = a.prompt_ids + (long)b * a.n_ids;
+  long* h = a.history + (long)b * n * a.hist_cap;
+  for (int i = threadIdx.x; i < a.n_ids; i += 256) {
+    const long id = ids[i];
+    for (int j = 0; j < n; ++j) h[(long)j * a.hist_cap + i] = id;
+  }
+  const int kl = a.kv_len[b];
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const long r = (long)b * n + j;
+    a.hist_len[r] = kl - a.n_image;
+    a.pos[r] = kl;
+    a.finished[r] = 0;
+  }
+}
+
+// ... and the first logits, one thread per piece: piece e of source row b -> rows b * n .. b * n + n - 1
+__device__ __forceinline__ void fanout_logits(const FanoutP& a, long r) {
+  const int n = a.n;
+  const long b = r / a.log_per, e = r - b * a.log_per;
+  const float* s = a.logits_src + b * a.V;
+  float* d = a.logits_dst + b * n * a.V;
+  if (a.log_wide) {
+    const u32x4 v = reinterpret_cast<const u32x4*>(s)[e];
+    for (int j = 0; j < n; ++j) reinterpret_cast<u32x4*>(d + (long)j * a.V)[e] = v;
+  } else {
+    const unsigned int v = reinterpret_cast<const unsigned int*>(s)[e];
+    for (int j = 0; j < n; ++j) reinterpret_cast<unsigned int*>(d + (long)j * a.V)[e] = v;
+  }
+}
+
 __global__ __launch_bounds__(256) void kv_fanout_kernel(FanoutP a) {
   const int n = a.n;
   const long first_state = (long)gridDim.x - a.B;
-  if (blockIdx.x >= first_state) {  // the state of prompt b's n rows (cur_tok and step are the sampler's)
-    const int b = (int)(blockIdx.x - first_state);
-    const long* ids = a.prompt_ids + (long)b * a.n_ids;
-    long* h = a.history + (long)b * n * a.hist_cap;
-    for (int i = threadIdx.x; i < a.n_ids; i += 256) {
-      const long id = ids[i];
-      for (int j = 0; j < n; ++j) h[(long)j * a.hist_cap + i] = id;
-    }
-    const int kl = a.kv_len[b];
-    for (int j = threadIdx.x; j < n; j += 256) {
-      const long r = (long)b * n + j;
-      a.hist_len[r] = kl - a.n_image;
-      a.pos[r] = kl;
-      a.finished[r] = 0;
-    }
+  if (blockIdx.x >= first_state) {
+    fanout_state(a, (int)(blockIdx.x - first_state));
     return;
   }
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n_copy) return;
-  if (i >= a.n_cache) {  // first logits: piece e of source row b -> rows b * n .. b * n + n - 1
-    const long r = i - a.n_cache;
-    const long b = r / a.log_per, e = r - b * a.log_per;
-    const float* s = a.logits_src + b * a.V;
-    float* d = a.logits_dst + b * n * a.V;
-    if (a.log_wide) {
-      const u32x4 v = reinterpret_cast<const u32x4*>(s)[e];
-      for (int j = 0; j < n; ++j) reinterpret_cast<u32x4*>(d + (long)j * a.V)[e] = v;
-    } else {
-      const unsigned int v = reinterpret_cast<const unsigned int*>(s)[e];
-      for (int j = 0; j < n; ++j) reinterpret_cast<unsigned int*>(d + (long)j * a.V)[e] = v;
-    }
+  if (i >= a.n_cache) {
+    fanout_logits(a, i - a.n_cache);
     return;
   }
   const bool wide = i < a.n_wide;
@@ -576,6 +586,17 @@ __global__ __launch_bounds__(256) void kv_fanout_kernel(FanoutP a) {
     unsigned short* d = reinterpret_cast<unsigned short*>(a.dst[2 + kv] + drow * 2) + e;
     for (int j = 0; j < n; ++j) d[j * dstep] = v;
   }
+}
+
+// tcavt_state_fanout: kv_fanout_kernel without a cache to copy (n_cache = 0) -- the logits pieces, and behind them the B state workgroups.
+__global__ __launch_bounds__(256) void state_fanout_kernel(FanoutP a) {
+  const long first_state = (long)gridDim.x - a.B;
+  if (blockIdx.x >= first_state) {
+    fanout_state(a, (int)(blockIdx.x - first_state));
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n_copy) fanout_logits(a, i);
 }
 
 // ---------------------------------------------------------------------------
@@ -1716,7 +1737,38 @@ extern "C" int tcavt_kv_fanout(const tcavt_kv_fanout_args* a, tcavt_stream_t str
   return TCAVT_OK;
 }
 
-extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_t stream) {
+extern "C" int tcavt_state_fanout(const tcavt_state_fanout_args* a, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "state_fanout: args is a null pointer");
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {a->prompt_ids, "prompt_ids"}, {a->kv_len, "kv_len"}, {a->logits_src, "logits_src"}, {a->logits_dst, "logits_dst"},
+      {a->history, "history"}, {a->hist_len, "hist_len"}, {a->pos, "pos"}, {a->finished, "finished"}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p, "state_fanout: %s is a null pointer", q.name);
+  TCAVT_CHECK_ARG(a->B >= 1, "state_fanout: B = %d must be >= 1", a->B);
+  TCAVT_CHECK_ARG(a->n >= 1, "state_fanout: n = %d must be >= 1", a->n);
+  TCAVT_CHECK_ARG((long)a->B * a->n <= 0x7fffffffL, "state_fanout: B * n = %ld rows are too many", (long)a->B * a->n);
+  TCAVT_CHECK_ARG(a->hist_cap > 0 && a->n_ids >= 0 && a->n_ids <= a->hist_cap, "state_fanout: n_ids = %d must be in [0, hist_cap = %d]", a->n_ids,
+                  a->hist_cap);
+  TCAVT_CHECK_ARG(a->n_image >= 0, "state_fanout: n_image = %d must be >= 0", a->n_image);
+  TCAVT_CHECK_ARG(a->V >= 1, "state_fanout: V = %d must be >= 1", a->V);
+  TCAVT_CHECK_ARG(aligned16(a->logits_src) && aligned16(a->logits_dst), "state_fanout: logits_src and logits_dst must be 16-byte aligned");
+  FanoutP p = {};
+  p.B = a->B; p.n = a->n; p.V = a->V;
+  p.log_wide = a->V % 4 == 0;  // (every logits row then starts 16-byte aligned)
+  p.log_per = p.log_wide ? a->V / 4 : a->V;
+  p.n_copy = (long)a->B * p.log_per;
+  const long blocks = (p.n_copy + 255) / 256 + a->B;
+  TCAVT_CHECK_ARG(blocks <= 0x7fffffffL, "state_fanout: too many rows");
+  p.logits_src = a->logits_src; p.logits_dst = a->logits_dst;
+  p.prompt_ids = reinterpret_cast<const long*>(a->prompt_ids); p.kv_len = a->kv_len; p.history = reinterpret_cast<long*>(a->history);
+  p.hist_len = a->hist_len; p.pos = a->pos; p.finished = a->finished;
+  p.n_ids = a->n_ids; p.hist_cap = a->hist_cap; p.n_image = a->n_image;
+  hipLaunchKernelGGL(state_fanout_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  TCAVT_CHECK_LAUNCH("state_fanout");
+  return TCAVT_OK;
+}
+
+// The decode step; px != NULL: the rows read their prompts' cache in place (tcavt_llama_decode_step_shared).
+static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* px, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(a && a->layers && a->gamma_final && a->rope_cos && a->rope_sin && a->table && a->txt_mod && a->cur_tok && a->pos &&
                       a->h16 && a->part && a->qkv && a->att && a->act && a->x16 && a->logits && a->bad_id_flag,
                   "llama_decode_step: null pointer");
@@ -1726,6 +1778,18 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
                   "llama_decode_step: the four kv8 planes come together");
   TCAVT_CHECK_ARG(!kv8 || (!a->k_cache && !a->v_cache), "llama_decode_step: the kv8 planes and k_cache / v_cache exclude each other");
   TCAVT_CHECK_ARG(kv8 || (a->k_cache && a->v_cache), "llama_decode_step: null pointer (k_cache / v_cache, or the four kv8 planes)");
+  // the shared prompt cache (tcavt_attn_decode_shared): k_cache / v_cache then hold the rows' suffixes only
+  if (px) {
+    TCAVT_CHECK_ARG(!kv8, "llama_decode_step: prefix and the kv8 planes exclude each other");
+    TCAVT_CHECK_ARG(px->k && px->v && px->len, "llama_decode_step: prefix: null pointer (k, v, len)");
+    TCAVT_CHECK_ARG(px->n >= 1 && px->lmax >= 1, "llama_decode_step: prefix: n = %d and lmax = %d must be >= 1", px->n, px->lmax);
+    TCAVT_CHECK_ARG(a->B > 0 && a->B % px->n == 0, "llama_decode_step: prefix: B = %d must be a multiple of n = %d", a->B, px->n);
+    TCAVT_CHECK_ARG((long)a->rope_L >= (long)px->lmax + a->kv_lmax, "llama_decode_step: prefix: rope_L = %d must be >= lmax + kv_lmax = %ld",
+                    a->rope_L, (long)px->lmax + a->kv_lmax);
+    TCAVT_CHECK_ARG(a->kv_lmax <= TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX,
+                    "llama_decode_step: prefix: kv_lmax = %d exceeds TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX = %d", a->kv_lmax,
+                    TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX);
+  }
   TCAVT_CHECK_ARG(a->n_layers > 0 && a->B > 0 && a->H % 256 == 0 && a->I > 0 && a->nq > 0 && a->nkv > 0 && a->nq % a->nkv == 0 &&
                       a->nq / a->nkv <= 8 && a->V > 0 && a->V % 16 == 0 && a->kv_lmax > 0 && a->rope_L >= a->kv_lmax && is16(a->dtype16),
                   "llama_decode_step: bad shape (H %% 256, V %% 16, nq / nkv <= 8, rope_L >= kv_lmax)");
@@ -1797,6 +1861,11 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
       TCAVT_TRY(tcavt_attn_decode8(a->qkv, static_cast<unsigned char*>(a->kv8_k_codes) + rows * 64, static_cast<unsigned char*>(a->kv8_k_scales) + rows * 2,
                                    static_cast<unsigned char*>(a->kv8_v_codes) + rows * 64, static_cast<unsigned char*>(a->kv8_v_scales) + rows * 2,
                                    a->pos, a->att, B, nq, nkv, a->kv_lmax, 0.125f, dt, al, stream));
+    } else if (px) {
+      const size_t pre_layer = (size_t)(B / px->n) * px->lmax * nkv * 64;
+      TCAVT_TRY(tcavt_attn_decode_shared(a->qkv, static_cast<const bf16_t*>(px->k) + li * pre_layer, static_cast<const bf16_t*>(px->v) + li * pre_layer,
+                                         px->len, static_cast<bf16_t*>(a->k_cache) + li * per_layer, static_cast<bf16_t*>(a->v_cache) + li * per_layer,
+                                         a->pos, a->att, B / px->n, px->n, nq, nkv, px->lmax, a->kv_lmax, 0.125f, dt, al, stream));
     } else {
       bf16_t* kc = static_cast<bf16_t*>(a->k_cache) + li * per_layer;
       bf16_t* vc = static_cast<bf16_t*>(a->v_cache) + li * per_layer;
@@ -1845,4 +1914,11 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
   g.M = B; g.N = a->V; g.K = H; g.out_dtype = TCAVT_F32; g.in_dtype = dt;
   g.splitk_ws = a->splitk_ws; g.splitk_ws_bytes = a->splitk_ws_bytes;
   return tcavt_gemm_bf16(&g, stream);
+}
+
+extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_t stream) { return decode_step_impl(a, nullptr, stream); }
+
+extern "C" int tcavt_llama_decode_step_shared(const tcavt_decode_args* a, const tcavt_kv_prefix* prefix, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(prefix, "llama_decode_step_shared: prefix is a null pointer");
+  return decode_step_impl(a, prefix, stream);
 }

@@ -201,7 +201,9 @@ class FinishedPoll:
 
 def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits, flags):
     """tcavt_decode_args of a decode step at B rows on the cache `cache` = (k, v, Lmax) or (k_codes, k_scales, v_codes,
-    v_scales, Lmax); scratch buffers come from the workspace under ``tag``; ``who`` names the caller in errors."""
+    v_scales, Lmax); scratch buffers come from the workspace under ``tag``; ``who`` names the caller in errors.
+    On a shared prompt cache (tcavt_llama_decode_step_shared) `cache` = (k, v, rows) is the rows' suffix cache and Lmax still
+    sizes the RoPE tables."""
     LW, ws, P = mllm.llama_wrapper, mllm._ws, mllm._prepared()
     ll, PL, dev = LW.shape, LW._prepared(), logits.device
     H, st = mllm.llama_hidden_size, LW.storage
@@ -243,7 +245,7 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
         a.kv8_k_codes, a.kv8_k_scales, a.kv8_v_codes, a.kv8_v_scales = (t_.data_ptr() for t_ in cache[:4])
         a.kv_lmax = Lmax
     else:
-        a.k_cache, a.v_cache, a.kv_lmax = cache[0].data_ptr(), cache[1].data_ptr(), Lmax
+        a.k_cache, a.v_cache, a.kv_lmax = cache[0].data_ptr(), cache[1].data_ptr(), cache[2]
     dx16 = ws.get(f"{tag}.dx16", (Br, H), st, dev, zero=True) if frag_act else ws.get(f"{tag}.x16", (B, H), st, dev)
     a.x16, a.logits, a.bad_id_flag = dx16.data_ptr(), logits.data_ptr(), flags.data_ptr()
     a.nonfinite_flag = flags[2:3].data_ptr()
@@ -267,12 +269,19 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
 def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
-                   num_return_sequences=1):
+                   num_return_sequences=1, share_prefix=False):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
-    everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument."""
+    everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
+    share_prefix (any n >= 1): the prompts' cache ``gen.src.*`` stays where the prefill wrote it and is read in place by every
+    decode step (tcavt_attn_decode_shared); one tcavt_state_fanout makes the rows' state and first logits, and the decode rows
+    own a suffix cache ``gen.sfx.*`` of their generated tokens alone."""
     who = "generate_batch"
     check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
+    if not isinstance(share_prefix, bool):
+        raise ValueError(f"generate_batch: share_prefix must be a bool, got {share_prefix!r}")
+    if share_prefix and kv_cache == "fp8":
+        raise ValueError("generate_batch: share_prefix=True reads the 16-bit prompt cache in place; kv_cache='fp8' has no shared form")
     rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
     if poll_every is not None and int(poll_every) < 1:
         raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
@@ -300,28 +309,41 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     Nq = mllm.qformer.num_query_tokens
     Lmax = Nq + Lt + N
     # n > 1: the prompts alone, into a cache of the prompt's own 16 + Lt rows (the width of the pool's one-sample prefill)
-    pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev) if n == 1 else Prefill(mllm, "gen.src", src_B, Lt, Nq + Lt, kv_cache, dev)
+    own_cache = n == 1 and not share_prefix  # the prefill writes straight into the decode rows' cache
+    pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev) if own_cache else Prefill(mllm, "gen.src", src_B, Lt, Nq + Lt, kv_cache, dev)
     with eval_arithmetic(mllm):
         # ---- prefill: image tokens + prompt through the decoder, keys / values of every layer into the cache
         logits = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
         kv_len = pf.buf("kvlen")
         # ---- device-resident generation state
         history = torch.zeros(B, Lt + N, dtype=I64, device=dev)
-        if n == 1:
-            cache = pf.buf("cache")
+        prefix = None
+        if own_cache:
+            cache = pf.buf("cache") + (Lmax,)
             history[:, :Lt] = input_ids
             st = slot_state(history, (kv_len - Nq).to(I32), torch.zeros(1, dtype=I32, device=dev),
                             torch.zeros(B, dtype=I64, device=dev), kv_len.clone(), torch.zeros(B, dtype=I32, device=dev))
         else:
             # one launch: every prompt's cache rows, first logits, history, hist_len, pos and finished to its n decode rows
+            # (share_prefix: the state and the first logits alone; the prompts' cache is read where it is, and the rows' own
+            #  cache holds the N - 1 tokens a row can append)
             LW = mllm.llama_wrapper
-            cache = cache_buffers(mllm._ws, "gen", LW, kv_cache, B, Lmax, dev)
+            if share_prefix:
+                sfx_rows = max(N - 1, 1)
+                cache = cache_buffers(mllm._ws, "gen.sfx", LW, "fp16", B, sfx_rows, dev) + (sfx_rows,)
+                pk, pv = pf.buf("cache")
+                prefix = capi.KvPrefix(pk.data_ptr(), pv.data_ptr(), kv_len.data_ptr(), n, Nq + Lt)
+            else:
+                cache = cache_buffers(mllm._ws, "gen", LW, kv_cache, B, Lmax, dev) + (Lmax,)
             st = slot_state(history, torch.empty(B, dtype=I32, device=dev), torch.zeros(1, dtype=I32, device=dev),
                             torch.zeros(B, dtype=I64, device=dev), torch.empty(B, dtype=I32, device=dev),
                             torch.zeros(B, dtype=I32, device=dev))
             logits_src, logits = logits, mllm._ws.get("gen.logits", (B, LW.shape.vocab), torch.float32, dev)
-            ops.kv_fanout(pf.buf("cache"), cache, n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids, kv_len,
-                          Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+            if share_prefix:
+                ops.state_fanout(n, input_ids, kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+            else:
+                ops.kv_fanout(pf.buf("cache"), cache[:-1], n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids,
+                              kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
         out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
         sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
                            pad_token_id, seed)
@@ -332,10 +354,13 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         select(logits, st, sp, out, False, sws, drules)
         steps_run = 0
         if N > 1:
-            a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, pf.flags)
+            a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, cache, st.cur, st.pos, logits, pf.flags)
 
             def one_step():
-                ops.llama_decode_step(a)
+                if prefix is None:
+                    ops.llama_decode_step(a)
+                else:
+                    ops.llama_decode_step_shared(a, prefix)
                 select(logits, st, sp, out, True, sws, drules)
 
             one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)

@@ -1282,7 +1282,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
-                       poll_every=None, num_return_sequences=1):
+                       poll_every=None, num_return_sequences=1, share_prefix=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1321,12 +1321,20 @@ class LlamaMultiModal(nn.Module, _Prepared):
         sample index b * n + j, the index the same row has in a call on the prompts repeated n times.  ``do_sample=False`` with
         n > 1 is allowed and yields n identical rows per prompt.  ``decode_weights="fp8"`` needs B * n <= 32.  n = 1, the default,
         is launch for launch the call without the argument.  generate_pool does not take it.
+        ``share_prefix`` = True (opt-in; a bool, anything else raises ValueError; any n >= 1): the prompts' cache stays where the
+        prefill wrote it (``gen.src.*``, B x (16 + Lt) rows, never written again) and every decode step reads it in place:
+        tcavt_attn_decode_shared fetches a prompt row once per (prompt, kv head, 32 queries) for all n continuations, where the
+        default reads n copies of it once per row and head.  One tcavt_state_fanout sets the rows' state and first logits (no
+        cache copy), and the decode rows own a suffix cache of max_new_tokens - 1 rows (``gen.sfx.*``).  Row order, Philox rows,
+        ending rules, poll_every, return_info, the graph and ``decode_weights`` are as above; the attention's summation order
+        differs from the default's, so tokens can differ where two logits are within rounding of each other.  It needs the 16-bit
+        cache: with ``kv_cache="fp8"`` it raises ValueError.  generate_pool does not take it.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
             self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences)
+            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix)
         res = self._generated_texts(out)
         return (res, info) if return_info else res
 

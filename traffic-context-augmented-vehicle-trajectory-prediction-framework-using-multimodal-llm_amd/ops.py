@@ -1283,6 +1283,31 @@ def kv_fanout(src, dst, n, rows, src_lmax, kv_lmax, n_layers, nkv, prompt_ids, k
     check(lib().tcavt_kv_fanout(ctypes.byref(a), stream_ptr()), "tcavt_kv_fanout")
 
 
+def state_fanout(n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished):
+    """kv_fanout without a cache to copy (tcavt_state_fanout), for decode rows that read their prompt's cache in place: prompt_ids
+    int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst [B * n, V], history int64 [B * n, cap] (its first n_ids
+    columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0 for row b * n + j."""
+    who = "state_fanout"
+    a = capi.StateFanoutArgs()
+    if prompt_ids.dim() != 2 or logits_src.dim() != 2 or logits_dst.dim() != 2 or history.dim() != 2:
+        raise capi.TcavtError(f"{who}: prompt_ids, logits_src, logits_dst and history are 2-D, one row per prompt / per decode row")
+    B, n = prompt_ids.shape[0], int(n)
+    if B < 1 or n < 1:
+        raise capi.TcavtError(f"{who}: B = {B} and n = {n} must be >= 1")
+    R, V = B * n, logits_src.shape[1]
+    if logits_src.shape[0] != B or tuple(logits_dst.shape) != (R, V) or history.shape[0] != R:
+        raise capi.TcavtError(f"{who}: logits_src needs B = {B} rows, logits_dst [{R}, {V}] and history {R} rows")
+    for t, dt, k, nm in ((prompt_ids, torch.int64, B, "prompt_ids"), (kv_len, torch.int32, B, "kv_len"),
+                         (logits_src, torch.float32, B * V, "logits_src"), (logits_dst, torch.float32, R * V, "logits_dst"),
+                         (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"), (pos, torch.int32, R, "pos"),
+                         (finished, torch.int32, R, "finished")):
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+        setattr(a, nm, t.data_ptr())
+    a.B, a.n, a.n_ids, a.hist_cap, a.n_image, a.V = B, n, prompt_ids.shape[1], history.shape[1], int(n_image), V
+    check(lib().tcavt_state_fanout(ctypes.byref(a), stream_ptr()), "tcavt_state_fanout")
+
+
 def gather_last(src16, kv_len, out16, B, L, H):
     _req16(src16, "gather_last.src16")
     _req16(out16, "gather_last.out16", like=src16)
@@ -1308,6 +1333,32 @@ def attn_decode(qkv, k_cache, v_cache, pos, out, B, nq, nkv, kv_lmax, scale, out
     _need(out, rows * nq * 64, "attn_decode.out")
     check(lib().tcavt_attn_decode(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(pos), ptr(out), B, nq, nkv, kv_lmax, scale,
                                   _DT[qkv.dtype], int(out_layout), stream_ptr()), "tcavt_attn_decode")
+
+
+def attn_decode_shared(qkv, prefix_k, prefix_v, prefix_len, suffix_k, suffix_v, pos, out, B, n, nq, nkv, prefix_lmax, suffix_lmax,
+                       scale, out_layout=0):
+    """attn_decode for the B * n rows of n continuations per prompt on ONE layer (tcavt_attn_decode_shared): the prompts' cache
+    prefix_k / prefix_v [B, prefix_lmax, nkv * 64] (rows < prefix_len[b]) is read in place and never written, each row owns
+    suffix_k / suffix_v [B * n, suffix_lmax, nkv * 64]; the qkv row's k | v go to suffix row pos[r] - prefix_len[r // n]."""
+    who = "attn_decode_shared"
+    R = B * n
+    _req16(qkv, f"{who}.qkv")
+    for t, nm in ((prefix_k, "prefix_k"), (prefix_v, "prefix_v"), (suffix_k, "suffix_k"), (suffix_v, "suffix_v"), (out, "out")):
+        _req16(t, f"{who}.{nm}", like=qkv)
+    _req(pos, torch.int32, f"{who}.pos")
+    _req(prefix_len, torch.int32, f"{who}.prefix_len")
+    _need(qkv, R * (nq + 2 * nkv) * 64, f"{who}.qkv")
+    _need(prefix_k, B * prefix_lmax * nkv * 64, f"{who}.prefix_k")
+    _need(prefix_v, B * prefix_lmax * nkv * 64, f"{who}.prefix_v")
+    _need(suffix_k, R * suffix_lmax * nkv * 64, f"{who}.suffix_k")
+    _need(suffix_v, R * suffix_lmax * nkv * 64, f"{who}.suffix_v")
+    _need(prefix_len, B, f"{who}.prefix_len")
+    _need(pos, R, f"{who}.pos")
+    rows = R if out_layout == 0 else 8 if out_layout == 2 else 16 * ((R + 15) // 16)
+    _need(out, rows * nq * 64, f"{who}.out")
+    check(lib().tcavt_attn_decode_shared(ptr(qkv), ptr(prefix_k), ptr(prefix_v), ptr(prefix_len), ptr(suffix_k), ptr(suffix_v), ptr(pos),
+                                         ptr(out), B, n, nq, nkv, prefix_lmax, suffix_lmax, scale, _DT[qkv.dtype], int(out_layout),
+                                         stream_ptr()), "tcavt_attn_decode_shared")
 
 
 def _kv8_planes(planes, rows, what):
@@ -1346,6 +1397,12 @@ def attn_decode8(qkv, k_codes, k_scales, v_codes, v_scales, pos, out, B, nq, nkv
 def llama_decode_step(args):
     """args: capi.DecodeArgs filled by model.LlamaMultiModal.generate_batch (which owns and sizes every buffer)."""
     check(lib().tcavt_llama_decode_step(ctypes.byref(args), stream_ptr()), "tcavt_llama_decode_step")
+
+
+def llama_decode_step_shared(args, prefix):
+    """llama_decode_step for n continuations per prompt on the prompts' cache in place (tcavt_llama_decode_step_shared).  prefix:
+    capi.KvPrefix; args.k_cache / v_cache are the suffix caches and args.kv_lmax counts their rows."""
+    check(lib().tcavt_llama_decode_step_shared(ctypes.byref(args), ctypes.byref(prefix), stream_ptr()), "tcavt_llama_decode_step_shared")
 
 
 def tlayer_stack_forward(args):
