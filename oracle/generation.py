@@ -68,17 +68,19 @@ def greedy_generate(W, cfg, vision, input_ids, attention_mask, max_new_tokens, c
 # logits processors + selection, as csrc/generate.hip (sample_kernel) computes them
 # ---------------------------------------------------------------------------------------------
 def process_logits(scores, history, repetition_penalty=1.2, no_repeat_ngram_size=3):
-    """RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on one row (numpy fp32, returns a copy)."""
+    """RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on one row (numpy fp32, returns a copy).  An id outside
+    [0, V) is neither penalised nor banned, as in the kernel."""
     x = np.array(scores, dtype=np.float32, copy=True)
     hist = [int(t) for t in history]
     if repetition_penalty != 1.0:
         for t in sorted(set(hist)):
-            x[t] = x[t] * np.float32(repetition_penalty) if x[t] < 0 else x[t] / np.float32(repetition_penalty)
+            if 0 <= t < x.size:
+                x[t] = x[t] * np.float32(repetition_penalty) if x[t] < 0 else x[t] / np.float32(repetition_penalty)
     n = no_repeat_ngram_size
     if n > 0 and len(hist) + 1 >= n:
         tail = hist[len(hist) - (n - 1):] if n > 1 else []
         for i in range(len(hist) - n + 1):
-            if hist[i:i + n - 1] == tail:
+            if hist[i:i + n - 1] == tail and 0 <= hist[i + n - 1] < x.size:
                 x[hist[i + n - 1]] = -np.inf
     return x
 
@@ -119,6 +121,8 @@ def select_token(x, do_sample, temperature=0.9, top_k=40, top_p=0.9, seed=0, ste
     kernel's Philox uniform of (seed, step, row)."""
     if not do_sample:
         return int(np.argmax(x))
+    if not np.isfinite(x).any():
+        return 0  # no finite score: the kernel has no candidate and emits token 0
     keep, w = warp_candidates(x, temperature, top_k, top_p)
     kt = np.float32(0)
     for e in w:

@@ -738,7 +738,14 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
   if (do_ban) {
     for (int i = tid; i + ng - 1 < hl; i += SMP_T) {
       bool match = true;
-      for (int k = 0; k < ng - 1 && match; ++k) match = tok_at(i + k) == tok_at(hl - (ng - 1) + k);
+      for (int k = 0; k < ng - 1 && match; ++k) {
+        const int p = i + k, q = hl - (ng - 1) + k;
+        const long a = tok_at(p);
+        match = a == tok_at(q);
+        // (the LDS copy folds every id below 0 onto -1 and every id from 2^31 - 1 up onto 2^31 - 1: two of those are equal only
+        //  if the ids themselves are, as in the one-stage form)
+        if (match && in_lds && (a == -1L || a == 0x7fffffffL)) match = hist[p] == hist[q];
+      }
       const long t = tok_at(i + ng - 1);
       if (match && t >= lo && t < hi) x[t] = -INFINITY;
     }
