@@ -1394,6 +1394,53 @@ typedef struct tcavt_sample_args {
 
 int tcavt_sample_tokens(const tcavt_sample_args* args, tcavt_stream_t stream);
 
+/* Log-probabilities of the generated tokens.  For every token that a LIVE row emits (finished == 0 before the selection; in the
+ * rows form its map entry in range), the ending token (EOS / stop token) included:
+ *     logprob = log_softmax(raw)[token]
+ * where raw is the fp32 logits row exactly as the lm_head wrote it -- BEFORE the repetition penalty, the n-gram ban, the
+ * min_new_tokens ban, the temperature and top-k / top-p: the model's distribution, independent of the sampling arguments (HF:
+ * output_logits=True followed by log_softmax(...).gather(token)).  Two launches bracket ONE call of any token-selection entry
+ * (tcavt_sample_logits / _slots / _rows / tcavt_sample_tokens) on the same logits and state, stream-ordered:
+ *   tcavt_logprob_begin   before the selection: rows x 16 workgroups reduce the slices of every live row to (max, sum exp(x - max))
+ *                         and record in the workspace whether the row was live, its step word, its hist_len and the raw logits at
+ *                         its history ids (the elements the repetition penalty rewrites in place).  logits is only read.
+ *   tcavt_logprob_finish  after the selection: per row, the 16 partials in slice order, the chosen token from
+ *                         out_tokens[row * out_cap + step_before], its raw logit (from the snapshot when the token occurs in the
+ *                         recorded history, else from the row), and
+ *                             token_logprobs[row * out_cap + step_before] = (x_tok - M) - log S     (fp32, indexed like out_tokens)
+ *                             sum_logprob[row] += that value                                        (fp32, in step order)
+ *                             n_scored[row]    += 1                                                 (int32)
+ * Inert, finished and skipped rows write none of the three; the caller initialises them (0.0 / 0).
+ * Indexing follows the selection entries: slot_of_row != NULL: the rows form (logits row g scores slot slot_of_row[g] of n_state
+ * slots; entries < 0 or >= n_state are skipped; out_row required); else out_row != NULL: the slots form (step is [rows]); else the
+ * batch form (step is one word, row = the sample).  In the slots and rows forms `row` above is out_row[s], so a request's record
+ * outlives its slot.  A row's three results are bit-identical whatever logits row, slot or partner rows it runs with: the
+ * summation order depends on V alone and no atomics are used.
+ * workspace: tcavt_logprob_workspace_bytes(rows, hist_cap) bytes (0 for rows <= 0), 16-byte aligned, no initial contents needed;
+ * the pair of calls owns it from begin to finish.  Both entries are capturable and read nothing on the host.
+ * Refused before any launch (tcavt_last_error names the argument): a null pointer (slot_of_row optional; out_row optional without
+ * it); rows, V, hist_cap or out_cap <= 0; slot_of_row with n_state <= 0; a workspace that is too small or not 16-byte aligned. */
+typedef struct tcavt_logprob_args {
+  const float* logits;               /* fp32 [rows][V]; never written */
+  const int32_t* slot_of_row;        /* rows form: device int32 [rows]; else NULL */
+  const int64_t* history;
+  const int32_t* hist_len;
+  const int32_t* step;
+  const int64_t* out_row;            /* slots / rows forms; else NULL */
+  const int32_t* finished;
+  const int64_t* out_tokens;
+  float* token_logprobs;
+  float* sum_logprob;
+  int32_t* n_scored;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t rows, V, n_state, hist_cap, out_cap;
+} tcavt_logprob_args;
+
+int64_t tcavt_logprob_workspace_bytes(int rows, int hist_cap);
+int tcavt_logprob_begin(const tcavt_logprob_args* args, tcavt_stream_t stream);
+int tcavt_logprob_finish(const tcavt_logprob_args* args, tcavt_stream_t stream);
+
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 

@@ -1,7 +1,7 @@
 """Text-generation throughput at the full model size (Llama-3.2-1B shape): prefill + hipGraph-replayed decode steps
 (BASELINE.json configs[4] "hipGraph-captured decode"; reference: scripts/train.py:577-654).  One MI355X.
     python tools/bench_generate.py [--batch 32] [--new 64] [--text-len 240] [--no-graph] [--greedy] [--decode-weights fp8] [--kv-cache fp8]
-        [--num-return-sequences 8 [--share-prefix]]"""
+        [--num-return-sequences 8 [--share-prefix]] [--logprobs]"""
 import argparse
 import json
 import os
@@ -30,6 +30,9 @@ ap.add_argument("--reps", type=int, default=7, help="timed pairs of the n > 1 A/
 ap.add_argument("--share-prefix", action="store_true",
                 help="with --num-return-sequences n: A/B of arm (a) num_return_sequences=n against arm (c) = (a) + share_prefix=True, "
                      "arms alternating in one process; and one layer's attention launch, both kernels, on the buffers the calls left")
+ap.add_argument("--logprobs", action="store_true",
+                help="A/B of generate_batch(return_logprobs=True) against the call without it, arms alternating in one process: "
+                     "ms per decode step of each arm (the two launches of the bracket and one more read of the logits)")
 args = ap.parse_args()
 capi.init(0)
 dev = torch.device("cuda:0")
@@ -189,6 +192,50 @@ def share_prefix_ab(n):
         "rows_equal_between_arms": int((outs["a"] == outs["c"]).all(1).sum().item()), "rows": R,
         "finite": bool(((outs["c"] >= 0) & (outs["c"] < ll.vocab)).all().item())}))
 
+
+def logprobs_ab():
+    """Arm "off": the call as it is; arm "on": the same call with return_logprobs=True.  A timed call is a whole generation ending
+    in a device synchronise; ms per decode step = (time of args.new tokens - time of 1 token) / (args.new - 1), per pair."""
+    def arm(flag, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = m.mllm.generate_batch(g["vision_emb"], None, max_new_tokens=new, return_logprobs=flag, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res
+
+    for flag in (False, True):  # packed weights, workspaces, every kernel form, the clocks
+        arm(flag, 4)
+        arm(flag, args.new)
+    step, first, last = {False: [], True: []}, {False: [], True: []}, {}
+    for _ in range(args.reps):
+        for flag in (False, True):
+            t1, _ = arm(flag, 1)
+            tn, last[flag] = arm(flag, args.new)
+            step[flag].append((tn - t1) / max(args.new - 1, 1) * 1e3)
+            first[flag].append(t1 * 1e3)
+    m.mllm.check_flags()
+    stat = lambda v: dict(median=round(sorted(v)[len(v) // 2], 4), min=round(min(v), 4), max=round(max(v), 4))
+    off, on = stat(step[False]), stat(step[True])
+    out, info = last[True]
+    ll = cfg.llama
+    print(json.dumps({
+        "workload": f"generate_batch: B={args.batch}, prompt {cfg.q_num_query_tokens}+{args.text_len} tokens (ragged), {args.new} new tokens, "
+                    f"{'greedy' if args.greedy else 'sampling'}, {'eager' if args.no_graph else 'hipGraph replay'}, "
+                    f"decode_weights={args.decode_weights}, kv_cache={args.kv_cache}; {args.reps} alternating pairs",
+        "off_decode_ms_per_step": off, "on_decode_ms_per_step": on,
+        "on_minus_off_us_per_step": round((on["median"] - off["median"]) * 1e3, 2), "off_spread_us": round((off["max"] - off["min"]) * 1e3, 2),
+        "on_over_off_median": round(on["median"] / off["median"], 4),
+        "off_prefill_plus_first_token_ms": stat(first[False]), "on_prefill_plus_first_token_ms": stat(first[True]),
+        "logits_bytes_read_again_per_step": 4 * ll.vocab * args.batch,
+        "tokens_equal_between_arms": bool(torch.equal(out, last[False])),
+        "n_scored_all_new": bool((info["n_scored"] == args.new).all().item()),
+        "mean_logprob_per_token": round(float((info["sum_logprob"] / info["n_scored"]).mean()), 4),
+        "finite": bool(torch.isfinite(info["token_logprobs"]).all().item() and ((out >= 0) & (out < ll.vocab)).all().item())}))
+
+
+if args.logprobs:
+    logprobs_ab()
+    sys.exit(0)
 
 if args.num_return_sequences > 1 or args.share_prefix:
     if args.share_prefix:

@@ -239,6 +239,14 @@ class SampleArgs(ctypes.Structure):
                     "rows", "V", "n_state", "hist_cap", "out_cap", "advance_pos")]
 
 
+class LogprobArgs(ctypes.Structure):
+    """Mirror of ``tcavt_logprob_args`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("logits", "slot_of_row", "history", "hist_len", "step", "out_row", "finished", "out_tokens",
+                                        "token_logprobs", "sum_logprob", "n_scored", "workspace")] + [
+        ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "V", "n_state", "hist_cap", "out_cap")]
+
+
 class SlotAdmitArgs(ctypes.Structure):
     """Mirror of ``tcavt_slot_admit_args`` (include/tcavt.h)."""
 
@@ -460,9 +468,12 @@ _SIGNATURES = {
     "tcavt_lm_eval": [ctypes.POINTER(LmEvalArgs), c_void_p],
     "tcavt_quant_mx8": [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p],
     "tcavt_gemm_mx8": [ctypes.POINTER(GemmMx8Args), c_void_p],
+    "tcavt_logprob_workspace_bytes": [c_int, c_int],
+    "tcavt_logprob_begin": [ctypes.POINTER(LogprobArgs), c_void_p],
+    "tcavt_logprob_finish": [ctypes.POINTER(LogprobArgs), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
-             "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64}
+             "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -4,6 +4,8 @@ one piece per job:
 
   Prefill          image tokens + prompt through the decoder into a KV cache, last rows through the lm_head -> first logits
   select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens)
+  LogprobRecord    return_logprobs: the three score tensors and the tcavt_logprob_begin / _finish bracket that select puts around
+                   the sampler entry; rank_continuations orders a prompt's n continuations by them (host only)
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
   FinishedPoll     the finished flags to pinned host memory and an event wait
   decode_args      the tcavt_decode_args of the decode step
@@ -153,10 +155,61 @@ def slot_view(st, s):
     return slot_state(*(t[s:s + 1] for t in (st.history, st.hist_len, st.step, st.cur, st.pos, st.finished, st.max_new, st.out_row)))
 
 
-def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None):
+def check_bool(who, name, value):
+    if not isinstance(value, bool):
+        raise ValueError(f"{who}: {name} must be a bool, got {value!r}")
+
+
+class LogprobRecord:
+    """The scores of return_logprobs: device tensors indexed like ``out`` (token_logprobs fp32 [rows, N] filled with 0.0, as out
+    is with the pad id; sum_logprob fp32 [rows]; n_scored int32 [rows]) and the workspaces of the tcavt_logprob_begin / _finish
+    bracket, one per logits shape, under ``{tag}.lp.ws`` -- new names, requested only with the flag."""
+
+    def __init__(self, ws, out):
+        rows, dev = out.shape[0], out.device
+        self.ws, self.out = ws, out
+        self.token_logprobs = torch.zeros(out.shape, dtype=torch.float32, device=dev)
+        self.sum_logprob = torch.zeros(rows, dtype=torch.float32, device=dev)
+        self.n_scored = torch.zeros(rows, dtype=I32, device=dev)
+
+    def reserve(self, tag, rows, hist_cap):
+        """The bracket's workspace for ``rows`` logits rows under ``tag`` (requested here, so before any capture)."""
+        return self.ws.get(f"{tag}.lp.ws", (ops.logprob_workspace_bytes(rows, hist_cap),), torch.uint8, self.out.device)
+
+    def args(self, tag, logits, st, slot_of_row):
+        return ops.logprob_args(logits, st.history, st.hist_len, st.step, st.finished, self.out, self.token_logprobs, self.sum_logprob,
+                                self.n_scored, self.reserve(tag, logits.shape[0], st.history.shape[1]), out_row=st.out_row,
+                                slot_of_row=slot_of_row)
+
+    def host(self):
+        return dict(token_logprobs=self.token_logprobs.cpu(), sum_logprob=self.sum_logprob.cpu(), n_scored=self.n_scored.cpu())
+
+
+def rank_continuations(sum_logprob, n_scored, n, length_penalty=1.0):
+    """The n continuations of every prompt, best first: int64 [B, n] of indices j (row b * n + j of a generate_batch result with
+    num_return_sequences = n) ordered by sum_logprob / n_scored ** length_penalty, descending; ties go to the lower index.
+    length_penalty = 1.0 is the mean log-probability per token, 0.0 the plain sum.  Host only (float64)."""
+    n = int(n)
+    s = torch.as_tensor(sum_logprob).detach().cpu().to(torch.float64).reshape(-1)
+    k = torch.as_tensor(n_scored).detach().cpu().to(torch.float64).reshape(-1)
+    if n < 1 or s.numel() != k.numel() or s.numel() % n != 0:
+        raise ValueError(f"rank_continuations: {s.numel()} sums and {k.numel()} counts do not make rows of n = {n}")
+    score = (s / k.clamp(min=1.0) ** float(length_penalty)).reshape(-1, n)
+    return torch.argsort(score, dim=1, descending=True, stable=True)
+
+
+def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None):
     """Logits processors + token selection on the state ``st``.  The form follows from the arguments: ``slot_of_row`` -> the rows
     of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
-    (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens."""
+    (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``lp`` (a LogprobRecord; its workspace
+    under ``lp_tag``): the selection is bracketed by tcavt_logprob_begin / _finish, which read the raw row before the processors
+    touch it and the chosen token afterwards; the selection itself is the one without."""
+    if lp is not None:
+        largs = lp.args(lp_tag, logits, st, slot_of_row)
+        ops.logprob_begin(largs)
+        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row)
+        ops.logprob_finish(largs)
+        return
     if drules is not None:
         ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
                           workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules)
@@ -269,7 +322,7 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
 def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
-                   num_return_sequences=1, share_prefix=False):
+                   num_return_sequences=1, share_prefix=False, return_logprobs=False):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
@@ -278,6 +331,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     own a suffix cache ``gen.sfx.*`` of their generated tokens alone."""
     who = "generate_batch"
     check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
+    check_bool(who, "return_logprobs", return_logprobs)
     if not isinstance(share_prefix, bool):
         raise ValueError(f"generate_batch: share_prefix must be a bool, got {share_prefix!r}")
     if share_prefix and kv_cache == "fp8":
@@ -351,7 +405,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
         # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
         drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
-        select(logits, st, sp, out, False, sws, drules)
+        lp = LogprobRecord(mllm._ws, out) if return_logprobs else None  # (the flag alone does not change the sampler entry)
+        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen")
         steps_run = 0
         if N > 1:
             a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, cache, st.cur, st.pos, logits, pf.flags)
@@ -361,7 +416,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                     ops.llama_decode_step(a)
                 else:
                     ops.llama_decode_step_shared(a, prefix)
-                select(logits, st, sp, out, True, sws, drules)
+                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen")
 
             one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)
             steps_run = 1
@@ -388,6 +443,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
             reason[ran_out], n_gen[ran_out] = BUDGET, N
             info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
+        if lp is not None:
+            info = dict(info or dict(steps=steps_run), **lp.host())
     return out, info
 
 
@@ -396,12 +453,13 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
 # --------------------------------------------------------------------------------------
 def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k,
                   top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights,
-                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info):
+                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs=False):
     """-> (out int64 [R, max budget] on the device, mllm.pool_stats)."""
     who = "generate_pool"
     # ---- every illegal value is refused before anything touches a device
     check_format(who, "kv_cache", kv_cache)
     check_format(who, "decode_weights", decode_weights)
+    check_bool(who, "return_logprobs", return_logprobs)
     rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
     S, poll_every = int(slots), int(poll_every)
     if S < 1:
@@ -433,6 +491,8 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
     if R == 0:
         if return_info or not rules.empty:
             stats.update(finish_reason=torch.zeros(0, dtype=I32), n_generated=torch.zeros(0, dtype=I32))
+        if return_logprobs:
+            stats.update(token_logprobs=torch.zeros(0, Nmax), sum_logprob=torch.zeros(0), n_scored=torch.zeros(0, dtype=I32))
         return out, stats
     input_ids = input_ids.to(dev).contiguous()
     mask64 = attention_mask.to(dev).to(I64).contiguous()
@@ -468,20 +528,21 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
         a = decode_args(mllm, "pool", who, S, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, flags)
         # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
         drules = rules.to(dev).records(R, dev) if return_info or not rules.empty else None
+        lp = LogprobRecord(ws, out) if return_logprobs else None
         # what both admission launches share: rows, src_lmax, kv_lmax, n_layers, S, nkv ... and the eight state arrays
         geometry = (L, L, Lmax, ll.layers, S, ll.n_kv_heads)
         state = (st.history, st.hist_len, st.step, st.max_new, st.out_row, st.pos, st.finished, st.cur)
 
         def one_step():
             ops.llama_decode_step(a)
-            select(logits, st, sp, out, True, sws, drules)
+            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool")
 
         def admit(s, r):
             # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
             # and the first token from the one-row logits with the slot's state (views that start at slot s)
             logits1 = pf.run(vision_embs[r:r + 1], input_ids[r:r + 1], mask64[r:r + 1], after_stack=lambda: ops.slot_admit(
                 pf.buf("cache"), cache, s, *geometry, input_ids[r], pf.buf("kvlen"), Nq, budgets[r], r, *state))
-            select(logits1, slot_view(st, s), sp, out, False, sws1, drules)
+            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf")
 
         if G > 1:
             # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
@@ -513,7 +574,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             def group_pass():
                 logits_g = pg.run(pg_vis, pg_ids, pg_mask, after_stack=lambda: ops.slot_admit_group(
                     pg.buf("cache"), cache, pg_slot, *geometry, pg_ids, pg.buf("kvlen"), Nq, pg_budget, pg_outrow, bad_slot, *state))
-                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot)
+                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg")
 
         sched = SlotScheduler(R, S, G)
         step = later_pass = None
@@ -547,4 +608,6 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             stats["retired"] += [(r, s, stats["steps"]) for r, s in sched.retired[n_ret:]]
         if drules is not None:
             stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
+        if lp is not None:
+            stats.update(lp.host())
     return out, stats

@@ -1282,7 +1282,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
-                       poll_every=None, num_return_sequences=1, share_prefix=False):
+                       poll_every=None, num_return_sequences=1, share_prefix=False, return_logprobs=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -1329,14 +1329,24 @@ class LlamaMultiModal(nn.Module, _Prepared):
         ending rules, poll_every, return_info, the graph and ``decode_weights`` are as above; the attention's summation order
         differs from the default's, so tokens can differ where two logits are within rounding of each other.  It needs the 16-bit
         cache: with ``kv_cache="fp8"`` it raises ValueError.  generate_pool does not take it.
+        ``return_logprobs`` = True (opt-in; a bool, anything else raises ValueError): returns (out, info) and info gains the host
+        tensors "token_logprobs" float32 [B * n, max_new_tokens], "sum_logprob" float32 [B * n] and "n_scored" int32 [B * n]
+        ("log-probabilities").  token_logprobs[row, i] = log_softmax(raw)[out[row, i]] for every token the
+        row emitted, the ending token included, where raw is the fp32 logits row as the lm_head wrote it -- before the repetition
+        penalty, the bans, the temperature and top-k / top-p: the model's distribution, independent of the sampling arguments
+        (HF: output_logits=True, log_softmax, gather).  Entries after a row's end are 0.0; sum_logprob is their fp32 sum in step
+        order, n_scored their number.  Two small launches (tcavt_logprob_begin / _finish) bracket every token selection, in the
+        captured step too; the tokens, the sampler entry chosen and every other launch are those of the call without the flag.
+        generation.rank_continuations orders the n continuations of a prompt by it.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
             self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix)
+            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
+            return_logprobs)
         res = self._generated_texts(out)
-        return (res, info) if return_info else res
+        return (res, info) if return_info or return_logprobs else res
 
     def _generated_texts(self, out):
         """Token ids as they are without a tokenizer; with one, the decoded strings, cut as the reference cuts them."""
@@ -1347,7 +1357,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
     def generate_pool(self, vision_embs, input_ids, attention_mask, max_new_tokens=128, slots=8, poll_every=1, do_sample=True,
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
                       pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1,
-                      stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False):
+                      stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False, return_logprobs=False):
         """Text generation over a LIST of R requests on a fixed pool of ``slots`` decode slots ("slot
         pool"): request r is served exactly once, first in first out, and the moment a request ends (EOS, or its budget) the
         next one of the queue is prefilled into its slot -- no decode row computes pad tokens for longer than one poll interval.
@@ -1377,13 +1387,17 @@ class LlamaMultiModal(nn.Module, _Prepared):
         uses (the decode loop, the G = 1 admission, the grouped admission); a request may end on its first token, at admission.
         With none set the sampler launches are those of a call without.  With rules or ``return_info`` the stats gain
         "finish_reason" / "n_generated": host int32 [R] (1 EOS, 2 stop token, 3 stop sequence, 4 budget); ``return_info`` returns
-        (out, stats)."""
+        (out, stats).
+        ``return_logprobs`` = True (a bool, anything else raises ValueError): returns (out, stats) and the stats gain the host tensors
+        "token_logprobs" float32 [R, max budget], "sum_logprob" float32 [R] and "n_scored" int32 [R], as in generate_batch: the
+        log-softmax of the raw logits row at every token request r emitted, 0.0 after its end.  The bracket sits around all three
+        sampler uses, and a request's three results do not depend on its slot, the schedule or its partners (for a fixed G)."""
         out, stats = generation.generate_pool(
             self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
             repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info)
+            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs)
         res = self._generated_texts(out)
-        return (res, stats) if return_info else res
+        return (res, stats) if return_info or return_logprobs else res
 
 
 # --------------------------------------------------------------------------------------

@@ -1227,6 +1227,60 @@ def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finishe
     check(lib().tcavt_sample_tokens(ctypes.byref(a), stream_ptr()), "tcavt_sample_tokens")
 
 
+def logprob_workspace_bytes(rows, hist_cap):
+    """Bytes of the workspace of logprob_begin / logprob_finish for ``rows`` logits rows and histories of ``hist_cap`` ids."""
+    return int(capi.lib().tcavt_logprob_workspace_bytes(int(rows), int(hist_cap)))
+
+
+def logprob_args(logits, history, hist_len, step, finished, out_tokens, token_logprobs, sum_logprob, n_scored, workspace,
+                 out_row=None, slot_of_row=None):
+    """The tcavt_logprob_args of one bracket around a token selection on the same logits and state (the form follows from
+    slot_of_row / out_row as in sample_tokens), each tensor checked first.  token_logprobs fp32 like out_tokens; sum_logprob fp32
+    and n_scored int32, one entry per row of out_tokens; workspace uint8 of logprob_workspace_bytes(rows, history.shape[1])."""
+    who = "logprob"
+    rows, V = logits.shape
+    if history.dim() != 2 or out_tokens.dim() != 2:
+        raise capi.TcavtError("logprob: history needs one row per sample / slot, out_tokens one row per sample / request")
+    if slot_of_row is not None and out_row is None:
+        raise capi.TcavtError("logprob: out_row is missing (slot_of_row is given)")
+    slots = out_row is not None
+    n = history.shape[0] if slot_of_row is not None else rows
+    if history.shape[0] != n or (not slots and out_tokens.shape[0] != rows):
+        raise capi.TcavtError("logprob: history / out_tokens need one row per sample")
+    if token_logprobs.shape != out_tokens.shape:
+        raise capi.TcavtError("logprob: token_logprobs must have the shape of out_tokens")
+    _req(logits, torch.float32, f"{who}.logits")
+    per_slot = ((out_row, torch.int64, n, "out_row"),) if slots else ()
+    per_row = ((slot_of_row, torch.int32, rows, "slot_of_row"),) if slot_of_row is not None else ()
+    n_out = out_tokens.shape[0]
+    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"),
+                         (step, torch.int32, n if slots else 1, "step"), *per_slot, *per_row, (finished, torch.int32, n, "finished"),
+                         (out_tokens, torch.int64, 1, "out_tokens"), (token_logprobs, torch.float32, 1, "token_logprobs"),
+                         (sum_logprob, torch.float32, n_out, "sum_logprob"), (n_scored, torch.int32, n_out, "n_scored"),
+                         (workspace, torch.uint8, logprob_workspace_bytes(rows, history.shape[1]), "workspace")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+    a = capi.LogprobArgs()
+    a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
+    a.step, a.out_row, a.finished, a.out_tokens = step.data_ptr(), ptr(out_row), finished.data_ptr(), out_tokens.data_ptr()
+    a.token_logprobs, a.sum_logprob, a.n_scored = token_logprobs.data_ptr(), sum_logprob.data_ptr(), n_scored.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    a.rows, a.V, a.n_state, a.hist_cap, a.out_cap = rows, V, n, history.shape[1], out_tokens.shape[1]
+    return a
+
+
+def logprob_begin(args):
+    """Before the token selection: the raw row's (max, sum exp) partials and the snapshot (tcavt_logprob_begin)."""
+    check(lib().tcavt_logprob_begin(ctypes.byref(args), stream_ptr()), "tcavt_logprob_begin")
+
+
+def logprob_finish(args):
+    """After the token selection: log_softmax(raw)[token] of every row that was live (tcavt_logprob_finish)."""
+    check(lib().tcavt_logprob_finish(ctypes.byref(args), stream_ptr()), "tcavt_logprob_finish")
+
+
 def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value,
                      out_row_value, bad_slot_flag, history, hist_len, step, max_new, out_row, pos, finished, cur_tok):
     """The G samples of a grouped prefill move into their slots of an S-slot pool in one launch (tcavt_slot_admit_group).  src: the
