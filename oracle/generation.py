@@ -10,7 +10,7 @@ next position, logits = lm_head(final RMSNorm(hidden)) with lm_head tied to embe
 
   * greedy_generate: the oracle decoder (oracle/forward.py) re-run on the growing sequence, one sample at a time.
   * process_logits / select_token: HF's logits processors (RepetitionPenalty, NoRepeatNGram, Temperature, TopK, TopP, in
-    that order) and the token draw, restated in numpy exactly as csrc/generate.hip computes them (same ordering of ties,
+    that order) and the token draw, restated in numpy exactly as csrc/sampler.hip computes them (same ordering of ties,
     same Philox uniform); pinned against transformers' own processor classes by tests/golden/tiny_generation.npz.
 """
 import numpy as np
@@ -65,7 +65,7 @@ def greedy_generate(W, cfg, vision, input_ids, attention_mask, max_new_tokens, c
 
 
 # ---------------------------------------------------------------------------------------------
-# logits processors + selection, as csrc/generate.hip (sample_kernel) computes them
+# logits processors + selection, as csrc/sampler.hip (sample_kernel) computes them
 # ---------------------------------------------------------------------------------------------
 def process_logits(scores, history, repetition_penalty=1.2, no_repeat_ngram_size=3):
     """RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on one row (numpy fp32, returns a copy).  An id outside

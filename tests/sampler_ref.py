@@ -1,4 +1,4 @@
-"""Float64 reference of the token sampler (csrc/generate.hip: sample_kernel, sample_slice_kernel) and the comparer that
+"""Float64 reference of the token sampler (csrc/sampler.hip: sample_kernel, sample_slice_kernel) and the comparer that
 decides when an fp32 kernel may differ from it -- TEST INFRASTRUCTURE ONLY, numpy only.
 
 Written from the definitions of the transformers processors (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor,

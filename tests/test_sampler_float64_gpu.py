@@ -1,4 +1,4 @@
-"""The token sampler (csrc/generate.hip: sample_kernel in its three modes, sample_slice_kernel) against the float64 reference of
+"""The token sampler (csrc/sampler.hip: sample_kernel in its three modes, sample_slice_kernel) against the float64 reference of
 tests/sampler_ref.py, through ops.sample_tokens and ops.sample_logits_slots, in the one-stage form (no workspace) and the
 two-stage form (a lent workspace) at every vocabulary size at which the code takes another path:
 

@@ -4,7 +4,7 @@
 // prefill wrote them ([B][prefix_lmax][nkv * 64], read only) and each of the R = B * n decode rows owns a suffix cache of its
 // generated tokens only.  A query attends to [ shared prefix | own suffix | its new token ].
 //
-// attn_decode_kernel (csrc/generate.hip) reads every cached row once per (row, query head).  Here a prefix row is fetched once
+// attn_decode_kernel (csrc/attn_decode.hip) reads every cached row once per (row, query head).  Here a prefix row is fetched once
 // per (prompt, kv head, block of 32 queries): the n * group queries that share a prompt's kv head -- query (j, g) =
 // continuation j, head g of the group, number j * group + g -- take the place of the sequence positions of
 // attn_causal_gqa_stream_kernel (csrc/attention.hip), and per 32-key tile the arithmetic is that kernel's:

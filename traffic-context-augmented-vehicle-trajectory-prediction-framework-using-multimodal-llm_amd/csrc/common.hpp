@@ -185,5 +185,7 @@ int embed_fuse_impl(const void* table16, const int64_t* ids, const float* img, c
                     float stream_scale, int frag16, tcavt_stream_t stream);
 int rmsnorm16_impl(const void* x16, const float* gamma, float eps, void* out16, float* out_f32, int M, int H, int dtype16, int frag16,
                    tcavt_stream_t stream);
+// The decode attention's launch rule (csrc/attn_decode.hip), which the decode step checks before its first launch
+bool attn_decode_rule(int kv_lmax, int* KS, size_t* lds);
 
 }  // namespace tcavt

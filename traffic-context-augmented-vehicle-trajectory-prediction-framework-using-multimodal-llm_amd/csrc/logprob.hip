@@ -1,7 +1,7 @@
 // Log-probabilities of the generated tokens (tcavt_logprob_begin / tcavt_logprob_finish, include/tcavt.h).
 //
 // logprob = log_softmax(raw)[token], raw = the fp32 logits row as the lm_head wrote it -- before the repetition penalty, the bans,
-// the temperature and top-k / top-p.  The token-selection kernels (csrc/generate.hip) rewrite the row in place and advance the
+// the temperature and top-k / top-p.  The token-selection kernels (csrc/sampler.hip) rewrite the row in place and advance the
 // row's state, so two launches bracket them:
 //
 //   begin   rows x 16 workgroups, before the selection: workgroup (r, g) holds slice g of row r in registers (16-byte loads when the

@@ -1307,15 +1307,10 @@ def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, 
     check(lib().tcavt_slot_admit_group(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit_group")
 
 
-def kv_fanout(src, dst, n, rows, src_lmax, kv_lmax, n_layers, nkv, prompt_ids, kv_len, n_image, logits_src, logits_dst, history,
-              hist_len, pos, finished):
-    """A B-sample prefill becomes the state of a decode batch of B * n rows in one launch (tcavt_kv_fanout): row b * n + j is
-    continuation j of prompt b.  src: the B-sample cache, dst: the cache of B * n samples, both (k, v) 16-bit [n_layers, B | B * n,
-    lmax, nkv * 64] or both the four KV8 planes [n_layers, B | B * n, nkv, lmax, 64 | 2]; rows 0 .. rows - 1 are copied byte for
-    byte, each piece of the source read once.  prompt_ids int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst
-    [B * n, V], history int64 [B * n, cap] (its first n_ids columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0."""
-    who = "kv_fanout"
-    a = capi.KvFanoutArgs()
+def _bind_fanout(a, who, n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished, caches=None):
+    """Into the tcavt_kv_fanout_args / tcavt_state_fanout_args ``a``: B prompts become B * n decode rows -- the shapes, then the caches
+    if there are any (``caches``: _bind_caches' arguments from src_lmax on), then the eight state tensors, each checked first
+    (``who`` in the errors)."""
     if prompt_ids.dim() != 2 or logits_src.dim() != 2 or logits_dst.dim() != 2 or history.dim() != 2:
         raise capi.TcavtError(f"{who}: prompt_ids, logits_src, logits_dst and history are 2-D, one row per prompt / per decode row")
     B, n = prompt_ids.shape[0], int(n)
@@ -1324,33 +1319,9 @@ def kv_fanout(src, dst, n, rows, src_lmax, kv_lmax, n_layers, nkv, prompt_ids, k
     R, V = B * n, logits_src.shape[1]
     if logits_src.shape[0] != B or tuple(logits_dst.shape) != (R, V) or history.shape[0] != R:
         raise capi.TcavtError(f"{who}: logits_src needs B = {B} rows, logits_dst [{R}, {V}] and history {R} rows")
-    _bind_caches(a, who, src, dst, B, R, src_lmax, kv_lmax, n_layers, nkv)
-    for t, dt, k, nm in ((prompt_ids, torch.int64, B, "prompt_ids"), (kv_len, torch.int32, B, "kv_len"),
-                         (logits_src, torch.float32, B * V, "logits_src"), (logits_dst, torch.float32, R * V, "logits_dst"),
-                         (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"), (pos, torch.int32, R, "pos"),
-                         (finished, torch.int32, R, "finished")):
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, k, f"{who}.{nm}")
-        setattr(a, nm, t.data_ptr())
-    a.n_layers, a.B, a.n, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, B, n, int(rows), src_lmax, kv_lmax, nkv
-    a.n_ids, a.hist_cap, a.n_image, a.V = prompt_ids.shape[1], history.shape[1], int(n_image), V
-    check(lib().tcavt_kv_fanout(ctypes.byref(a), stream_ptr()), "tcavt_kv_fanout")
-
-
-def state_fanout(n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished):
-    """kv_fanout without a cache to copy (tcavt_state_fanout), for decode rows that read their prompt's cache in place: prompt_ids
-    int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst [B * n, V], history int64 [B * n, cap] (its first n_ids
-    columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0 for row b * n + j."""
-    who = "state_fanout"
-    a = capi.StateFanoutArgs()
-    if prompt_ids.dim() != 2 or logits_src.dim() != 2 or logits_dst.dim() != 2 or history.dim() != 2:
-        raise capi.TcavtError(f"{who}: prompt_ids, logits_src, logits_dst and history are 2-D, one row per prompt / per decode row")
-    B, n = prompt_ids.shape[0], int(n)
-    if B < 1 or n < 1:
-        raise capi.TcavtError(f"{who}: B = {B} and n = {n} must be >= 1")
-    R, V = B * n, logits_src.shape[1]
-    if logits_src.shape[0] != B or tuple(logits_dst.shape) != (R, V) or history.shape[0] != R:
-        raise capi.TcavtError(f"{who}: logits_src needs B = {B} rows, logits_dst [{R}, {V}] and history {R} rows")
+    if caches is not None:
+        src, dst, *shape = caches
+        _bind_caches(a, who, src, dst, B, R, *shape)
     for t, dt, k, nm in ((prompt_ids, torch.int64, B, "prompt_ids"), (kv_len, torch.int32, B, "kv_len"),
                          (logits_src, torch.float32, B * V, "logits_src"), (logits_dst, torch.float32, R * V, "logits_dst"),
                          (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"), (pos, torch.int32, R, "pos"),
@@ -1359,6 +1330,28 @@ def state_fanout(n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history
         _need(t, k, f"{who}.{nm}")
         setattr(a, nm, t.data_ptr())
     a.B, a.n, a.n_ids, a.hist_cap, a.n_image, a.V = B, n, prompt_ids.shape[1], history.shape[1], int(n_image), V
+
+
+def kv_fanout(src, dst, n, rows, src_lmax, kv_lmax, n_layers, nkv, prompt_ids, kv_len, n_image, logits_src, logits_dst, history,
+              hist_len, pos, finished):
+    """A B-sample prefill becomes the state of a decode batch of B * n rows in one launch (tcavt_kv_fanout): row b * n + j is
+    continuation j of prompt b.  src: the B-sample cache, dst: the cache of B * n samples, both (k, v) 16-bit [n_layers, B | B * n,
+    lmax, nkv * 64] or both the four KV8 planes [n_layers, B | B * n, nkv, lmax, 64 | 2]; rows 0 .. rows - 1 are copied byte for
+    byte, each piece of the source read once.  prompt_ids int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst
+    [B * n, V], history int64 [B * n, cap] (its first n_ids columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0."""
+    a = capi.KvFanoutArgs()
+    _bind_fanout(a, "kv_fanout", n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished,
+                 caches=(src, dst, src_lmax, kv_lmax, n_layers, nkv))
+    a.n_layers, a.rows, a.src_lmax, a.kv_lmax, a.nkv = n_layers, int(rows), src_lmax, kv_lmax, nkv
+    check(lib().tcavt_kv_fanout(ctypes.byref(a), stream_ptr()), "tcavt_kv_fanout")
+
+
+def state_fanout(n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished):
+    """kv_fanout without a cache to copy (tcavt_state_fanout), for decode rows that read their prompt's cache in place: prompt_ids
+    int64 [B, n_ids], kv_len int32 [B], logits_src fp32 [B, V] -> logits_dst [B * n, V], history int64 [B * n, cap] (its first n_ids
+    columns), hist_len = kv_len - n_image, pos = kv_len, finished = 0 for row b * n + j."""
+    a = capi.StateFanoutArgs()
+    _bind_fanout(a, "state_fanout", n, prompt_ids, kv_len, n_image, logits_src, logits_dst, history, hist_len, pos, finished)
     check(lib().tcavt_state_fanout(ctypes.byref(a), stream_ptr()), "tcavt_state_fanout")
 
 
