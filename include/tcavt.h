@@ -658,7 +658,7 @@ typedef struct tcavt_llama_layer {
   const void* w_o;    /* 16-bit [H][nq * 64] */
   const void* w_gu;   /* 16-bit [2 I][H], gate / up rows interleaved in blocks of 16 (TCAVT_EPI_SILU_MUL), post_attention_layernorm.weight folded in */
   const void* w_d;    /* 16-bit [H][I] */
-  /* LoRA-trainable variant (optional, all NULL otherwise): per-layer buffers the backward reads (csrc/llm_backward.hip) */
+  /* LoRA-trainable variant (optional, all NULL otherwise): per-layer buffers the backward reads (csrc/llm_backward.hip, csrc/attn_bwd.hip) */
   float* tape_h_mid;  /* [M][H]: residual stream after the attention half (then h_in stays untouched): fp32, or -- 16-bit
                          residual stream, tcavt_llama_stack_args.h == NULL -- of the 16-bit storage type (cast the pointer) */
   float* tape_h_out;  /* [M][H]: residual stream after the MLP half (same type) */

@@ -1,4 +1,4 @@
-"""The attention backward kernels of csrc/llm_backward.hip against float64 on every path.
+"""The attention backward kernels of csrc/attn_bwd.hip and csrc/attn_bwd_check.hip against float64 on every path.
 
 Every case calls the C entry points and checks them per element against one float64 evaluation of the operation in torch on the
 GPU, computed from the same 16-bit inputs:
@@ -15,7 +15,7 @@ round_dt(O64); the forward kernel is not part of this module, which also serves 
 tcavt_attn_bwd_scores, the scalar kernel) are checked against P = the float64 softmax and delta = sum_j P dP.
 test_formula_matches_autograd ties the formula to float64 autograd of softmax(S) v (1e-12 relative, unrounded att and lse).
 
-_paths(entry, T, nq, nkv, lse, outputs) mirrors the host rules of llm_backward.hip; test_paths_coverage asserts from the case
+_paths(entry, T, nq, nkv, lse, outputs) mirrors the host rules of attn_bwd.hip; test_paths_coverage asserts from the case
 lists that every kernel and instantiation is reached in fp16 and bf16.  Cases (B, T, nq, nkv, kv_len):
 
 | resident (tcavt_attn_bwd_resident: attn_bwd_dq_kernel + attn_bwd_dkv_res_kernel, 16-bit stores) | why |
@@ -181,7 +181,7 @@ def _case_id(c):
 # host-rule mirror and the case lists
 
 def _paths(entry, T, nq, nkv, lse=True, outputs=()):
-    """The kernels a call of `entry` launches, by the rules of llm_backward.hip; None when the entry point refuses the shape.
+    """The kernels a call of `entry` launches, by the rules of attn_bwd.hip; None when the entry point refuses the shape.
     outputs (tcavt_attn_bwd_scores only): which of dQ, stats, dS, PT are requested."""
     if nkv <= 0 or nq <= 0 or nq % nkv or T <= 0:
         return None
@@ -1278,6 +1278,10 @@ def test_attn_bwd_refusals(gpu):
             # (the dispatch hands the chunked form only what the resident form does not serve: T > 256)
             assert bool(L.tcavt_attn_bwd_long_ok(T, group, 1)) == (_paths("long", T, group, 1) is not None and T > 256), (T, group)
             assert bool(L.tcavt_attn_bwd_resident_ok(T, 2 * group, 2)) == bool(L.tcavt_attn_bwd_resident_ok(T, group, 1))
+    # no query heads: every predicate says no (pure host calls, a T inside each one's own range; nothing is launched)
+    assert L.tcavt_attn_bwd_resident_ok(96, 0, 1) == 0
+    assert L.tcavt_attn_bwd_long_ok(300, 0, 1) == 0
+    assert L.tcavt_attn_bwd_stream_ok(600, 0, 1) == 0
 
 
 def test_report_worst_ratio(gpu):

@@ -33,6 +33,19 @@ void set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+// MaxDynamicSharedMemorySize of a kernel that asks for more than 64 KB of dynamic LDS, set once: `set` is the flag of that
+// kernel instantiation, `who` the entry point named in the message (csrc/attn_bwd.hip, csrc/attn_bwd_check.hip)
+static inline int dyn_lds_limit(const void* kernel, int bytes, const char* who, bool& set) {
+  if (set) return TCAVT_OK;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+    return TCAVT_ERR_HIP;
+  }
+  set = true;
+  return TCAVT_OK;
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
@@ -87,6 +100,14 @@ template <bool F16>
 __device__ __forceinline__ float from16_lo(unsigned int w) { return from16<F16>(static_cast<bf16_t>(w & 0xffffu)); }
 template <bool F16>
 __device__ __forceinline__ float from16_hi(unsigned int w) { return from16<F16>(static_cast<bf16_t>(w >> 16)); }
+// one MFMA step on raw 16-byte fragments of the 16-bit type the backward runs in (F16: IEEE half = the forward's storage
+// contract, gradients carried under a power-of-two scale, tcavt_grad_scale_pick; otherwise bf16, round 1's contract)
+// (csrc/attn_bwd.hip, csrc/llm_backward.hip)
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma16b(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+  if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
 
 // nonzero when either half of a packed fp16 pair is +-inf or NaN (exponent field all ones)
 __device__ __forceinline__ unsigned int half_is_inf2(unsigned int w) {
