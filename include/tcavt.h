@@ -433,11 +433,15 @@ int tcavt_out_head(const float* fused, const float* w, const float* bias,
  * scripts/test.py:1342-1382; ablation_study_without_lora.py:1233-1238).
  *   pred [B][K][2][To] (K candidates; K = 1 for the plain path), gt [B][2][To],
  *   norm_stat [B][4] = (min_x, max_x, min_y, max_y)
- *   sums[0] = sum_b sum_t (dx^2)   sums[1] = sum_b sum_t (dy^2)   (K must be 1; MSE numerators)
+ *   sums[0] = sum_b sum_t (dx^2)   sums[1] = sum_b sum_t (dy^2)   (MSE numerators: those of candidate k = 0; the loss
+ *                                                                  path calls with K = 1)
  *   sums[2] = sum_b min_k ADE      sums[3] = sum_b min_k FDE      sums[4] = sum_b min_k RMSE
- *   argmin [B][3] int32: index of the minimising candidate for ADE/FDE/RMSE
+ *   argmin [B][3] int32 (optional): index of the minimising candidate for ADE/FDE/RMSE
  *   (first minimum, as torch.min / np.argmin)
- * sums must be zeroed by the caller; accumulated with one atomicAdd per block.
+ *   per_sample [B][3] fp32 (optional): min_k ADE, min_k FDE, min_k RMSE of each sample
+ * sums[] accumulates over calls (one call per batch): the caller zeroes it once.  One workgroup computes the five batch
+ * sums in a fixed order and adds each to sums[i] with a single plain +=, no atomics: the result is bit-reproducible.
+ * A non-finite pred or gt reaches sums[0] / sums[1] (tcavt_adamw_gated's gate relies on it).
  * ---------------------------------------------------------------------- */
 int tcavt_traj_metrics(const float* pred, const float* gt, const float* norm_stat,
                        float* sums, int32_t* argmin, float* per_sample, int B, int K,
