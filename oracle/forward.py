@@ -415,7 +415,7 @@ def ltsf_forward(W, cfg, x, poly_emb, final_hidden, r, drop=_ident, xattn_pad=64
     if r.mode() == "fp32":
         a = r(mha_core(q, k, v, cfg.cross_nhead, drop=drop, drop_cols=drop_cols))
     else:
-        # The 16-bit contracts follow the HIP path's absorbed form (model.TransformerLTSF.forward): with To queries against
+        # The 16-bit contracts follow the HIP path's absorbed form (ltsf.TransformerLTSF.forward): with To queries against
         # Lk keys per sample the K / V projections move to the query / output side,
         #     q_h (fh W_k[h]^T + b_k)^T = (q_h W_k[h]) fh^T + const per query (softmax-invariant),
         #     P_h (fh W_v[h]^T + b_v)   = (P_h fh) W_v[h]^T + b_v,

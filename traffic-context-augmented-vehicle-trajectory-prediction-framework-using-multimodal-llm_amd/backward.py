@@ -4,7 +4,7 @@ In the reference, ``loss.backward()`` (train.py:1182) walks an autograd graph th
 lane-polygon encoder and ``TransformerLTSF``: every MLLM parameter has ``requires_grad=False``
 (train.py:1140-1142), so the LLM's final hidden states are a constant.  This module spells that
 graph out stage by stage, in reverse, on the activations the forward retained
-(``save_for_backward`` workspaces of model.py).  Nothing here calls torch autograd or torch math.
+(``save_for_backward`` workspaces of tlayers.py / ltsf.py).  Nothing here calls torch autograd or torch math.
 
 Precision: fp32 wherever the forward is fp32; the cross-attention projections run their backward
 contractions in bf16 MFMA with fp32 accumulation (standard mixed precision), writing fp32 gradients.
@@ -16,8 +16,8 @@ import os
 
 import torch
 
-from . import ops, streams
-from .model import XATTN_PAD
+from . import capi, ops, streams
+from .layout import XATTN_PAD
 
 
 SPLITK_WS = 8 * 127 * 64 * 64  # floats: 8 split-K slices of the largest output tcavt_gemm_f32_strided splits (< 128 tiles)
@@ -25,6 +25,12 @@ SPLITK_WS = 8 * 127 * 64 * 64  # floats: 8 split-K slices of the largest output 
 
 def _rup(n, m):
     return (n + m - 1) // m * m
+
+
+def _carries(struct, spec, site="dropout_site"):
+    """True when the forward's argument struct holds the dropout triple `spec` (None: no dropout) as a C call would write it."""
+    p, seed, s = capi.drop_spec(spec)
+    return (struct.dropout_p, struct.dropout_seed, getattr(struct, site)) == (ctypes.c_float(p).value, seed, s)
 
 
 class GradBook:
@@ -297,7 +303,7 @@ class Backward:
         form (fp16 storage, absorbed cross-attention, C++ stage forward) with the sites numbered as the stage numbers them
         (self-attention block first_site .. + 3, post-MLP + 4); None -> the Python composition below."""
         m = self.m.ltsf
-        if not (m._absorbed and m._stage_ok(self.book.grads.device)):
+        if not (m._absorbed and m._stage_ok(self.book.grads.device) and m.xattn_stage is not None):  # (both forward phases ran as stages)
             return None
         sp = getattr(m.attn_block, "drop_specs", None) or [None] * 4
         post = getattr(m, "drop_post", None) if m.decoder.use_post_mlp else None
@@ -315,58 +321,28 @@ class Backward:
 
     def _ltsf_stage(self, g_out, x_in, on_poly_grad):
         """Backward.ltsf as tcavt_ltsf_backward: phase 1 (head .. g_poly), the lane-polygon hand-off, phase 2 (the rest);
-        the same kernels on the same named buffers as the composition in ltsf()/_sab()/_xattn_absorbed(), on one stream."""
-        from . import capi
-
-        m, G, ws = self.m.ltsf, self.book.g, self.m.ltsf._ws
-        dec, sab, pl = m.decoder, m.attn_block, self.pl
+        the same kernels on the same buffers as the composition in ltsf()/_sab()/_xattn_absorbed(), on one stream.  The
+        forward's arguments are the struct its own two stage calls filled (TransformerLTSF.stage), not a second one."""
+        m, G = self.m.ltsf, self.book.g
+        dec, pl = m.decoder, self.pl
         B, F, T = x_in.shape
-        C, To, dev = m.d_model, m.out_len, g_out.device
+        C, To = m.d_model, m.out_len
         Mo, Mt, H, nh = B * To, B * T, dec.cross_dim, dec.cross_nhead
         dh, L = H // nh, self._L
         Lp, Mp = _rup(L, XATTN_PAD), _rup(Mo, 64)
-        f32, bf, st = torch.float32, torch.bfloat16, m.storage
+        bf = torch.bfloat16
         p, seed, s0 = self._ltsf_stage_specs()
-        P = m._prepared()
-        fl, ca = dec.fusion_layer, dec.cross_attn
+        ca = dec.cross_attn
         post = dec.post_mlp[0].weight.shape[0] if dec.use_post_mlp else 0
         keep = []
-
-        def put(obj, **kw):
-            for k_, t_ in kw.items():
-                if t_ is not None:
-                    setattr(obj, k_, t_.data_ptr())
-                    keep.append(t_)
-
-        lt = lambda n, shape, dt=f32: ws.get("lt." + n, shape, dt, dev)
-        sa = lambda n, shape: sab._ws.get("sab." + n, shape, f32, dev)
-        # ---- the forward's arguments (both phases): activations by their workspace names, weights as the forward used them
-        f = capi.LtsfArgs()
-        put(f, x=x_in, enc_w=P.enc_w, tok=lt("tok", (Mt, C)), xp_tok=lt("xp", (Mt, C)),
-            sa_n1_w=sab.norm1.weight, sa_in_w=sab.mha.in_proj_weight, sa_out_w=sab.mha.out_proj.weight, sa_n2_w=sab.norm2.weight,
-            sa_f0_w=sab.ffn[0].weight, sa_f3_w=sab.ffn[3].weight,
-            sa_xn=sa("xn", (Mt, C)), sa_qkv=sa("qkv", (Mt, 3 * C)), sa_att=sa("att", (Mt, C)), sa_res1=sa("res1", (Mt, C)),
-            sa_rn=sa("rn", (Mt, C)), sa_f=sa("f", (Mt, 4 * C)), e=sa("out", (Mt, C)),
-            poly_emb=self._poly_emb.contiguous(), lane_w=dec.lane_fc.weight, dec_w=P.dec_w, d0=lt("dec0", (B, C * To)),
-            dec_tb=lt("dectb", (Mo, C), st), proj=lt("proj", (Mo, H), st), cross=lt("cross", (Mo, H), st),
-            fused=lt("fused", (Mo, C)), fl_n_w=fl[0].weight, fn=lt("fn", (Mo, C)), fl1_w=fl[1].weight, f1=lt("f1", (Mo, C)),
-            fl3_w=fl[3].weight, f2=lt("f2", (Mo, C)), out_w=dec.out_proj.weight)
-        if post:
-            put(f, pm0_w=dec.post_mlp[0].weight, pm3_w=dec.post_mlp[3].weight, hid=lt("hid", (B, post)))
-        put(f.xattn, q=lt("q", (Mo, H), st), fh=self._fh_b, scores=lt("S", (B * nh * To, Lp)),
-            probs=lt("P", (B * nh * To, Lp), torch.float16), ctx=lt("ctx", (nh, Mo, H), st), att=lt("att", (Mo, H), st))
-        fx = f.xattn
-        fx.B, fx.To, fx.L, fx.Lp, fx.H, fx.nhead, fx.dtype16 = B, To, L, Lp, H, nh, capi.F16
+        put = lambda obj, **kw: capi.bind(obj, keep, **kw)
+        f = m.stage[0]
         xsp = getattr(m, "drop_xattn", None)
-        if xsp is not None:
-            fx.dropout_p, fx.dropout_seed, fx.dropout_site = xsp[0], xsp[1] & 0xFFFFFFFFFFFFFFFF, xsp[2]
-        f.B, f.C, f.T, f.To, f.F, f.H, f.nhead_sa = B, C, T, To, F, H, sab.nhead
-        f.poly_dim, f.post_hidden = self._poly_emb.shape[1], post
-        f.dropout_p, f.dropout_seed, f.first_site = p, seed & 0xFFFFFFFFFFFFFFFF, s0
+        # under the gate of _ltsf_stage_specs the forward numbered its sites as the stage does: its struct carries the triples
+        assert _carries(f, (p, seed, s0), "first_site") and _carries(f.xattn, xsp), "the forward's struct holds other dropout sites"
         # ---- gradients, workspaces
         a = capi.LtsfBwdArgs()
-        a.fwd = ctypes.pointer(f)
-        a.xattn.fwd = ctypes.cast(ctypes.addressof(f) + capi.LtsfArgs.xattn.offset, ctypes.POINTER(capi.CrossAttnArgs))
+        a.fwd, a.xattn.fwd = ctypes.pointer(f), ctypes.pointer(f.xattn)
         b = self._buf
         g_q = b("xa.g_q", (Mo, H), bf)
         put(a.xattn, g_att=b("g_att", (Mo, H), bf), w_in=ca.in_proj_weight.detach(), gw_in=G[pl + "decoder.cross_attn.in_proj_weight"],
@@ -543,7 +519,7 @@ class Backward:
         return g_q, g_k, g_v, L
 
     def _xattn_absorbed(self, g_att, q, B, To, H, nh, dh, gWin, gbin):
-        """Backward of the absorbed cross-attention (model.TransformerLTSF.forward), per head h with F = the sample's final
+        """Backward of the absorbed cross-attention (ltsf.TransformerLTSF.forward), per head h with F = the sample's final
         hidden states (a constant: the MLLM is frozen), q' = q_h W_k[h], S = q' F^T / sqrt(dh), P = dropout(softmax(S)),
         ctx = P F, att_h = ctx W_v[h]^T + b_v:
             gW_v[h] = g_att_h^T ctx      gb_v = colsum(g_att)      g_ctx = g_att_h W_v[h]
@@ -563,16 +539,11 @@ class Backward:
         scale = 1.0 / math.sqrt(dh)
         ctx = ws.get("lt.ctx", (nh, M, H), st, dev)
         Pm = ws.get("lt.P", (B * nh * To, Lp), torch.float16, dev)
-        if os.environ.get("TCAVT_PY_TLAYERS", "0") != "1":  # one C call: tcavt_cross_attn_backward (csrc/tlayers.hip)
-            from . import capi
-            f = capi.CrossAttnArgs()
-            fwd = dict(q=q, fh=self._fh_b, scores=ws.get("lt.S", (B * nh * To, Lp), torch.float32, dev), probs=Pm, ctx=ctx)
-            for k_, t_ in fwd.items():
-                setattr(f, k_, t_.data_ptr())
-            f.B, f.To, f.L, f.Lp, f.H, f.nhead, f.dtype16 = B, To, L, Lp, H, nh, capi.F16
+        if os.environ.get("TCAVT_PY_TLAYERS", "0") != "1" and m.xattn_stage is not None:
+            # one C call: tcavt_cross_attn_backward (csrc/tlayers.hip) on the struct the forward's own stage call filled
+            f = m.xattn_stage[0]
             xsp = getattr(m, "drop_xattn", None)
-            if xsp is not None:
-                f.dropout_p, f.dropout_seed, f.dropout_site = xsp[0], xsp[1] & 0xFFFFFFFFFFFFFFFF, xsp[2]
+            assert _carries(f, xsp), "the forward's struct holds another dropout site"
             a = capi.CrossAttnBwdArgs()
             a.fwd = ctypes.pointer(f)
             g_q = self._buf("xa.g_q", (M, H), bf)
@@ -584,13 +555,10 @@ class Backward:
                         g_qp=self._buf("xa.g_qp", (nh, M, H), bf))
             if xsp is not None:
                 bufs["p_undropped"] = self._buf("xa.Pu", (B * nh * To, Lp), torch.float16)
-            for k_, t_ in bufs.items():
-                setattr(a, k_, t_.data_ptr())
+            capi.bind(a, **bufs)
             red = self._buf("xa.red", (_rup(M, 128) // 128 * H,))
             a.red_ws, a.red_ws_elems = red.data_ptr(), red.numel()
-            bufs["red"] = red
             ops.cross_attn_backward(a)
-            del fwd, bufs
             return g_q
         # bf16 copies of the hidden states for the gradient-side contractions: per-sample transposed [H][B*Lp] (converted
         # while transposing, keys padded to Lp with zeros) and, transposed back, row-major [B*Lp][H]
@@ -725,10 +693,8 @@ class Backward:
         """Backward.polygon's layer loop as tcavt_tlayer_stack_backward (fp32 encoder layers; csrc/tlayers.hip): the gradient
         of the stack input lands in the buffer "po.g_x0".  False -> the caller runs the Python composition (TCAVT_PY_TLAYERS=1,
         or dropout sites that are not the stage's numbering)."""
-        if os.environ.get("TCAVT_PY_TLAYERS", "0") == "1":
+        if os.environ.get("TCAVT_PY_TLAYERS", "0") == "1" or sv.stage is None:  # (None: the forward ran the composition)
             return False
-        from . import capi
-
         enc, G, pp = self.m.lane_polygon_encoder, self.book.g, self.pp
         n, M = len(sv.layers), B * P
         specs = [s.get("drop") or [None] * 4 for s in sv.layers]
@@ -742,31 +708,18 @@ class Backward:
             if any(x[0] != p or x[1] != seed for x in flat) or [x[2] for x in flat] != list(range(s0, s0 + 4 * n)):
                 return False
         keep = []
-
-        def put(obj, **kw):
-            for k_, t_ in kw.items():
-                setattr(obj, k_, t_.data_ptr())
-                keep.append(t_)
-
-        arr, grads = (capi.TLayer * n)(), (capi.TLayerGrads * n)()
+        put = lambda obj, **kw: capi.bind(obj, keep, **kw)
+        f = sv.stage[0]  # the forward's own TStackArgs (its TLayer array names every layer's weights and retained activations)
+        assert _carries(f, (p, seed, s0), "first_site"), "the forward's struct holds other dropout sites"
+        grads = (capi.TLayerGrads * n)()
         ff = enc.encoder.layers[0].linear1.weight.shape[0]
-        for i, (s, lyr) in enumerate(zip(sv.layers, enc.encoder.layers)):
-            sa, pre = lyr.self_attn, f"{pp}encoder.layers.{i}."
-            put(arr[i], w_in=sa.in_proj_weight.detach(), w_out=sa.out_proj.weight.detach(), w1=lyr.linear1.weight.detach(),
-                w2=lyr.linear2.weight.detach(), n1_w=lyr.norm1.weight.detach(), n2_w=lyr.norm2.weight.detach(), qkv=s["qkv"],
-                att=s["att"], y=s["y"], x1=s["x1"], ffh=s["f"], y2=s["y2"])
-            if i > 0:
-                put(arr[i - 1], out=s["x"])  # a layer's input is its predecessor's output
+        for i in range(n):
+            pre = f"{pp}encoder.layers.{i}."
             put(grads[i], g_w_in=G[pre + "self_attn.in_proj_weight"], g_b_in=G[pre + "self_attn.in_proj_bias"],
                 g_w_out=G[pre + "self_attn.out_proj.weight"], g_b_out=G[pre + "self_attn.out_proj.bias"],
                 g_w1=G[pre + "linear1.weight"], g_b1=G[pre + "linear1.bias"], g_w2=G[pre + "linear2.weight"],
                 g_b2=G[pre + "linear2.bias"], g_n1_w=G[pre + "norm1.weight"], g_n1_b=G[pre + "norm1.bias"],
                 g_n2_w=G[pre + "norm2.weight"], g_n2_b=G[pre + "norm2.bias"])
-        f = capi.TStackArgs()
-        f.layers, f.n_layers = arr, n
-        put(f, x=sv.layers[0]["x"], key_len=sv.lens)
-        f.B, f.L, f.E, f.FF, f.nhead, f.dtype16 = B, P, D, ff, nh, 0
-        f.dropout_p, f.dropout_seed, f.first_site = p, seed & 0xFFFFFFFFFFFFFFFF, s0
         a = capi.TStackBwdArgs()
         a.fwd, a.grads = ctypes.pointer(f), grads
         b = self._buf

@@ -534,3 +534,38 @@ def ptr(t):
     if t is None:
         return None
     return c_void_p(t.data_ptr())
+
+
+def bind(struct, keep=None, **tensors):
+    """struct.<name> = t.data_ptr() for every tensor given by field name (None: the field stays as it is).  `keep`: a list that
+    receives the tensors -- whoever holds it keeps what the raw pointers name alive until the call has been made."""
+    for name, t in tensors.items():
+        if t is not None:
+            setattr(struct, name, t.data_ptr())
+            if keep is not None:
+                keep.append(t)
+
+
+def drop_spec(d):
+    """dropout spec (p, seed, site) or None -> (p, seed, site) ctypes-ready."""
+    if d is None:
+        return 0.0, 0, 0
+    p, seed, site = d
+    return float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF
+
+
+def bind_dropout(struct, spec, p="dropout_p", seed="dropout_seed", site="dropout_site"):
+    """The dropout spec (p, seed, site) into the struct's three fields (named per struct: first_site, lora_first_site,
+    lora_dropout_p ...); None: nothing is written."""
+    if spec is not None:
+        for field, value in zip((p, seed, site), drop_spec(spec)):
+            setattr(struct, field, value)
+
+
+def clone_layers(src):
+    """A field-for-field copy of a LlamaLayer array: the caller then overrides the pointers that differ."""
+    dst = (LlamaLayer * len(src))()
+    for d, s in zip(dst, src):
+        for name, _ in LlamaLayer._fields_:
+            setattr(d, name, getattr(s, name))
+    return dst

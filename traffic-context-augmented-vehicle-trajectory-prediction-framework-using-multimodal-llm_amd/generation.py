@@ -1,5 +1,5 @@
 """Host side of text generation: what LlamaMultiModal.generate_batch and generate_pool run.  The user
-contract -- arguments, defaults, semantics -- is documented on those two methods (model.py); this module is the code behind them,
+contract -- arguments, defaults, semantics -- is documented on those two methods (mllm.py); this module is the code behind them,
 one piece per job:
 
   Prefill          image tokens + prompt through the decoder into a KV cache, last rows through the lm_head -> first logits
@@ -284,8 +284,7 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
                 act=ws.get(f"{tag}.dact", (Br, ll.inter), st, dev, zero=True), t=ws.get(f"{tag}.dt", (B, 64), st, dev, zero=True))
     if not LW.stream16:
         bufs["h"] = ws.get(f"{tag}.dh", (B, H), torch.float32, dev)
-    for k_, v_ in bufs.items():
-        setattr(a, k_, v_.data_ptr())
+    capi.bind(a, **bufs)
     a.layers, a.gamma_final = PL.carr, PL.g_final.data_ptr()
     if DW is not None:
         a.layers, a.table_packed = DW.carr, DW.table.data_ptr()

@@ -26,7 +26,7 @@ import os
 import torch
 
 from . import capi, ops, streams
-from .model import LORA_V
+from .layout import LORA_V
 
 
 def _rup(x, m):
@@ -171,8 +171,7 @@ class LoraBackward:
         a.rope_cos, a.rope_sin, a.kv_len = cos.data_ptr(), sin.data_ptr(), tape.kv_len.data_ptr()
         a.scale, a.scale_scratch = scale.data_ptr(), self._buf("scale_scratch", (1,), torch.int32, zero=True).data_ptr()
         a.scale_backoff = None if self.scale_backoff is None else self.scale_backoff.data_ptr()
-        for k in ("g_h", "g_hb", "g_xn", "g_xl", "g_att", "dA", "dB"):
-            setattr(a, k, buf[k].data_ptr())
+        capi.bind(a, **{k: buf[k] for k in ("g_h", "g_hb", "g_xn", "g_xl", "g_att", "dA", "dB")})
         a.g_qkv0, a.g_qkv1, a.g_t0, a.g_t1 = buf["g_qkv"][0].data_ptr(), buf["g_qkv"][1].data_ptr(), buf["g_t"][0].data_ptr(), buf["g_t"][1].data_ptr()
         a.stats = self._buf("at.stats", (B * nq * L, 4), torch.float32).data_ptr()
         if leaf is not None:
@@ -185,7 +184,7 @@ class LoraBackward:
         a.rms_eps, a.lora_scale = eps, s
         dspec = tape.layers[0].dspec
         if dspec is not None:  # ((p, seed, site_q), (p, seed, site_v)) of layer 0: sites advance by two per layer
-            a.lora_dropout_p, a.dropout_seed, a.lora_first_site = dspec[0][0], dspec[0][1] & 0xFFFFFFFFFFFFFFFF, dspec[0][2]
+            capi.bind_dropout(a, dspec[0], p="lora_dropout_p", site="lora_first_site")
         capi.check(capi.lib().tcavt_llama_stack_backward(ctypes.byref(a), capi.stream_ptr()), "tcavt_llama_stack_backward")
         self._keep = (arr, a)
 

@@ -53,12 +53,7 @@ def _need(t, numel, name):
         raise capi.TcavtError(f"{name}: buffer has {t.numel()} elements, kernel needs {numel}")
 
 
-def _drop(d):
-    """dropout spec (p, seed, site) or None -> (p, seed, site) ctypes-ready."""
-    if d is None:
-        return 0.0, 0, 0
-    p, seed, site = d
-    return float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF
+_drop = capi.drop_spec  # dropout spec (p, seed, site) or None -> (p, seed, site) ctypes-ready
 
 
 def gemm_bf16(a, w, out=None, *, out_dtype=None, bias=None, relu=False, residual=None, a2=None,
@@ -375,7 +370,7 @@ def gemm_mx8(a8, a_scale, w8, w_scale, out, dtype16, *, epilogue=0, **fields):
         if (not out.is_cuda and not _ALLOW_CPU) or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < n_out:
             raise capi.TcavtError(f"gemm_mx8.out: 2-D GPU tensor of at least ({M}, {n_out}) with unit column stride required")
         args.C, args.ldc, args.out_dtype = out.data_ptr(), out.stride(0), _DT[out.dtype]
-    for k, v in fields.items():
+    for k, v in fields.items():  # (tensors and scalars mixed: not capi.bind's case)
         setattr(args, k, v.data_ptr() if torch.is_tensor(v) else v)
     check(lib().tcavt_gemm_mx8(ctypes.byref(args), stream_ptr()), "tcavt_gemm_mx8")
     return out
@@ -1020,7 +1015,7 @@ def adamw_gated(p, g, m, v, lr, beta1, beta2, eps, weight_decay, loss, ctl, grad
 # stage-level entry points (include/tcavt.h "Stage-level entry points")
 # ----------------------------------------------------------------------------------------------
 def llama_stack_forward(args):
-    """args: capi.LlamaStackArgs filled by model.LlamaWithCrossAttnPEFT (which owns and sizes every buffer it names)."""
+    """args: capi.LlamaStackArgs filled by llama.LlamaWithCrossAttnPEFT (which owns and sizes every buffer it names)."""
     check(lib().tcavt_llama_stack_forward(ctypes.byref(args), stream_ptr()), "tcavt_llama_stack_forward")
 
 
@@ -1132,14 +1127,14 @@ def _bind_caches(a, who, src, dst, n_src, n_dst, src_lmax, kv_lmax, n_layers, nk
                                (dst[1], "dst_v", kv_lmax, n_dst)):
             _req16(t, f"{who}.{nm}", like=src[0])
             _need(t, n_layers * n * lmax * nkv * 64, f"{who}.{nm}")
-            setattr(a, nm, t.data_ptr())
+            capi.bind(a, **{nm: t})
         a.dtype16 = _DT[src[0].dtype]
     else:
         _kv8_planes(src, n_layers * n_src * nkv * src_lmax, f"{who}.src")
         _kv8_planes(dst, n_layers * n_dst * nkv * kv_lmax, f"{who}.dst")
         for side, planes in (("src", src), ("dst", dst)):
             for t, nm in zip(planes, ("k_codes", "k_scales", "v_codes", "v_scales")):
-                setattr(a, f"{side}_{nm}", t.data_ptr())
+                capi.bind(a, **{f"{side}_{nm}": t})
         a.dtype16 = capi.F16  # (bytes are copied: the planes have no 16-bit type)
 
 
@@ -1153,7 +1148,7 @@ def _bind_admit(a, who, src, dst, n_src, src_lmax, kv_lmax, n_layers, S, nkv, hi
                       (finished, torch.int32, "finished"), (cur_tok, torch.int64, "cur_tok")):
         _req(t, dt, f"{who}.{nm}")
         _need(t, S, f"{who}.{nm}")
-        setattr(a, nm, t.data_ptr())
+        capi.bind(a, **{nm: t})
     if history.dim() != 2 or history.shape[0] != S:
         raise capi.TcavtError(f"{who}: history needs one row per slot")
     a.n_layers, a.S, a.src_lmax, a.kv_lmax, a.nkv, a.hist_cap = n_layers, S, src_lmax, kv_lmax, nkv, history.shape[1]
@@ -1302,7 +1297,7 @@ def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, 
                          (bad_slot_flag, torch.int32, 1, "bad_slot_flag")):
         _req(t, dt, "slot_admit_group." + nm)
         _need(t, n, "slot_admit_group." + nm)
-        setattr(a, nm, t.data_ptr())
+        capi.bind(a, **{nm: t})
     a.slot, a.G, a.rows, a.n_ids, a.n_image = slot.data_ptr(), G, int(rows), prompt_ids.shape[1], int(n_image)
     check(lib().tcavt_slot_admit_group(ctypes.byref(a), stream_ptr()), "tcavt_slot_admit_group")
 
@@ -1328,7 +1323,7 @@ def _bind_fanout(a, who, n, prompt_ids, kv_len, n_image, logits_src, logits_dst,
                          (finished, torch.int32, R, "finished")):
         _req(t, dt, f"{who}.{nm}")
         _need(t, k, f"{who}.{nm}")
-        setattr(a, nm, t.data_ptr())
+        capi.bind(a, **{nm: t})
     a.B, a.n, a.n_ids, a.hist_cap, a.n_image, a.V = B, n, prompt_ids.shape[1], history.shape[1], int(n_image), V
 
 
@@ -1442,7 +1437,7 @@ def attn_decode8(qkv, k_codes, k_scales, v_codes, v_scales, pos, out, B, nq, nkv
 
 
 def llama_decode_step(args):
-    """args: capi.DecodeArgs filled by model.LlamaMultiModal.generate_batch (which owns and sizes every buffer)."""
+    """args: capi.DecodeArgs filled by generation.generate_batch (which owns and sizes every buffer)."""
     check(lib().tcavt_llama_decode_step(ctypes.byref(args), stream_ptr()), "tcavt_llama_decode_step")
 
 
@@ -1453,12 +1448,12 @@ def llama_decode_step_shared(args, prefix):
 
 
 def tlayer_stack_forward(args):
-    """args: capi.TStackArgs filled by model._TLayerRunner.run_stack (which owns and sizes every buffer)."""
+    """args: capi.TStackArgs filled by tlayers._TLayerRunner.run_stack (which owns and sizes every buffer)."""
     check(lib().tcavt_tlayer_stack_forward(ctypes.byref(args), stream_ptr()), "tcavt_tlayer_stack_forward")
 
 
 def cross_attn_forward(args):
-    """args: capi.CrossAttnArgs filled by model.TransformerLTSF.forward (which owns and sizes every buffer)."""
+    """args: capi.CrossAttnArgs filled by ltsf.TransformerLTSF.forward (which owns and sizes every buffer)."""
     check(lib().tcavt_cross_attn_forward(ctypes.byref(args), stream_ptr()), "tcavt_cross_attn_forward")
 
 
@@ -1468,7 +1463,7 @@ def cross_attn_backward(args):
 
 
 def ltsf_forward(args, phase):
-    """args: capi.LtsfArgs filled by model.TransformerLTSF (which owns and sizes every buffer); phase 1 / 2 / 3."""
+    """args: capi.LtsfArgs filled by ltsf.TransformerLTSF (which owns and sizes every buffer); phase 1 / 2 / 3."""
     check(lib().tcavt_ltsf_forward(ctypes.byref(args), int(phase), stream_ptr()), "tcavt_ltsf_forward")
 
 
@@ -1670,9 +1665,8 @@ def lm_eval(h16, table, labels, Nq, B, L, *, loss, count, lse, pred, workspace, 
     a.B, a.L, a.V, a.H, a.Nq = B, L, V, H, Nq
     a.dtype16 = _DT[h16.dtype]
     a.loss, a.count, a.lse, a.pred = loss.data_ptr(), count.data_ptr(), lse.data_ptr(), pred.data_ptr()
-    for nm, t in (("row_loss", row_loss), ("flag", flag), ("correct", correct), ("sample_tokens", sample_tokens),
-                  ("sample_correct", sample_correct), ("sample_nll", sample_nll)):
-        setattr(a, nm, None if t is None else t.data_ptr())
+    capi.bind(a, row_loss=row_loss, flag=flag, correct=correct, sample_tokens=sample_tokens, sample_correct=sample_correct,
+              sample_nll=sample_nll)
     a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
     check(lib().tcavt_lm_eval(ctypes.byref(a), stream_ptr()), "tcavt_lm_eval")
     return pred

@@ -11,6 +11,8 @@ import ctypes
 
 import torch
 
+from . import capi
+
 MAX_SEQS = 16
 MAX_SEQ_LEN = 8
 RUNNING, EOS, STOP_TOKEN, STOP_SEQUENCE, BUDGET = 0, 1, 2, 3, 4  # finish_reason; when several apply in one step the smallest wins
@@ -99,15 +101,10 @@ class DeviceStopRules:
         return self
 
     def struct(self):
-        from . import capi
-
         if self._struct is None:
             s = capi.StopRules()
-            for name in ("bitmap", "seqs", "seq_len"):
-                t = getattr(self, name)
-                setattr(s, "stop_" + name, t.data_ptr() if t is not None else None)
-            s.finish_reason = self.finish_reason.data_ptr() if self.finish_reason is not None else None
-            s.n_generated = self.n_generated.data_ptr() if self.n_generated is not None else None
+            capi.bind(s, stop_bitmap=self.bitmap, stop_seqs=self.seqs, stop_seq_len=self.seq_len, finish_reason=self.finish_reason,
+                      n_generated=self.n_generated)
             s.n_seqs, s.min_new_tokens = len(self.rules.stop_sequences), self.rules.min_new_tokens
             self._struct = s
         return self._struct

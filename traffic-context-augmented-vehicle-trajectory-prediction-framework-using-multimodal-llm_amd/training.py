@@ -18,6 +18,7 @@ import torch.distributed as dist
 from . import ops, streams
 from .backward import Backward, GradBook
 from .llm_backward import LoraBackward, lora_named_parameters
+from .parts import DropoutCtx
 from .qformer_backward import QFormerBackward
 
 
@@ -537,8 +538,6 @@ class MllmTrainer:
 
     def forward_backward(self, vision_embs, input_ids, attention_mask, labels):
         """zero_grad + taped forward + LM loss + backward; gradients end up in ``self.book.g``.  Returns the loss (device scalar)."""
-        from .model import DropoutCtx
-
         m = self.model
         mm, lw = m.mllm, m.mllm.llama_wrapper
         with torch.no_grad():
