@@ -29,6 +29,7 @@ Coverage (form: how it is reached -- shapes M x N x K; gx = XCD partition of the
 | skinny | tile 0, M <= 32, K % 256 | M 1, 17, 32 x 512; 32x8192 (two column blocks) | 17x1024 (no preact) | 17x768 (K2 = 64) | 17x512 |
 | two-launch split K | tile 0, NORM16, workspace | | | | 1024x2048x4096 |
 | SILU_BWD | tile 0 / 257 | 512x512x256 in place and out of place | | | |
+| batched (batch > 1), dropout epilogue | tiles 0, 64, 128, 256 | tests/test_gemm_batched_gpu.py, same rules and helpers | | | |
 
 Each row runs in bf16 and fp16 and in both regimes; out dtypes f32 and the operand type (the 4-wave SiLU / RoPE forms
 refuse f32, asserted).  test_decoder_projections runs the four projections with tcavt_llama_stack_forward's flag sets at

@@ -185,7 +185,7 @@ def gemm_batched(a, w, out, *, M, N, K, lda, ldw, ldc, batch, inner, sA, sW, sC,
     for t, s, rows, ld, cols, nm in ((a, sA, M, lda, K, "a"), (w, sW, N, ldw, K, "w"), (out, sC, M, ldc, N, "out")):
         if not t.is_cuda and not _ALLOW_CPU:
             raise capi.TcavtError(f"gemm_batched.{nm}: tensor must live on the GPU")
-        last_inner = (inner - 1) // w_group if nm == "w" else inner - 1  # w_group products share one W
+        last_inner = (inner - 1) // max(w_group, 1) if nm == "w" else inner - 1  # w_group products share one W (0: off, as 1)
         need = (outer - 1) * s[0] + last_inner * s[1] + (rows - 1) * ld + cols
         if _avail(t) < need:
             raise capi.TcavtError(f"gemm_batched.{nm}: buffer has {_avail(t)} elements past its pointer, needs {need}")
