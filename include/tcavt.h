@@ -1445,6 +1445,95 @@ int64_t tcavt_logprob_workspace_bytes(int rows, int hist_cap);
 int tcavt_logprob_begin(const tcavt_logprob_args* args, tcavt_stream_t stream);
 int tcavt_logprob_finish(const tcavt_logprob_args* args, tcavt_stream_t stream);
 
+/* ---- Beam search (HF GenerationMixin._beam_search, num_beams = n, do_sample = False) on R = B * n decode rows, row r = b * n + j --
+ * One step of the search is tcavt_beam_select on the step's logits followed by tcavt_beam_reorder; between two steps the caller
+ * runs the decode step on cur_tok / pos.  Step 0 uses the prefill's logits (every row of a prompt holds a copy).  Prompts are
+ * independent: a prompt's results are the same bits whatever other prompts run beside it.  With K = 2 n, per prompt b and its step
+ * s = step[b]:
+ *   1. every live beam j: lp = log_softmax(raw fp32 row) -- per-row (max, sum exp) in the fixed slice order of tcavt_logprob_begin,
+ *      so the summation order depends on V alone -- then HF's processors ON lp with history = the row's hist_len ids (the prompt's
+ *      valid ids and the beam's tokens): repetition penalty lp < 0 ? lp * p : lp / p, n-gram ban -inf; acc = lp + run_score[j] (fp32).
+ *      logits is only read.
+ *   2. candidates: the K first of all live (j, token) by (acc descending, j * V + token ascending).
+ *   3. stop[k] = token == eos_token_id || s + 1 == N.
+ *   4. new running beams: the first n candidates with !stop in candidate order -> parent[r] (the LOCAL beam index), cur_tok[r],
+ *      run_score[r] = acc, live[r] = 1; fewer than n (only at s + 1 == N): the rest are dead (live 0, parent j, cur_tok pad).
+ *   5. finished store (n slots per prompt, best first, empty slots last): candidate k is admitted iff stop[k] && k < n && unsat[b]
+ *      && !(all fin_flag && early_stopping), with score acc / len_pow[s] (ONE IEEE fp32 division; len_pow is the caller's table of
+ *      float32((s + 1) ** length_penalty)); the old slots, then the admitted candidates in candidate order, are merged and the n
+ *      best by (score descending, merge index ascending) kept.  fin_tokens of a slot: its fin_len tokens, pad_token_id behind.
+ *   6. best = run_score[first new beam] / len_pow[s] if that beam is live; unsat[b] &= (a fin_flag is 0) || best > min fin_score.
+ *   7. done[b] = !unsat[b] || (all fin_flag && early_stopping) || all K stop; finished[r] = done[b] for the prompt's rows.
+ * A prompt that was done before the call is inert: parent = identity, plan[b][0] = -1, nothing else of it is written.
+ * plan int32 [B][4] is what tcavt_beam_reorder needs of the step: {s, or -1: nothing to do; suffix slots written so far
+ * (s > 0 ? pos[b * n] - prefix_len[b] + 1 : 0); parent is not the identity; index at which the generated part of a history starts}.
+ * trace (optional) int32 [N][B][K][3]: the K sorted candidates of this step as (parent, token, bits of acc) at trace[s][b][k];
+ * (-1, -1, 0) where fewer than K candidates exist.
+ * Three launches on the stream, capturable, no host read, no atomics.  workspace: tcavt_beam_workspace_bytes(R) bytes (0 for
+ * R <= 0), 16-byte aligned, no initial contents needed.  The caller initialises run_score = 0, live = [1, 0, ..] per prompt,
+ * fin_flag = 0, unsat = 1, done = 0, step = 0.
+ * Refused before any launch (tcavt_last_error names the argument): a null pointer (trace optional), n outside [2, 16], R not a
+ * positive multiple of n, V < 2 n or V > 262144, N < 1, hist_cap <= 0, a negative no_repeat_ngram_size, a repetition_penalty
+ * <= 0, a workspace that is too small or not 16-byte aligned. */
+typedef struct tcavt_beam_args {
+  const float* logits;               /* fp32 [R][V]; never written */
+  const int64_t* history;            /* int64 [R][hist_cap] */
+  const int32_t* hist_len;           /* int32 [R] */
+  float* run_score;                  /* fp32 [R] */
+  int32_t* live;                     /* int32 [R] */
+  int64_t* fin_tokens;               /* int64 [B][n][N] */
+  float* fin_score;                  /* fp32 [B][n] */
+  int32_t* fin_flag;                 /* int32 [B][n] */
+  int32_t* fin_len;                  /* int32 [B][n] */
+  int32_t* unsat;                    /* int32 [B] */
+  int32_t* done;                     /* int32 [B] */
+  int64_t* cur_tok;                  /* int64 [R] */
+  const int32_t* pos;                /* int32 [R]; read only here */
+  int32_t* finished;                 /* int32 [R] */
+  const int32_t* step;               /* int32 [B]; advanced by tcavt_beam_reorder */
+  const int32_t* prefix_len;         /* int32 [B]: tcavt_kv_prefix.len */
+  const float* len_pow;              /* fp32 [N] */
+  int32_t* parent;                   /* int32 [R] */
+  int32_t* plan;                     /* int32 [B][4] */
+  int32_t* trace;                    /* optional int32 [N][B][2 n][3] */
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t eos_token_id, pad_token_id; /* eos < 0: none */
+  float repetition_penalty;
+  int32_t no_repeat_ngram_size, early_stopping;
+  int32_t R, n, V, N, hist_cap;
+} tcavt_beam_args;
+
+int64_t tcavt_beam_workspace_bytes(int R);
+int tcavt_beam_select(const tcavt_beam_args* args, tcavt_stream_t stream);
+
+/* The state of a prompt's n rows follows the parents that tcavt_beam_select chose, in place and in one launch whose grid depends
+ * on the shapes alone (capturable).  For every prompt with plan[b][0] = s >= 0:
+ *   - if the parents are not the identity, row j of the new state is row parent[j] of the old for the generated part of history
+ *     (s entries from plan[b][3]) and for the suffix keys and values of ALL layers, suffix_k / suffix_v 16-bit
+ *     [n_layers][R][suffix_lmax][nkv * 64], slots 0 .. plan[b][1] - 1.  A thread owns one 16-byte piece position (k or v, layer,
+ *     prompt, slot, piece): it loads the piece from every row that is somebody's parent into registers and then stores
+ *     dst[j] = src[parent[j]] for every parent[j] != j; no other thread touches those addresses, so a swap of two beams is safe
+ *     and no second buffer is needed.  Slots beyond the written ones and pieces of other prompts are neither read nor written;
+ *   - then history[r][hist_len[r]] = cur_tok[r], hist_len[r] += 1, pos[r] += 1 if s > 0 (step 0 follows the prefill, whose pos
+ *     already names the next slot), step[b] = s + 1.
+ * The prompts' own cache is never touched.  Refused before the launch: a null pointer, n outside [2, 16], R not a positive
+ * multiple of n, hist_cap, n_layers, nkv or suffix_lmax <= 0, caches that are not 16-byte aligned. */
+typedef struct tcavt_beam_reorder_args {
+  const int32_t* parent;             /* int32 [R] */
+  const int32_t* plan;               /* int32 [B][4] */
+  const int64_t* cur_tok;            /* int64 [R] */
+  int64_t* history;                  /* int64 [R][hist_cap] */
+  int32_t* hist_len;                 /* int32 [R] */
+  int32_t* pos;                      /* int32 [R] */
+  int32_t* step;                     /* int32 [B] */
+  void* suffix_k;
+  void* suffix_v;
+  int32_t R, n, hist_cap, n_layers, nkv, suffix_lmax;
+} tcavt_beam_reorder_args;
+
+int tcavt_beam_reorder(const tcavt_beam_reorder_args* args, tcavt_stream_t stream);
+
 /* out16[b] = src16[b * L + kv_len[b] - 1]: 16-bit rows of width H */
 int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int B, int L, int H, tcavt_stream_t stream);
 

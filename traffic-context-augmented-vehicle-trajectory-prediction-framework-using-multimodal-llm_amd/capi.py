@@ -247,6 +247,23 @@ class LogprobArgs(ctypes.Structure):
         ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "V", "n_state", "hist_cap", "out_cap")]
 
 
+class BeamArgs(ctypes.Structure):
+    """Mirror of ``tcavt_beam_args`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("logits", "history", "hist_len", "run_score", "live", "fin_tokens", "fin_score", "fin_flag",
+                                        "fin_len", "unsat", "done", "cur_tok", "pos", "finished", "step", "prefix_len", "len_pow",
+                                        "parent", "plan", "trace", "workspace")] + [
+        ("workspace_bytes", c_int64), ("eos_token_id", c_int64), ("pad_token_id", c_int64), ("repetition_penalty", c_float)] + [
+        (n, ctypes.c_int32) for n in ("no_repeat_ngram_size", "early_stopping", "R", "n", "V", "N", "hist_cap")]
+
+
+class BeamReorderArgs(ctypes.Structure):
+    """Mirror of ``tcavt_beam_reorder_args`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("parent", "plan", "cur_tok", "history", "hist_len", "pos", "step", "suffix_k", "suffix_v")] + [
+        (n, ctypes.c_int32) for n in ("R", "n", "hist_cap", "n_layers", "nkv", "suffix_lmax")]
+
+
 class SlotAdmitArgs(ctypes.Structure):
     """Mirror of ``tcavt_slot_admit_args`` (include/tcavt.h)."""
 
@@ -471,9 +488,13 @@ _SIGNATURES = {
     "tcavt_logprob_workspace_bytes": [c_int, c_int],
     "tcavt_logprob_begin": [ctypes.POINTER(LogprobArgs), c_void_p],
     "tcavt_logprob_finish": [ctypes.POINTER(LogprobArgs), c_void_p],
+    "tcavt_beam_workspace_bytes": [c_int],
+    "tcavt_beam_select": [ctypes.POINTER(BeamArgs), c_void_p],
+    "tcavt_beam_reorder": [ctypes.POINTER(BeamReorderArgs), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
-             "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64}
+             "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64,
+             "tcavt_beam_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

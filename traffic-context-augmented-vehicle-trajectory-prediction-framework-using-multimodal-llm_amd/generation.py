@@ -8,12 +8,15 @@ one piece per job:
                    the sampler entry; rank_continuations orders a prompt's n continuations by them (host only)
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
   FinishedPoll     the finished flags to pinned host memory and an event wait
+  decode_loop      the N - 1 steps behind the first selection: one eager, the rest replayed, polled or not
+  beam_search      generate_batch(num_beams > 1): tcavt_beam_select / tcavt_beam_reorder around the shared-prefix decode step
   decode_args      the tcavt_decode_args of the decode step
   sample_params, eval_arithmetic, the check_* / stop_rules argument checks, cache_buffers (with the KV8 plane table)
 
 Workspace names and the order in which they are first requested are part of what tests/test_generation_trace_cpu.py pins;
 ``Prefill.reserve`` exists so that the pool can request a prefill's buffers where that order has them."""
 import contextlib
+import math
 import numbers
 import os
 from types import SimpleNamespace
@@ -252,6 +255,31 @@ class FinishedPoll:
         return self.host
 
 
+def decode_loop(one_step, N, rows, dev, use_graph, poll_every, finished):
+    """The N - 1 decode steps behind the first token selection (N > 1) -> how many ran.  Token 2 runs eagerly (also the warm-up of
+    every kernel form the step uses), the N - 2 replays of the captured step are tokens 3 .. N.  poll_every: every poll_every steps
+    the finished flags are read, and the loop ends once every row has ended (a finished row only ever writes pad: the result is
+    the same)."""
+    one_step()
+    steps_run = 1
+    if N > 2:
+        step = capture(one_step, dev, use_graph)
+        if poll_every is None:
+            for _ in range(N - 2):
+                step()
+            steps_run = N - 1
+        else:
+            poll = FinishedPoll(rows, dev)
+            while steps_run < N - 1:
+                n_now = min(int(poll_every), N - 1 - steps_run)
+                for _ in range(n_now):
+                    step()
+                steps_run += n_now
+                if bool((poll.read(finished) != 0).all()):
+                    break
+    return steps_run
+
+
 def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits, flags):
     """tcavt_decode_args of a decode step at B rows on the cache `cache` = (k, v, Lmax) or (k_codes, k_scales, v_codes,
     v_scales, Lmax); scratch buffers come from the workspace under ``tag``; ``who`` names the caller in errors.
@@ -321,14 +349,22 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
 def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
-                   num_return_sequences=1, share_prefix=False, return_logprobs=False):
+                   num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1, length_penalty=1.0,
+                   early_stopping=False):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
     share_prefix (any n >= 1): the prompts' cache ``gen.src.*`` stays where the prefill wrote it and is read in place by every
     decode step (tcavt_attn_decode_shared); one tcavt_state_fanout makes the rows' state and first logits, and the decode rows
-    own a suffix cache ``gen.sfx.*`` of their generated tokens alone."""
+    own a suffix cache ``gen.sfx.*`` of their generated tokens alone.  num_beams > 1: beam_search below."""
     who = "generate_batch"
+    if isinstance(num_beams, bool) or not isinstance(num_beams, numbers.Integral) or not 1 <= num_beams <= ops.BEAMS_MAX:
+        raise ValueError(f"generate_batch: num_beams must be an int in [1, {ops.BEAMS_MAX}], got {num_beams!r}")
+    if num_beams > 1:
+        return beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample,
+                           repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, use_graph, decode_weights, kv_cache,
+                           stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences,
+                           return_logprobs, int(num_beams), length_penalty, early_stopping)
     check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
     check_bool(who, "return_logprobs", return_logprobs)
     if not isinstance(share_prefix, bool):
@@ -417,25 +453,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                     ops.llama_decode_step_shared(a, prefix)
                 select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen")
 
-            one_step()  # token 2 eagerly (also the warm-up of every kernel form the step uses)
-            steps_run = 1
-            if N > 2:
-                step = capture(one_step, dev, use_graph)  # the N - 2 replays are tokens 3 .. N
-                if poll_every is None:
-                    for _ in range(N - 2):
-                        step()
-                    steps_run = N - 1
-                else:
-                    # every poll_every steps: read the finished flags, and out once every row has ended (out was filled with
-                    # pad and a finished row only ever writes pad: the result is the same)
-                    poll = FinishedPoll(B, dev)
-                    while steps_run < N - 1:
-                        n_now = min(int(poll_every), N - 1 - steps_run)
-                        for _ in range(n_now):
-                            step()
-                        steps_run += n_now
-                        if bool((poll.read(st.finished) != 0).all()):
-                            break
+            steps_run = decode_loop(one_step, N, B, dev, use_graph, poll_every, st.finished)
         info = None
         if return_info:
             reason, n_gen = drules.finish_reason.cpu(), drules.n_generated.cpu()
@@ -444,6 +462,118 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
         if lp is not None:
             info = dict(info or dict(steps=steps_run), **lp.host())
+    return out, info
+
+
+# --------------------------------------------------------------------------------------
+# LlamaMultiModal.generate_batch(num_beams = n > 1)
+# --------------------------------------------------------------------------------------
+def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, repetition_penalty,
+                no_repeat_ngram_size, eos_token_id, pad_token_id, use_graph, decode_weights, kv_cache, stop_token_ids, stop_sequences,
+                min_new_tokens, return_info, poll_every, num_return_sequences, return_logprobs, n, length_penalty, early_stopping):
+    """Beam search with n beams per prompt on the shared prompt cache -> (out int64 [B * r, max_new_tokens] on the device, info or
+    None), r = num_return_sequences <= n.  The prompts are prefilled at B rows (``gen.src.*``), tcavt_state_fanout makes the state
+    and first logits of the R = B * n beam rows, which own the suffix cache ``gen.sfx.*``; the first selection runs on the
+    prefill's logits, then one step is tcavt_llama_decode_step_shared -> tcavt_beam_select -> tcavt_beam_reorder.  Scores, beams,
+    the finished store and the done flags live on the device (include/tcavt.h states the semantics); the result is copied out
+    of the finished store at the end."""
+    who = "generate_batch"
+    # ---- every illegal value is refused before anything touches a device
+    check_format(who, "kv_cache", kv_cache)
+    check_format(who, "decode_weights", decode_weights)
+    if do_sample:
+        raise ValueError("generate_batch: num_beams > 1 needs do_sample=False (beam sampling is not built)")
+    if kv_cache == "fp8":
+        raise ValueError("generate_batch: num_beams > 1 reads the 16-bit prompt cache in place; kv_cache='fp8' has no beam form")
+    for name, value, unset in (("stop_token_ids", stop_token_ids, not stop_token_ids), ("stop_sequences", stop_sequences, not stop_sequences),
+                               ("min_new_tokens", min_new_tokens, min_new_tokens in (0, None))):
+        if not unset:
+            raise ValueError(f"generate_batch: {name} is not built for num_beams > 1 (got {value!r})")
+    if return_logprobs is not False:
+        raise ValueError(f"generate_batch: return_logprobs is not built for num_beams > 1 (got {return_logprobs!r})")
+    if not isinstance(early_stopping, bool):
+        raise ValueError(f"generate_batch: early_stopping must be False or True (HF's 'never' is not built), got {early_stopping!r}")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, numbers.Real) or not math.isfinite(length_penalty):
+        raise ValueError(f"generate_batch: length_penalty must be a finite number, got {length_penalty!r}")
+    V = mllm.llama_wrapper.shape.vocab
+    if V < 2 * n:
+        raise ValueError(f"generate_batch: num_beams = {n} needs a vocabulary of at least 2 * num_beams ids, got {V}")
+    r = num_return_sequences
+    if isinstance(r, bool) or not isinstance(r, numbers.Integral) or not 1 <= r <= n:
+        raise ValueError(f"generate_batch: num_return_sequences must be an int in [1, num_beams = {n}], got {num_return_sequences!r}")
+    r = int(r)
+    if poll_every is not None and int(poll_every) < 1:
+        raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
+    if input_ids is None:
+        if mllm.tokenizer is None or context_str_list is None:
+            raise NotImplementedError(
+                "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
+        enc = mllm.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
+                             return_tensors="pt")
+        input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
+    B, Lt = input_ids.shape
+    N = int(max_new_tokens)
+    if N < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    R, K = B * n, 2 * n
+    check_fp8_weights(who, decode_weights, R, "B * num_beams")
+    dev = vision_embs_batch.device
+    input_ids = input_ids.to(dev).contiguous()
+    attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
+    LW, ws = mllm.llama_wrapper, mllm._ws
+    Nq = mllm.qformer.num_query_tokens
+    Lmax = Nq + Lt + N
+    pf = Prefill(mllm, "gen.src", B, Lt, Nq + Lt, "fp16", dev)
+    with eval_arithmetic(mllm):
+        logits_src = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
+        kv_len = pf.buf("kvlen")
+        sfx_rows = max(N - 1, 1)
+        sfx = cache_buffers(ws, "gen.sfx", LW, "fp16", R, sfx_rows, dev)
+        pk, pv = pf.buf("cache")
+        prefix = capi.KvPrefix(pk.data_ptr(), pv.data_ptr(), kv_len.data_ptr(), n, Nq + Lt)
+        # ---- device-resident state: the rows', the prompts' and the finished store
+        z32 = lambda *shape: torch.zeros(*shape, dtype=I32, device=dev)  # noqa: E731
+        st = slot_state(torch.zeros(R, Lt + N, dtype=I64, device=dev), torch.empty(R, dtype=I32, device=dev), z32(B),
+                        torch.zeros(R, dtype=I64, device=dev), torch.empty(R, dtype=I32, device=dev), z32(R))
+        logits = ws.get("gen.logits", (R, V), torch.float32, dev)
+        ops.state_fanout(n, input_ids, kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+        run_score = torch.zeros(R, dtype=torch.float32, device=dev)
+        live = z32(B, n)
+        live[:, 0] = 1
+        fin_tokens = torch.full((B, n, N), int(pad_token_id), dtype=I64, device=dev)
+        fin_score, fin_flag, fin_len = torch.zeros(B, n, dtype=torch.float32, device=dev), z32(B, n), z32(B, n)
+        unsat, done, parent, plan = torch.ones(B, dtype=I32, device=dev), z32(B), z32(R), z32(B, 4)
+        len_pow = torch.tensor([float(s + 1) ** float(length_penalty) for s in range(N)], dtype=torch.float64).to(torch.float32).to(dev)
+        trace = torch.full((N, B, K, 3), -1, dtype=I32, device=dev) if return_info else None
+        bws = ws.get("gen.beam_ws", (ops.beam_workspace_bytes(R),), torch.uint8, dev)
+        sel = ops.beam_args(logits, n, N, st.history, st.hist_len, run_score, live, fin_tokens, fin_score, fin_flag, fin_len, unsat, done,
+                            st.cur, st.pos, st.finished, st.step, kv_len, len_pow, parent, plan, bws, eos_token_id, pad_token_id,
+                            repetition_penalty, no_repeat_ngram_size, early_stopping, trace=trace)
+        reo = ops.beam_reorder_args(n, parent, plan, st.cur, st.history, st.hist_len, st.pos, st.step, sfx[0], sfx[1], LW.shape.layers,
+                                    LW.shape.n_kv_heads)
+        ops.beam_select(sel)  # the first selection: from the prefill's logits
+        ops.beam_reorder(reo)
+        steps_run = 0
+        if N > 1:
+            a = decode_args(mllm, "gen", who, R, Lmax, decode_weights, sfx + (sfx_rows,), st.cur, st.pos, logits, pf.flags)
+
+            def one_step():
+                ops.llama_decode_step_shared(a, prefix)
+                ops.beam_select(sel)
+                ops.beam_reorder(reo)
+
+            steps_run = decode_loop(one_step, N, R, dev, use_graph, poll_every, st.finished)
+        out = fin_tokens[:, :r].reshape(B * r, N).contiguous()
+        info = None
+        if return_info:
+            n_gen = fin_len[:, :r].reshape(-1).cpu()
+            last = out.cpu().gather(1, (n_gen.to(I64) - 1).clamp(min=0)[:, None])[:, 0]
+            is_eos = (last == int(eos_token_id)) if eos_token_id is not None else torch.zeros_like(last, dtype=torch.bool)
+            reason = torch.where(is_eos, 1, BUDGET).to(I32)
+            t = trace[:steps_run + 1].cpu()
+            info = dict(sequences_scores=fin_score[:, :r].reshape(-1).cpu(), n_generated=n_gen, finish_reason=reason, steps=steps_run,
+                        beam_trace=dict(parent=t[..., 0].contiguous(), token=t[..., 1].contiguous(),
+                                        acc=t[..., 2].contiguous().view(torch.float32)))
     return out, info
 
 

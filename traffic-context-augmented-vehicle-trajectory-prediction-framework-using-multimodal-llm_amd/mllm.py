@@ -230,7 +230,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
-                       poll_every=None, num_return_sequences=1, share_prefix=False, return_logprobs=False):
+                       poll_every=None, num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1,
+                       length_penalty=1.0, early_stopping=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -286,13 +287,29 @@ class LlamaMultiModal(nn.Module, _Prepared):
         order, n_scored their number.  Two small launches (tcavt_logprob_begin / _finish) bracket every token selection, in the
         captured step too; the tokens, the sampler entry chosen and every other launch are those of the call without the flag.
         generation.rank_continuations orders the n continuations of a prompt by it.
+        ``num_beams`` = n with 2 <= n <= 16 ("beam search"): the deterministic search of HF's
+        generate(num_beams=n, do_sample=False), per prompt and independent of the other prompts, on the shared prompt cache
+        (share_prefix is implied; passing it makes no difference).  It needs ``do_sample=False`` (beam sampling is not built:
+        ValueError); temperature, top_k, top_p and seed are ignored as in HF; repetition_penalty and no_repeat_ngram_size act on the
+        log-probabilities with history = the prompt's valid ids + the beam's tokens; eos_token_id ends a hypothesis.  A finished
+        hypothesis scores sum of log-probabilities / length ** ``length_penalty`` (a finite float); ``early_stopping`` = False
+        (HF's heuristic: stop once no running beam can beat the worst kept hypothesis) or True (stop as soon as n hypotheses are
+        kept).  ``num_return_sequences`` = r with 1 <= r <= n returns the r best hypotheses per prompt, best first: row b * r + j is
+        hypothesis j of prompt b, EOS kept and pad_token_id behind it.  One step is tcavt_llama_decode_step_shared ->
+        tcavt_beam_select -> tcavt_beam_reorder at B * n rows; use_graph, poll_every and return_info work as above, and info holds
+        "sequences_scores" float32 [B * r], "n_generated" int32 [B * r], "finish_reason" (1 EOS, 4 ran out), "steps" and
+        "beam_trace" (per step, prompt and candidate k < 2 n: "parent", "token" int32 and "acc" float32 [steps + 1, B, 2 n]).
+        ``decode_weights="fp8"`` needs B * n <= 32.  Refused with ValueError before anything touches a device: kv_cache="fp8",
+        stop_token_ids / stop_sequences / min_new_tokens, return_logprobs=True, early_stopping="never", a vocabulary below 2 n, a
+        num_beams that is no int in [1, 16], a length_penalty that is not finite.  num_beams = 1, the default, is launch for
+        launch the call without the argument.  generate_pool does not take the three.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
             self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
             stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
-            return_logprobs)
+            return_logprobs, num_beams, length_penalty, early_stopping)
         res = self._generated_texts(out)
         return (res, info) if return_info or return_logprobs else res
 

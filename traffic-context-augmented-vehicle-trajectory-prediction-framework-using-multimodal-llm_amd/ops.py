@@ -1276,6 +1276,89 @@ def logprob_finish(args):
     check(lib().tcavt_logprob_finish(ctypes.byref(args), stream_ptr()), "tcavt_logprob_finish")
 
 
+BEAMS_MAX = 16  # beams per prompt of tcavt_beam_select / tcavt_beam_reorder
+
+
+def beam_workspace_bytes(R):
+    """Bytes of the workspace of beam_select for R = B * n decode rows."""
+    return int(capi.lib().tcavt_beam_workspace_bytes(int(R)))
+
+
+def beam_args(logits, n, N, history, hist_len, run_score, live, fin_tokens, fin_score, fin_flag, fin_len, unsat, done, cur_tok, pos,
+              finished, step, prefix_len, len_pow, parent, plan, workspace, eos_token_id, pad_token_id, repetition_penalty,
+              no_repeat_ngram_size, early_stopping, trace=None):
+    """The tcavt_beam_args of a beam search on R = B * n rows (logits fp32 [R, V]; the per-row, per-prompt and finished-store
+    tensors as include/tcavt.h lists them), each tensor checked first.  The struct names fixed device arrays: one serves every
+    step of a call, captured or not."""
+    who = "beam_select"
+    R, V = logits.shape
+    n, N = int(n), int(N)
+    if n < 1 or R % n != 0:
+        raise capi.TcavtError(f"{who}: {R} logits rows do not make prompts of n = {n} beams")
+    B = R // n
+    if history.dim() != 2 or history.shape[0] != R:
+        raise capi.TcavtError(f"{who}: history needs one row per decode row")
+    for t, dt, k, nm in ((logits, torch.float32, R * V, "logits"), (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"),
+                         (run_score, torch.float32, R, "run_score"), (live, torch.int32, R, "live"),
+                         (fin_tokens, torch.int64, R * N, "fin_tokens"), (fin_score, torch.float32, R, "fin_score"),
+                         (fin_flag, torch.int32, R, "fin_flag"), (fin_len, torch.int32, R, "fin_len"), (unsat, torch.int32, B, "unsat"),
+                         (done, torch.int32, B, "done"), (cur_tok, torch.int64, R, "cur_tok"), (pos, torch.int32, R, "pos"),
+                         (finished, torch.int32, R, "finished"), (step, torch.int32, B, "step"), (prefix_len, torch.int32, B, "prefix_len"),
+                         (len_pow, torch.float32, N, "len_pow"), (parent, torch.int32, R, "parent"), (plan, torch.int32, 4 * B, "plan"),
+                         (workspace, torch.uint8, beam_workspace_bytes(R), "workspace")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+    _req(trace, torch.int32, f"{who}.trace")
+    _need(trace, N * B * 2 * n * 3, f"{who}.trace")
+    a = capi.BeamArgs()
+    capi.bind(a, logits=logits, history=history, hist_len=hist_len, run_score=run_score, live=live, fin_tokens=fin_tokens,
+              fin_score=fin_score, fin_flag=fin_flag, fin_len=fin_len, unsat=unsat, done=done, cur_tok=cur_tok, pos=pos,
+              finished=finished, step=step, prefix_len=prefix_len, len_pow=len_pow, parent=parent, plan=plan, trace=trace,
+              workspace=workspace)
+    a.workspace_bytes = workspace.numel()
+    a.eos_token_id, a.pad_token_id = -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id)
+    a.repetition_penalty, a.no_repeat_ngram_size, a.early_stopping = float(repetition_penalty), int(no_repeat_ngram_size), int(bool(early_stopping))
+    a.R, a.n, a.V, a.N, a.hist_cap = R, n, V, N, history.shape[1]
+    return a
+
+
+def beam_select(args):
+    """One step's selection of a beam search (tcavt_beam_select): candidates, new beams, finished store, done flags, the plan."""
+    check(lib().tcavt_beam_select(ctypes.byref(args), stream_ptr()), "tcavt_beam_select")
+
+
+def beam_reorder_args(n, parent, plan, cur_tok, history, hist_len, pos, step, suffix_k, suffix_v, n_layers, nkv):
+    """The tcavt_beam_reorder_args of the same search: suffix_k / suffix_v 16-bit [n_layers, R, suffix_lmax, nkv * 64]."""
+    who = "beam_reorder"
+    R, n = parent.numel(), int(n)
+    if n < 1 or R % n != 0:
+        raise capi.TcavtError(f"{who}: {R} rows do not make prompts of n = {n} beams")
+    B = R // n
+    if history.dim() != 2 or history.shape[0] != R or suffix_k.dim() != 4 or suffix_k.shape != suffix_v.shape:
+        raise capi.TcavtError(f"{who}: history needs one row per decode row, suffix_k / suffix_v [n_layers, R, suffix_lmax, nkv * 64]")
+    if tuple(suffix_k.shape[:2]) != (n_layers, R) or suffix_k.shape[3] != nkv * 64:
+        raise capi.TcavtError(f"{who}: suffix caches of shape {tuple(suffix_k.shape)} for n_layers = {n_layers}, R = {R}, nkv = {nkv}")
+    for t, dt, k, nm in ((parent, torch.int32, R, "parent"), (plan, torch.int32, 4 * B, "plan"), (cur_tok, torch.int64, R, "cur_tok"),
+                         (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"), (pos, torch.int32, R, "pos"),
+                         (step, torch.int32, B, "step")):
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+    _req16(suffix_k, f"{who}.suffix_k")
+    _req16(suffix_v, f"{who}.suffix_v", like=suffix_k)
+    a = capi.BeamReorderArgs()
+    capi.bind(a, parent=parent, plan=plan, cur_tok=cur_tok, history=history, hist_len=hist_len, pos=pos, step=step,
+              suffix_k=suffix_k, suffix_v=suffix_v)
+    a.R, a.n, a.hist_cap, a.n_layers, a.nkv, a.suffix_lmax = R, n, history.shape[1], int(n_layers), int(nkv), suffix_k.shape[2]
+    return a
+
+
+def beam_reorder(args):
+    """Histories and suffix caches follow the parents of the last beam_select, in place (tcavt_beam_reorder)."""
+    check(lib().tcavt_beam_reorder(ctypes.byref(args), stream_ptr()), "tcavt_beam_reorder")
+
+
 def slot_admit_group(src, dst, slot, rows, src_lmax, kv_lmax, n_layers, S, nkv, prompt_ids, kv_len, n_image, max_new_value,
                      out_row_value, bad_slot_flag, history, hist_len, step, max_new, out_row, pos, finished, cur_tok):
     """The G samples of a grouped prefill move into their slots of an S-slot pool in one launch (tcavt_slot_admit_group).  src: the
