@@ -1398,6 +1398,43 @@ typedef struct tcavt_sample_args {
 
 int tcavt_sample_tokens(const tcavt_sample_args* args, tcavt_stream_t stream);
 
+/* Prompt-lookup speculative decoding: the draft.  For each of S sequences, from history[s][0 : hist_len[s]] (the prompt's text ids
+ * and everything generated so far, ending in the current token), by the rule of HF PromptLookupCandidateGenerator: for n from
+ * min(max_matching_ngram_size, len - 1) down to 1 take the last n ids; among the earlier windows that equal them take the earliest
+ * whose continuation is not empty; the draft is up to k ids right behind that window, cut at len; no match: no draft.  Ids are
+ * compared as int64, whatever their value.  With T = k + 1 and row r = s * T + j the launch writes
+ *   n_draft  int32 [S]      in [0, k]; 0 for a finished sequence (finished[s] != 0)
+ *   cur_rows int64 [S * T]  cur[s] at j = 0, draft id j - 1 at 1 <= j <= n_draft[s], pad_token_id behind that
+ *   pos_rows int32 [S * T]  pos[s] + j
+ * -- the cur_tok / pos arrays of tcavt_llama_decode_step_multi.  history int64 [S][hist_cap], hist_len (clamped into
+ * [0, hist_cap]), cur, pos and finished are the per-slot state of tcavt_sample_tokens and are only read.  One launch, no workspace.
+ * Refused before the launch: null pointers, S or hist_cap < 1, k outside [1, 255], max_matching_ngram_size < 1. */
+int tcavt_ngram_draft(const int64_t* history, int hist_cap, const int32_t* hist_len, const int64_t* cur, const int32_t* pos,
+                      const int32_t* finished, int S, int k, int max_matching_ngram_size, int64_t pad_token_id, int32_t* n_draft,
+                      int64_t* cur_rows, int32_t* pos_rows, tcavt_stream_t stream);
+
+/* Prompt-lookup speculative decoding: verify and commit.  logits row s * T + j holds the model's scores behind sequence s's
+ * current token (j = 0) or behind draft j - 1.  For j = 0 .. T - 1 the token of row (s, j) is selected and committed by
+ * tcavt_sample_tokens itself (its rows form, one launch pair per j) on sequence s's state as the passes before it left it --
+ * history extended by the accepted drafts, hist_len + j, step[s] + j, Philox row out_row[s] -- and pass j runs for sequence s only
+ * while every earlier selection equalled its draft and did not end the row (EOS, stop set, budget).  So a = the number of accepted
+ * drafts, a + 1 tokens go to out_tokens and history, hist_len / pos / step advance by a + 1, cur_tok is the last token committed,
+ * finished / finish_reason / n_generated are set at the token that ends the row, and the tokens are those of a + 1 plain steps,
+ * drawn with the same uniforms.  A finished sequence is inert (cur_tok = pad), as in the plain loop. */
+typedef struct tcavt_spec_verify_args {
+  const tcavt_sample_args* sample;   /* the slots form over the S sequences: state arrays [S], max_new and out_row set; logits fp32
+                                        [S * T][V]; workspace optional, tcavt_sample_workspace_bytes(S * T); rows, n_state and
+                                        slot_of_row are ignored */
+  const int32_t* n_draft;            /* device int32 [S], from tcavt_ngram_draft */
+  const int64_t* cur_rows;           /* device int64 [S * T], from tcavt_ngram_draft */
+  int32_t* slot_of_row;              /* scratch: device int32 [S * T + S] */
+  int32_t* drafted;                  /* device int32 [S]: += n_draft[s] per call on a live sequence */
+  int32_t* accepted;                 /* device int32 [S]: += a */
+  int32_t S, T;
+} tcavt_spec_verify_args;
+
+int tcavt_spec_verify(const tcavt_spec_verify_args* args, tcavt_stream_t stream);
+
 /* Log-probabilities of the generated tokens.  For every token that a LIVE row emits (finished == 0 before the selection; in the
  * rows form its map entry in range), the ending token (EOS / stop token) included:
  *     logprob = log_softmax(raw)[token]
@@ -1549,6 +1586,23 @@ int tcavt_gather_last(const void* src16, const int32_t* kv_len, void* out16, int
 int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos, void* out, int B, int nq, int nkv,
                       int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
 
+/* tcavt_attn_decode for T consecutive positions of each of S sequences (the verify step of prompt-lookup decoding): R = S * T rows,
+ * row r = s * T + j, on ONE cache per sequence.  ONE layer, one launch, no workspace.
+ *   qkv       16-bit [R][(nq + 2 nkv) * 64]: q | k | v of the rows' tokens, already rotated (row r at position pos_rows[s * T] + j)
+ *   k_cache / v_cache  16-bit [S][kv_lmax][nkv * 64]
+ *   pos_rows  int32 [R]; only base = pos_rows[s * T] of every sequence is read.  The caller keeps base >= 0 and
+ *             base + T - 1 <= kv_lmax - 1 (a value outside is clamped into the cache, so that no address leaves the buffers)
+ *   out       16-bit [R][nq * 64] in the three out_layouts of tcavt_attn_decode, with R in the place of its B
+ * Query (s, j, head) attends to cache rows 0 .. base - 1 of sequence s and to the new keys and values j' <= j, which it takes from
+ * the qkv rows s * T + j' as tcavt_attn_decode takes its one new key from qkv.  Cache rows base .. base + T - 1 of every kv head
+ * are overwritten with the qkv rows' k | v bits; no other byte of any cache is written and no cache row at or beyond base is read.
+ * One workgroup per (row, query head) runs the body of tcavt_attn_decode over base + j + 1 keys: every query's output is bit for
+ * bit what tcavt_attn_decode gives for that query at pos = base + j over the same keys.  T = 1 IS tcavt_attn_decode (the same
+ * launch).  Refused before the launch (tcavt_last_error names the argument): what tcavt_attn_decode refuses with R in the place
+ * of B, and T outside [1, kv_lmax]. */
+int tcavt_attn_decode_multi(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos_rows, void* out, int S, int T, int nq,
+                            int nkv, int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream);
+
 /* tcavt_attn_decode for R = B * n rows, n continuations per prompt (row r = b * n + j), that read their prompt's keys and values
  * in place: ONE layer, one launch, no workspace.
  *   qkv        16-bit [R][(nq + 2 nkv) * 64]: q | k | v of the rows' new tokens, already rotated
@@ -1671,6 +1725,15 @@ int tcavt_llama_decode_step(const tcavt_decode_args* args, tcavt_stream_t stream
  * Refused before anything is launched, beyond what tcavt_llama_decode_step refuses: a null prefix, k, v or len; the kv8 planes
  * together with a prefix; n or lmax < 1; B % n != 0; rope_L < lmax + kv_lmax; kv_lmax > TCAVT_ATTN_DECODE_SHARED_MAX_SUFFIX. */
 int tcavt_llama_decode_step_shared(const tcavt_decode_args* args, const tcavt_kv_prefix* prefix, tcavt_stream_t stream);
+
+/* tcavt_llama_decode_step for R = args->B rows that are T consecutive positions of each of R / T sequences (row r = s * T + j:
+ * sequence s, offset j) on one cache per sequence: one step yields the logits of T positions.  args is the struct of
+ * tcavt_llama_decode_step, unchanged in layout, read as follows: cur_tok / pos are the R-row arrays that tcavt_ngram_draft writes
+ * (pos[s * T + j] = pos[s * T] + j), k_cache / v_cache are [n_layers][R / T][kv_lmax][nkv * 64].  Every layer's attention is
+ * tcavt_attn_decode_multi; every other launch of the step is that of tcavt_llama_decode_step at R rows.
+ * Refused before anything is launched, beyond what tcavt_llama_decode_step refuses: T < 1, R % T != 0, R > 32, T > kv_lmax, the
+ * kv8 planes, rope_L < kv_lmax. */
+int tcavt_llama_decode_step_multi(const tcavt_decode_args* args, int T, tcavt_stream_t stream);
 
 /* Fragment-major copy of a 16-bit weight matrix W [N][ldw] (N % 16 == 0, K % 32 == 0) for the skinny form of tcavt_gemm_bf16
  * (tcavt_gemm_args.w_layout = TCAVT_W_FRAG16): out holds N * K elements; block b (rows 16 b .. 16 b + 15), k-step j (columns

@@ -239,6 +239,13 @@ class SampleArgs(ctypes.Structure):
                     "rows", "V", "n_state", "hist_cap", "out_cap", "advance_pos")]
 
 
+class SpecVerifyArgs(ctypes.Structure):
+    """Mirror of ``tcavt_spec_verify_args`` (include/tcavt.h)."""
+
+    _fields_ = [("sample", ctypes.POINTER(SampleArgs))] + [(n, c_void_p) for n in (
+        "n_draft", "cur_rows", "slot_of_row", "drafted", "accepted")] + [("S", ctypes.c_int32), ("T", ctypes.c_int32)]
+
+
 class LogprobArgs(ctypes.Structure):
     """Mirror of ``tcavt_logprob_args`` (include/tcavt.h)."""
 
@@ -491,6 +498,12 @@ _SIGNATURES = {
     "tcavt_beam_workspace_bytes": [c_int],
     "tcavt_beam_select": [ctypes.POINTER(BeamArgs), c_void_p],
     "tcavt_beam_reorder": [ctypes.POINTER(BeamReorderArgs), c_void_p],
+    "tcavt_ngram_draft": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p,
+                          c_void_p, c_void_p],
+    "tcavt_attn_decode_multi": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                c_int, c_void_p],
+    "tcavt_llama_decode_step_multi": [ctypes.POINTER(DecodeArgs), c_int, c_void_p],
+    "tcavt_spec_verify": [ctypes.POINTER(SpecVerifyArgs), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64,

@@ -1,6 +1,7 @@
-// Decode attention of text generation (include/tcavt.h: tcavt_attn_decode, tcavt_kv_store8, tcavt_attn_decode8): the one new query of
-// every sample over its cached keys, on the 16-bit cache or on the opt-in FP8 cache ("KV8"), and the KV8 store of a prefill.  The
-// decode step (csrc/generate.hip) calls these once per layer; the shared-prefix form is csrc/attn_decode_shared.hip.
+// Decode attention of text generation (include/tcavt.h: tcavt_attn_decode, tcavt_attn_decode_multi, tcavt_kv_store8,
+// tcavt_attn_decode8): the one new query of every sample over its cached keys -- or, in the multi form, T consecutive new queries of
+// every sequence --, on the 16-bit cache or on the opt-in FP8 cache ("KV8"), and the KV8 store of a prefill.  The decode step
+// (csrc/generate.hip) calls these once per layer; the shared-prefix form is csrc/attn_decode_shared.hip.
 #include "common.hpp"
 
 namespace tcavt {
@@ -19,28 +20,45 @@ namespace tcavt {
 // PFV: the first round of value rows is requested before the softmax statistics meet (its latency passes under the reductions
 // and the barrier).  Costs 32 registers, i.e. resident waves: a gain when the grid is one workgroup per CU (B = 8: 1.138 ->
 // 1.129 ms per step), a loss when several workgroups per CU hide each other's latencies anyway (B = 32: 1.45 -> 1.56).
-template <bool F16, bool PFV>
+// MULTI (tcavt_attn_decode_multi): T queries per sequence, row b = s * T + j of qkv on the cache of sequence s = b / T.  With
+// base = pos[s * T], query j attends the cached keys 0 .. base - 1 and the new keys 0 .. j of its sequence, which it takes from the
+// qkv rows s * T .. s * T + j where the plain form takes its one new key from row b; its own k | v go to cache row base + j.  The
+// key count n = base + j + 1 fixes the splits, so the arithmetic of a query is the plain form's at pos = base + j, bit for bit.  A
+// workgroup reads cache rows < base only and writes row base + j only: the workgroups of a launch need no order among themselves.
+template <bool F16, bool PFV, bool MULTI = false>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                            bf16_t* __restrict__ vc, const int* __restrict__ pos,
                                                            bf16_t* __restrict__ out, int lmax, int nq, int nkv, float scale,
-                                                           int KS, int out_frag) {
+                                                           int KS, int out_frag, int T) {
   extern __shared__ float sc[];  // [lmax] scores | [KS][2] (max, sum) | [KS][64] partial outputs
   const int group = nq / nkv;
   const int b = blockIdx.x / nq, head = blockIdx.x % nq, kvh = head / group;
   const int lane = threadIdx.x & 63, ks = threadIdx.x >> 6;
   const int g = lane >> 3, c = lane & 7;
-  const int n = min(pos[b] + 1, lmax);
+  const int cb = MULTI ? b / T : b;  // whose cache
+  // MULTI: the first position whose key comes from qkv (clamped into the cache: the caller keeps base + T <= lmax)
+  const int base = MULTI ? min(max(pos[cb * T], 0), lmax - 1) : 0;
+  const int n = MULTI ? min(base + (b - cb * T) + 1, lmax) : min(pos[b] + 1, lmax);
   const int ld = (nq + 2 * nkv) * 64, w = nkv * 64;
-  const bf16_t* kb = kc + (long)b * lmax * w + kvh * 64;
-  const bf16_t* vb = vc + (long)b * lmax * w + kvh * 64;
+  const bf16_t* kb = kc + (long)cb * lmax * w + kvh * 64;
+  const bf16_t* vb = vc + (long)cb * lmax * w + kvh * 64;
   const int jn = n - 1;  // the new token's position
   const bf16_t* knew = qkv + (long)b * ld + (nq + kvh) * 64;
   const bf16_t* vnew = qkv + (long)b * ld + (nq + nkv + kvh) * 64;
   if (head % group == 0 && ks == 0 && lane < 16) {  // append: 8 lanes x 16 bytes of k, 8 of v
     const int cc = (lane & 7) * 8;
-    if (lane < 8) *reinterpret_cast<u32x4*>(kc + ((long)b * lmax + jn) * w + kvh * 64 + cc) = *reinterpret_cast<const u32x4*>(knew + cc);
-    else *reinterpret_cast<u32x4*>(vc + ((long)b * lmax + jn) * w + kvh * 64 + cc) = *reinterpret_cast<const u32x4*>(vnew + cc);
+    if (lane < 8) *reinterpret_cast<u32x4*>(kc + ((long)cb * lmax + jn) * w + kvh * 64 + cc) = *reinterpret_cast<const u32x4*>(knew + cc);
+    else *reinterpret_cast<u32x4*>(vc + ((long)cb * lmax + jn) * w + kvh * 64 + cc) = *reinterpret_cast<const u32x4*>(vnew + cc);
   }
+  // key / value row j <= jn: the plain form has one new row, MULTI the rows base .. jn of the sequence's qkv block (j - base <= b - cb * T)
+  auto krow = [&](int j) -> const bf16_t* {
+    if constexpr (MULTI) return j >= base ? qkv + ((long)cb * T + (j - base)) * ld + (nq + kvh) * 64 : kb + (long)j * w;
+    else return j == jn ? knew : kb + (long)j * w;
+  };
+  auto vrow = [&](int j) -> const bf16_t* {
+    if constexpr (MULTI) return j >= base ? qkv + ((long)cb * T + (j - base)) * ld + (nq + nkv + kvh) * 64 : vb + (long)j * w;
+    else return j == jn ? vnew : vb + (long)j * w;
+  };
   float* s = sc;
   float* st = sc + lmax;
   float* po = st + KS * 2;
@@ -61,7 +79,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const bf16_t* __restr
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int j = min(jb + i * 8 + g, jn);
-      kr[i] = *reinterpret_cast<const u32x4*>((j == jn ? knew : kb + (long)j * w) + c * 8);
+      kr[i] = *reinterpret_cast<const u32x4*>(krow(j) + c * 8);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -86,7 +104,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const bf16_t* __restr
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int j = min(j0 + i * 8 + g, jn);
-      vr0[i] = *reinterpret_cast<const u32x4*>((j == jn ? vnew : vb + (long)j * w) + c * 8);
+      vr0[i] = *reinterpret_cast<const u32x4*>(vrow(j) + c * 8);
     }
   }
   mx = wave_max(mx);
@@ -110,7 +128,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const bf16_t* __restr
         vr[i] = vr0[PFV ? i : 0];
       } else {
         const int j = min(jb + i * 8 + g, jn);
-        vr[i] = *reinterpret_cast<const u32x4*>((j == jn ? vnew : vb + (long)j * w) + c * 8);
+        vr[i] = *reinterpret_cast<const u32x4*>(vrow(j) + c * 8);
       }
     }
 #pragma unroll
@@ -381,8 +399,36 @@ extern "C" int tcavt_attn_decode(const void* qkv, void* k_cache, void* v_cache, 
                                   : (pfv ? attn_decode_kernel<false, true> : attn_decode_kernel<false, false>);
   hipLaunchKernelGGL(kfn, dim3(B * nq), dim3(KS * 64), lds, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
                      static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), pos, static_cast<bf16_t*>(out), kv_lmax, nq, nkv, scale,
-                     KS, out_layout);
+                     KS, out_layout, 1);
   TCAVT_CHECK_LAUNCH("attn_decode");
+  return TCAVT_OK;
+}
+
+// T queries per sequence on one cache per sequence (the verify step of prompt-lookup decoding): the plain launch with R = S * T rows
+// in the place of B; T = 1 is tcavt_attn_decode itself.
+extern "C" int tcavt_attn_decode_multi(const void* qkv, void* k_cache, void* v_cache, const int32_t* pos_rows, void* out, int S, int T,
+                                       int nq, int nkv, int kv_lmax, float scale, int dtype16, int out_layout, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(qkv && k_cache && v_cache && pos_rows && out, "attn_decode_multi: null pointer");
+  TCAVT_CHECK_ARG(is16(dtype16), "attn_decode_multi: dtype16 must be TCAVT_F16 or TCAVT_BF16");
+  TCAVT_CHECK_ARG(S > 0 && nq > 0 && nkv > 0 && nq % nkv == 0 && nq / nkv <= 8, "attn_decode_multi: bad shape (S, nq, nkv > 0, nq %% nkv == 0, nq / nkv <= 8)");
+  TCAVT_CHECK_ARG(T >= 1 && T <= kv_lmax, "attn_decode_multi: T = %d must be in [1, kv_lmax = %d]", T, kv_lmax);
+  TCAVT_CHECK_ARG((long)S * T * nq <= 0x7fffffffL, "attn_decode_multi: S * T * nq too large");
+  TCAVT_CHECK_ARG(kv_lmax >= 1, "attn_decode_multi: kv_lmax must be >= 1");
+  int KS;
+  size_t lds;
+  TCAVT_CHECK_ARG(attn_decode_rule(kv_lmax, &KS, &lds), "attn_decode_multi: kv_lmax = %d too long for the score buffer", kv_lmax);
+  const int R = S * T;
+  TCAVT_CHECK_ARG(out_layout == 0 || (out_layout == 1 && R <= 32 && (nq * 64) % 256 == 0) || (out_layout == 2 && R <= 8),
+                  "attn_decode_multi: out_layout must be 0, 1 (S * T <= 32, nq * 64 %% 256 == 0) or 2 (S * T <= 8)");
+  TCAVT_CHECK_ARG(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_decode_multi: qkv and the caches must be 16-byte aligned");
+  if (T == 1) return tcavt_attn_decode(qkv, k_cache, v_cache, pos_rows, out, S, nq, nkv, kv_lmax, scale, dtype16, out_layout, stream);
+  const bool pfv = R * nq <= 512;  // (tcavt_attn_decode's rule)
+  auto kfn = dtype16 == TCAVT_F16 ? (pfv ? attn_decode_kernel<true, true, true> : attn_decode_kernel<true, false, true>)
+                                  : (pfv ? attn_decode_kernel<false, true, true> : attn_decode_kernel<false, false, true>);
+  hipLaunchKernelGGL(kfn, dim3(R * nq), dim3(KS * 64), lds, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), pos_rows, static_cast<bf16_t*>(out), kv_lmax, nq, nkv,
+                     scale, KS, out_layout, T);
+  TCAVT_CHECK_LAUNCH("attn_decode_multi");
   return TCAVT_OK;
 }
 

@@ -16,6 +16,8 @@
 // The projections reuse the MFMA GEMM (M = batch rows: weight-streaming, HBM-bound); RMSNorm is fused exactly as in the
 // prefill (csrc/stack.hip).  This file is the step itself; its attention is csrc/attn_decode.hip (attn_decode_shared.hip), the
 // selection csrc/sampler.hip, and the kernels that move a prefilled cache into a decode batch csrc/kv_move.hip.
+// tcavt_llama_decode_step_multi is the same step on T consecutive positions per sequence (prompt-lookup speculative decoding: the
+// draft and the verification around it are csrc/spec.hip).
 #include "common.hpp"
 
 namespace tcavt {
@@ -49,8 +51,9 @@ extern "C" int tcavt_gather_last(const void* src16, const int32_t* kv_len, void*
   return TCAVT_OK;
 }
 
-// The decode step; px != NULL: the rows read their prompts' cache in place (tcavt_llama_decode_step_shared).
-static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* px, tcavt_stream_t stream) {
+// The decode step; px != NULL: the rows read their prompts' cache in place (tcavt_llama_decode_step_shared); T > 0: the B rows are
+// T consecutive positions of each of B / T sequences on one cache per sequence (tcavt_llama_decode_step_multi).
+static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* px, tcavt_stream_t stream, int T = 0) {
   TCAVT_CHECK_ARG(a && a->layers && a->gamma_final && a->rope_cos && a->rope_sin && a->table && a->txt_mod && a->cur_tok && a->pos &&
                       a->h16 && a->part && a->qkv && a->att && a->act && a->x16 && a->logits && a->bad_id_flag,
                   "llama_decode_step: null pointer");
@@ -60,6 +63,13 @@ static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* p
                   "llama_decode_step: the four kv8 planes come together");
   TCAVT_CHECK_ARG(!kv8 || (!a->k_cache && !a->v_cache), "llama_decode_step: the kv8 planes and k_cache / v_cache exclude each other");
   TCAVT_CHECK_ARG(kv8 || (a->k_cache && a->v_cache), "llama_decode_step: null pointer (k_cache / v_cache, or the four kv8 planes)");
+  if (T > 0) {
+    TCAVT_CHECK_ARG(!kv8, "llama_decode_step_multi: the kv8 planes are not supported");
+    TCAVT_CHECK_ARG(a->B > 0 && a->B % T == 0, "llama_decode_step_multi: B = %d must be a multiple of T = %d", a->B, T);
+    TCAVT_CHECK_ARG(a->B <= 32, "llama_decode_step_multi: B = %d rows exceed 32", a->B);
+    TCAVT_CHECK_ARG(T <= a->kv_lmax, "llama_decode_step_multi: T = %d exceeds kv_lmax = %d", T, a->kv_lmax);
+    TCAVT_CHECK_ARG(a->rope_L >= a->kv_lmax, "llama_decode_step_multi: rope_L = %d must be >= kv_lmax = %d", a->rope_L, a->kv_lmax);
+  }
   // the shared prompt cache (tcavt_attn_decode_shared): k_cache / v_cache then hold the rows' suffixes only
   if (px) {
     TCAVT_CHECK_ARG(!kv8, "llama_decode_step: prefix and the kv8 planes exclude each other");
@@ -101,7 +111,7 @@ static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* p
   // (a->h == NULL: the residual stream is the 16-bit h16 itself, as in tcavt_llama_stack_forward)
   TCAVT_TRY(embed_fuse_impl(a->table, a->cur_tok, a->txt_mod /* unused: Nq = 0 */, a->txt_mod, a->txt_mod, a->h, B, 0, 1, H, a->V,
                             a->bad_id_flag, dt, a->h16, a->part, np_in, ss_, al, stream));
-  const size_t per_layer = (size_t)B * a->kv_lmax * nkv * 64;
+  const size_t per_layer = (size_t)(T > 0 ? B / T : B) * a->kv_lmax * nkv * 64;
   {
     int KS;
     size_t lds;
@@ -151,7 +161,8 @@ static int decode_step_impl(const tcavt_decode_args* a, const tcavt_kv_prefix* p
     } else {
       bf16_t* kc = static_cast<bf16_t*>(a->k_cache) + li * per_layer;
       bf16_t* vc = static_cast<bf16_t*>(a->v_cache) + li * per_layer;
-      TCAVT_TRY(tcavt_attn_decode(a->qkv, kc, vc, a->pos, a->att, B, nq, nkv, a->kv_lmax, 0.125f, dt, al, stream));
+      if (T > 0) TCAVT_TRY(tcavt_attn_decode_multi(a->qkv, kc, vc, a->pos, a->att, B / T, T, nq, nkv, a->kv_lmax, 0.125f, dt, al, stream));
+      else TCAVT_TRY(tcavt_attn_decode(a->qkv, kc, vc, a->pos, a->att, B, nq, nkv, a->kv_lmax, 0.125f, dt, al, stream));
     }
     {
       tcavt_gemm_args g = {};
@@ -203,4 +214,10 @@ extern "C" int tcavt_llama_decode_step(const tcavt_decode_args* a, tcavt_stream_
 extern "C" int tcavt_llama_decode_step_shared(const tcavt_decode_args* a, const tcavt_kv_prefix* prefix, tcavt_stream_t stream) {
   TCAVT_CHECK_ARG(prefix, "llama_decode_step_shared: prefix is a null pointer");
   return decode_step_impl(a, prefix, stream);
+}
+
+extern "C" int tcavt_llama_decode_step_multi(const tcavt_decode_args* a, int T, tcavt_stream_t stream) {
+  TCAVT_CHECK_ARG(a, "llama_decode_step_multi: args is a null pointer");
+  TCAVT_CHECK_ARG(T >= 1, "llama_decode_step_multi: T = %d must be >= 1", T);
+  return decode_step_impl(a, nullptr, stream, T);
 }

@@ -9,6 +9,8 @@ one piece per job:
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
   FinishedPoll     the finished flags to pinned host memory and an event wait
   decode_loop      the N - 1 steps behind the first selection: one eager, the rest replayed, polled or not
+  check_prompt_lookup, prompt_lookup_step   generate_batch(prompt_lookup_num_tokens = k): the argument checks, and the step
+                   tcavt_ngram_draft -> tcavt_llama_decode_step_multi -> tcavt_spec_verify that commits 1 .. k + 1 tokens
   beam_search      generate_batch(num_beams > 1): tcavt_beam_select / tcavt_beam_reorder around the shared-prefix decode step
   decode_args      the tcavt_decode_args of the decode step
   sample_params, eval_arithmetic, the check_* / stop_rules argument checks, cache_buffers (with the KV8 plane table)
@@ -344,20 +346,72 @@ def decode_args(mllm, tag, who, B, Lmax, decode_weights, cache, cur, pos, logits
 
 
 # --------------------------------------------------------------------------------------
+# generate_batch(prompt_lookup_num_tokens = k): prompt-lookup speculative decoding
+# --------------------------------------------------------------------------------------
+PROMPT_LOOKUP_MAX_TOKENS, PROMPT_LOOKUP_MAX_NGRAM, PROMPT_LOOKUP_MAX_ROWS, PROMPT_LOOKUP_POLL = 7, 8, 32, 4
+
+
+def check_prompt_lookup(who, k, m, kv_cache, share_prefix, num_beams, return_logprobs, stop_sequences):
+    """The arguments of a call with prompt_lookup_num_tokens = k set -> (k, m) as ints.  Nothing here touches a device."""
+    for name, v, hi in (("prompt_lookup_num_tokens", k, PROMPT_LOOKUP_MAX_TOKENS), ("max_matching_ngram_size", m, PROMPT_LOOKUP_MAX_NGRAM)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v <= hi:
+            raise ValueError(f"{who}: {name} must be an int in [1, {hi}], got {v!r}")
+    for name, bad, why in (("kv_cache='fp8'", kv_cache == "fp8", "the multi-position attention reads the 16-bit cache"),
+                           ("share_prefix=True", share_prefix is True, "the multi-position attention has no shared-prefix form"),
+                           ("num_beams > 1", num_beams != 1, "beam search has its own step"),
+                           ("return_logprobs=True", return_logprobs is True, "the log-probability bracket is per single step"),
+                           ("stop_sequences", bool(stop_sequences), "a stop sequence can end inside a block of drafts")):
+        if bad:
+            raise ValueError(f"{who}: prompt_lookup_num_tokens is not built for {name} ({why})")
+    return int(k), int(m)
+
+
+def prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out, drules, pad_token_id, flags):
+    """-> (one_step, drafted, accepted).  one_step: tcavt_ngram_draft (every sequence's draft of up to k ids and the S * (k + 1)
+    token / position rows) -> tcavt_llama_decode_step_multi (the logits of all k + 1 positions in one step) -> tcavt_spec_verify
+    (select every position with the plain sampler on the state the plain loop has there, commit while it equals the draft).
+    The device arrays are fixed for the call, so the captured step stays valid.  Buffers under ``gen.pl.*``."""
+    ws, LW, dev = mllm._ws, mllm.llama_wrapper, out.device
+    S, T = out.shape[0], k + 1
+    R = S * T
+    n_draft, cur_rows, pos_rows = ws.get("gen.pl.n_draft", (S,), I32, dev), ws.get("gen.pl.cur", (R,), I64, dev), ws.get("gen.pl.pos", (R,), I32, dev)
+    scratch = ws.get("gen.pl.slot", (R + S,), I32, dev, zero=True)
+    drafted, accepted = torch.zeros(S, dtype=I32, device=dev), torch.zeros(S, dtype=I32, device=dev)
+    logits = ws.get("gen.pl.logits", (R, LW.shape.vocab), torch.float32, dev)
+    sws = sample_workspace(ws, "gen.pl.sample_ws", R, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
+    a = decode_args(mllm, "gen.pl", who, R, Lmax, decode_weights, cache, cur_rows, pos_rows, logits, flags)
+    v = ops.spec_verify_args(logits, T, n_draft, cur_rows, scratch, drafted, accepted, st.history, st.hist_len, sp, st.step, st.max_new,
+                             st.out_row, st.cur, st.pos, st.finished, out, advance_pos=True, workspace=sws, stop=drules)
+
+    def one_step():
+        ops.ngram_draft(st.history, st.hist_len, st.cur, st.pos, st.finished, k, m, pad_token_id, n_draft, cur_rows, pos_rows)
+        ops.llama_decode_step_multi(a, T)
+        ops.spec_verify(v)
+
+    return one_step, drafted, accepted
+
+
+# --------------------------------------------------------------------------------------
 # LlamaMultiModal.generate_batch
 # --------------------------------------------------------------------------------------
 def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
                    num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1, length_penalty=1.0,
-                   early_stopping=False):
+                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
     share_prefix (any n >= 1): the prompts' cache ``gen.src.*`` stays where the prefill wrote it and is read in place by every
     decode step (tcavt_attn_decode_shared); one tcavt_state_fanout makes the rows' state and first logits, and the decode rows
-    own a suffix cache ``gen.sfx.*`` of their generated tokens alone.  num_beams > 1: beam_search below."""
+    own a suffix cache ``gen.sfx.*`` of their generated tokens alone.  num_beams > 1: beam_search below.
+    prompt_lookup_num_tokens = k: the cache has k more rows, the state is the per-slot form (step [S], max_new = N, out_row[s] = s:
+    the same Philox rows and the same tokens as the batch form) and a step is prompt_lookup_step above; None is the call without."""
     who = "generate_batch"
+    k = m = None
+    if prompt_lookup_num_tokens is not None:  # (before anything touches a device, and before the beam search takes over)
+        k, m = check_prompt_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, kv_cache, share_prefix, num_beams,
+                                   return_logprobs, stop_sequences)
     if isinstance(num_beams, bool) or not isinstance(num_beams, numbers.Integral) or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate_batch: num_beams must be an int in [1, {ops.BEAMS_MAX}], got {num_beams!r}")
     if num_beams > 1:
@@ -392,11 +446,17 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     check_format(who, "decode_weights", decode_weights)
     src_B, B = B, B * n  # the prefill's rows; from here on B counts decode rows (n continuations per prompt, prompt-major)
     check_fp8_weights(who, decode_weights, B, "B" if n == 1 else "B * num_return_sequences")
+    if k is not None:
+        if B * (k + 1) > PROMPT_LOOKUP_MAX_ROWS:
+            raise ValueError(f"{who}: prompt_lookup_num_tokens = {k} needs sequences * (k + 1) <= {PROMPT_LOOKUP_MAX_ROWS} decode rows, "
+                             f"got {B} * {k + 1}")
+        if not 0 <= int(pad_token_id) < mllm.llama_wrapper.shape.vocab:  # (the rows behind a draft feed the pad token to the step)
+            raise ValueError(f"{who}: prompt_lookup_num_tokens needs pad_token_id inside [0, vocab), got {pad_token_id}")
     dev = vision_embs_batch.device
     input_ids = input_ids.to(dev).contiguous()
     attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
     Nq = mllm.qformer.num_query_tokens
-    Lmax = Nq + Lt + N
+    Lmax = Nq + Lt + N + (k or 0)  # (a verify step writes k rows beyond the last position a row can reach)
     # n > 1: the prompts alone, into a cache of the prompt's own 16 + Lt rows (the width of the pool's one-sample prefill)
     own_cache = n == 1 and not share_prefix  # the prefill writes straight into the decode rows' cache
     pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev) if own_cache else Prefill(mllm, "gen.src", src_B, Lt, Nq + Lt, kv_cache, dev)
@@ -433,6 +493,9 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             else:
                 ops.kv_fanout(pf.buf("cache"), cache[:-1], n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids,
                               kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+        if k is not None:  # the per-slot form of the same state: every row has its own step word and the budget N
+            st.step, st.max_new = torch.zeros(B, dtype=I32, device=dev), torch.full((B,), N, dtype=I32, device=dev)
+            st.out_row = torch.arange(B, dtype=I64, device=dev)
         out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
         sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
                            pad_token_id, seed)
@@ -443,7 +506,13 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         lp = LogprobRecord(mllm._ws, out) if return_logprobs else None  # (the flag alone does not change the sampler entry)
         select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen")
         steps_run = 0
-        if N > 1:
+        drafted = accepted = None
+        if N > 1 and k is not None:
+            one_step, drafted, accepted = prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out, drules,
+                                                             int(pad_token_id), pf.flags)
+            steps_run = decode_loop(one_step, N, B, dev, use_graph, PROMPT_LOOKUP_POLL if poll_every is None else poll_every,
+                                    st.finished)
+        elif N > 1:
             a = decode_args(mllm, "gen", who, B, Lmax, decode_weights, cache, st.cur, st.pos, logits, pf.flags)
 
             def one_step():
@@ -460,6 +529,9 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
             reason[ran_out], n_gen[ran_out] = BUDGET, N
             info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
+            if k is not None:
+                zero = torch.zeros(B, dtype=I32)
+                info.update(drafted=zero if drafted is None else drafted.cpu(), accepted=zero.clone() if accepted is None else accepted.cpu())
         if lp is not None:
             info = dict(info or dict(steps=steps_run), **lp.host())
     return out, info

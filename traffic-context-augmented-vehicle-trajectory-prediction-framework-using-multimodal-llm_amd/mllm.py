@@ -230,8 +230,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        attention_mask=None, do_sample=True, temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2,
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
-                       poll_every=None, num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1,
-                       length_penalty=1.0, early_stopping=False):
+                       poll_every=None, num_return_sequences=1, share_prefix=False, prompt_lookup_num_tokens=None,
+                       max_matching_ngram_size=2, return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -303,13 +303,29 @@ class LlamaMultiModal(nn.Module, _Prepared):
         stop_token_ids / stop_sequences / min_new_tokens, return_logprobs=True, early_stopping="never", a vocabulary below 2 n, a
         num_beams that is no int in [1, 16], a length_penalty that is not finite.  num_beams = 1, the default, is launch for
         launch the call without the argument.  generate_pool does not take the three.
+        ``prompt_lookup_num_tokens`` = k with 1 <= k <= 7 (HF's name; DESIGN.md section 7, "prompt-lookup decoding"): speculative
+        decoding without a draft model.  Every step drafts up to k tokens per sequence -- the continuation of the earliest earlier
+        occurrence of the sequence's last n ids, n from ``max_matching_ngram_size`` (1 .. 8) down to 1, in [the prompt's ids | the
+        tokens so far] (tcavt_ngram_draft) --, runs the decoder on all k + 1 positions of every sequence at once
+        (tcavt_llama_decode_step_multi, S * (k + 1) <= 32 rows, S = B * num_return_sequences) and commits the drafts the model
+        would have chosen itself plus its own next token (tcavt_spec_verify): 1 .. k + 1 tokens per step.  Every position is
+        selected by the plain sampler on the state the plain loop has at that token, with the uniform the plain loop draws there,
+        so the tokens are those of the call without the argument wherever the decode step's logits do not depend on the row count
+        (DESIGN.md states what was measured), sampled or greedy.  The loop runs at most max_new_tokens - 1 steps and reads the
+        finished flags every ``poll_every`` steps (default 4 here); return_info adds "drafted" and "accepted" (host int32 per
+        sequence) and "steps" counts the steps run.  decode_weights="fp8" and num_return_sequences > 1 work as above.  Refused with
+        ValueError before anything touches a device: kv_cache="fp8", share_prefix=True, num_beams > 1, return_logprobs=True,
+        stop_sequences, S * (k + 1) > 32, a pad_token_id outside the vocabulary (the rows behind a draft feed it to the step), a k
+        or max_matching_ngram_size outside its range.  None, the default, is launch for launch the call without the argument.
+        generate_pool does not take the two.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
             self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
             stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
-            return_logprobs, num_beams, length_penalty, early_stopping)
+            return_logprobs, num_beams, length_penalty, early_stopping, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size)
         res = self._generated_texts(out)
         return (res, info) if return_info or return_logprobs else res
 

@@ -1530,6 +1530,92 @@ def llama_decode_step_shared(args, prefix):
     check(lib().tcavt_llama_decode_step_shared(ctypes.byref(args), ctypes.byref(prefix), stream_ptr()), "tcavt_llama_decode_step_shared")
 
 
+def llama_decode_step_multi(args, T):
+    """llama_decode_step for args.B = S * T rows, T consecutive positions of each of S sequences on one cache per sequence
+    (tcavt_llama_decode_step_multi).  args.cur_tok / pos are the row arrays ngram_draft writes; args.k_cache / v_cache hold S
+    sequences per layer."""
+    check(lib().tcavt_llama_decode_step_multi(ctypes.byref(args), int(T), stream_ptr()), "tcavt_llama_decode_step_multi")
+
+
+def attn_decode_multi(qkv, k_cache, v_cache, pos_rows, out, S, T, nq, nkv, kv_lmax, scale, out_layout=0):
+    """attn_decode for T consecutive positions of each of S sequences on ONE layer's cache [S, kv_lmax, nkv * 64]
+    (tcavt_attn_decode_multi): row r = s * T + j of qkv attends cache rows < base = pos_rows[s * T] and the new keys of rows
+    s * T .. r, taken from qkv; cache rows base .. base + T - 1 receive the rows' k | v.  Bit for bit attn_decode per query."""
+    who = "attn_decode_multi"
+    R = S * T
+    _req16(qkv, f"{who}.qkv")
+    for t, nm in ((k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
+        _req16(t, f"{who}.{nm}", like=qkv)
+    _req(pos_rows, torch.int32, f"{who}.pos_rows")
+    _need(qkv, R * (nq + 2 * nkv) * 64, f"{who}.qkv")
+    _need(k_cache, S * kv_lmax * nkv * 64, f"{who}.k_cache")
+    _need(v_cache, S * kv_lmax * nkv * 64, f"{who}.v_cache")
+    _need(pos_rows, R, f"{who}.pos_rows")
+    rows = R if out_layout == 0 else 8 if out_layout == 2 else 16 * ((R + 15) // 16)
+    _need(out, rows * nq * 64, f"{who}.out")
+    check(lib().tcavt_attn_decode_multi(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(pos_rows), ptr(out), S, T, nq, nkv, kv_lmax, scale,
+                                        _DT[qkv.dtype], int(out_layout), stream_ptr()), "tcavt_attn_decode_multi")
+
+
+def ngram_draft(history, hist_len, cur, pos, finished, k, max_matching_ngram_size, pad_token_id, n_draft, cur_rows, pos_rows):
+    """Prompt-lookup draft of every sequence in one launch (tcavt_ngram_draft): from history int64 [S, cap] / hist_len and the
+    per-slot state cur, pos, finished -> n_draft int32 [S], cur_rows int64 [S * (k + 1)], pos_rows int32 [S * (k + 1)]."""
+    who = "ngram_draft"
+    if history.dim() != 2:
+        raise capi.TcavtError(f"{who}: history needs one row per sequence")
+    S, T = history.shape[0], int(k) + 1
+    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (cur, torch.int64, S, "cur"),
+                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (n_draft, torch.int32, S, "n_draft"),
+                         (cur_rows, torch.int64, S * T, "cur_rows"), (pos_rows, torch.int32, S * T, "pos_rows")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, n, f"{who}.{nm}")
+    check(lib().tcavt_ngram_draft(ptr(history), history.shape[1], ptr(hist_len), ptr(cur), ptr(pos), ptr(finished), S, int(k),
+                                  int(max_matching_ngram_size), int(pad_token_id), ptr(n_draft), ptr(cur_rows), ptr(pos_rows),
+                                  stream_ptr()), "tcavt_ngram_draft")
+
+
+def spec_verify_args(logits, T, n_draft, cur_rows, scratch, drafted, accepted, history, hist_len, params, step, max_new, out_row,
+                     cur_tok, pos, finished, out_tokens, advance_pos=True, workspace=None, stop=None):
+    """The tcavt_spec_verify_args of a verify-and-commit on logits fp32 [S * T, V] and the per-slot state of S sequences (the
+    arguments of sample_tokens in its slots form), each tensor checked first.  scratch: int32 [S * T + S].  The struct names fixed
+    device arrays: one serves every step of a call, captured or not."""
+    who = "spec_verify"
+    R, V = logits.shape
+    T = int(T)
+    if history.dim() != 2 or out_tokens.dim() != 2 or T < 1 or R % T != 0 or history.shape[0] != R // T:
+        raise capi.TcavtError(f"{who}: logits [S * T, V], history one row per sequence, out_tokens one row per request")
+    S = R // T
+    _sampler_guard(who, logits, workspace, S, S, 1, history, hist_len, step, cur_tok, pos, finished, out_tokens, slots=(max_new, out_row))
+    for t, dt, n, nm in ((n_draft, torch.int32, S, "n_draft"), (cur_rows, torch.int64, R, "cur_rows"), (scratch, torch.int32, R + S, "scratch"),
+                         (drafted, torch.int32, S, "drafted"), (accepted, torch.int32, S, "accepted")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, n, f"{who}.{nm}")
+    sa = capi.SampleArgs()
+    sa.logits, sa.history, sa.hist_len = logits.data_ptr(), history.data_ptr(), hist_len.data_ptr()
+    sa.params, sa.step, sa.max_new, sa.out_row = ctypes.pointer(params), step.data_ptr(), max_new.data_ptr(), out_row.data_ptr()
+    sa.cur_tok, sa.pos, sa.finished, sa.out_tokens = cur_tok.data_ptr(), pos.data_ptr(), finished.data_ptr(), out_tokens.data_ptr()
+    sa.workspace, sa.workspace_bytes = ptr(workspace), workspace.numel() if workspace is not None else 0
+    if stop is not None:
+        sa.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
+    sa.rows, sa.V, sa.n_state, sa.hist_cap, sa.out_cap, sa.advance_pos = R, V, S, history.shape[1], out_tokens.shape[1], int(advance_pos)
+    a = capi.SpecVerifyArgs()
+    a.sample = ctypes.pointer(sa)
+    a.n_draft, a.cur_rows, a.slot_of_row = n_draft.data_ptr(), cur_rows.data_ptr(), scratch.data_ptr()
+    a.drafted, a.accepted, a.S, a.T = drafted.data_ptr(), accepted.data_ptr(), S, T
+    a._keep = (sa, params, stop, logits, n_draft, cur_rows, scratch, drafted, accepted, history, hist_len, step, max_new, out_row,
+               cur_tok, pos, finished, out_tokens, workspace)
+    return a
+
+
+def spec_verify(args):
+    """T passes of (gate, sample_tokens) that select, compare with the draft and commit (tcavt_spec_verify); args: spec_verify_args."""
+    check(lib().tcavt_spec_verify(ctypes.byref(args), stream_ptr()), "tcavt_spec_verify")
+
+
 def tlayer_stack_forward(args):
     """args: capi.TStackArgs filled by tlayers._TLayerRunner.run_stack (which owns and sizes every buffer)."""
     check(lib().tcavt_tlayer_stack_forward(ctypes.byref(args), stream_ptr()), "tcavt_tlayer_stack_forward")
