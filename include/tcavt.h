@@ -1398,6 +1398,42 @@ typedef struct tcavt_sample_args {
 
 int tcavt_sample_tokens(const tcavt_sample_args* args, tcavt_stream_t stream);
 
+/* tcavt_sample_tokens with the sampling parameters PER REQUEST: every row reads its tcavt_sample_params -- and, when given, its own
+ * min_new_tokens -- from device tables at the row's REQUEST INDEX r, and its step is then exactly the step tcavt_sample_tokens
+ * makes of that row with table[r] as args->params (and min_new_tokens[r] as stop->min_new_tokens): same processors, candidates,
+ * draw, ending rules and records.  r is
+ *   the row b                        in the batch form (n_req >= rows is required),
+ *   out_row[s]                       in the slots form,
+ *   out_row[slot_of_row[row]]        in the rows form,
+ * i.e. the index of the row of out_tokens the row writes; the Philox counter stays (step, r, 0x5A3B, 0) and the key becomes
+ * table[r].seed.  The form follows from the pointers of args exactly as in tcavt_sample_tokens.
+ *   table           device, n_req entries in the layout of tcavt_sample_params, 8-byte aligned.  table[r].pad_token_id is not read:
+ *                   the pad token stays ONE value per call, args->params->pad_token_id (idle and finished slots feed it to the
+ *                   decode step).  args->params is still required; its other fields are validated as in tcavt_sample_tokens and
+ *                   otherwise unused.
+ *   min_new_tokens  device int32 [n_req], or NULL: then stop->min_new_tokens serves every request, as in tcavt_sample_tokens.
+ *   bad_index_flag  optional device int32: a row of the slots or rows form whose r lies outside [0, n_req) is INERT -- nothing of
+ *                   its state and no out_tokens element is written, nothing of the tables is read -- and bit 0 of the word is set.
+ *   n_req           entries of the tables, >= 1.
+ * The launch cannot read device memory: the VALUES of the tables are the caller's contract, established on the host copy by
+ * tcavt_request_params_check.  Refused before any launch (tcavt_last_error names the argument): what tcavt_sample_tokens refuses; a
+ * NULL request struct or table; n_req < 1; n_req < rows in the batch form; a misaligned table, min_new_tokens or bad_index_flag. */
+typedef struct tcavt_request_params {
+  const tcavt_sample_params* table;
+  const int32_t* min_new_tokens;     /* optional */
+  int32_t* bad_index_flag;           /* optional */
+  int32_t n_req;
+  int32_t reserved0;
+} tcavt_request_params;
+
+int tcavt_sample_tokens_per_request(const tcavt_sample_args* args, const tcavt_request_params* req, tcavt_stream_t stream);
+
+/* Host only, no device needed: the checks tcavt_sample_tokens makes on its one struct, on every entry of a HOST copy of the tables
+ * (host_min_new optional): temperature > 0, 1 <= top_k <= 256 and 0 < top_p <= 1 when do_sample; repetition_penalty > 0;
+ * no_repeat_ngram_size >= 0; min_new >= 0; a positive minimum needs that entry's own eos_token_id >= 0 or has_stop_bitmap != 0;
+ * every pad_token_id equal to entry 0's.  tcavt_last_error names the failing index and field. */
+int tcavt_request_params_check(const tcavt_sample_params* host_table, const int32_t* host_min_new, int n_req, int has_stop_bitmap);
+
 /* Prompt-lookup speculative decoding: the draft.  For each of S sequences, from history[s][0 : hist_len[s]] (the prompt's text ids
  * and everything generated so far, ending in the current token), by the rule of HF PromptLookupCandidateGenerator: for n from
  * min(max_matching_ngram_size, len - 1) down to 1 take the last n ids; among the earlier windows that equal them take the earliest

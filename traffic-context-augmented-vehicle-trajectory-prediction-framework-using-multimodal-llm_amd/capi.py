@@ -239,6 +239,13 @@ class SampleArgs(ctypes.Structure):
                     "rows", "V", "n_state", "hist_cap", "out_cap", "advance_pos")]
 
 
+class RequestParams(ctypes.Structure):
+    """Mirror of ``tcavt_request_params`` (include/tcavt.h)."""
+
+    _fields_ = [("table", ctypes.POINTER(SampleParams)), ("min_new_tokens", c_void_p), ("bad_index_flag", c_void_p),
+                ("n_req", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+
 class SpecVerifyArgs(ctypes.Structure):
     """Mirror of ``tcavt_spec_verify_args`` (include/tcavt.h)."""
 
@@ -504,6 +511,8 @@ _SIGNATURES = {
                                 c_int, c_void_p],
     "tcavt_llama_decode_step_multi": [ctypes.POINTER(DecodeArgs), c_int, c_void_p],
     "tcavt_spec_verify": [ctypes.POINTER(SpecVerifyArgs), c_void_p],
+    "tcavt_sample_tokens_per_request": [ctypes.POINTER(SampleArgs), ctypes.POINTER(RequestParams), c_void_p],
+    "tcavt_request_params_check": [ctypes.POINTER(SampleParams), c_void_p, c_int, c_int],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64,

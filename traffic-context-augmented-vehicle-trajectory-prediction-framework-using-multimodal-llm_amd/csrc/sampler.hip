@@ -1,5 +1,6 @@
 // Token selection of text generation (include/tcavt.h: tcavt_sample_logits, tcavt_sample_logits_slots, tcavt_sample_logits_rows,
-// tcavt_sample_tokens, tcavt_sample_workspace_bytes): the logits processors, the ending rules and the draw, the last launches of a
+// tcavt_sample_tokens, tcavt_sample_tokens_per_request, tcavt_request_params_check, tcavt_sample_workspace_bytes): the logits
+// processors, the ending rules and the draw -- the parameters by value or, per request, from a device table --, the last launches of a
 // decode step (csrc/generate.hip).  They also advance the per-row state (history, position, step, finished) on the device.
 #include "common.hpp"
 #include "philox.hpp"
@@ -32,6 +33,35 @@ struct StopP {
   int n_seqs, min_new;
 };
 constexpr int SMP_SEQS = 16, SMP_SEQ_LEN = 8;
+
+// Per-request parameters (tcavt_request_params; sample kernels with REQ): the workgroup of a row reads its SampleP and its own
+// min_new from device tables at the row's request index r -- the row b in the batch form, out_row[sb] in the slots and rows forms --
+// in the place of the kernel arguments, and runs the same code on them: r, and with it every branch on the parameters, is uniform
+// per workgroup.  pad stays the call's.  A row whose r lies outside [0, n_req) reads nothing of the table, writes nothing and sets
+// bit 0 of *bad_flag.
+struct ReqP {
+  const tcavt_sample_params* table;  // [n_req]
+  const int* min_new;                // [n_req]; or NULL: StopP.min_new
+  int* bad_flag;                     // or NULL
+  const long* out_row;               // slots and rows forms (the kernels' out_row); NULL in the batch form
+  long pad;
+  int n_req;
+};
+template <bool REQ> struct sample_arg { typedef SampleP type; };
+template <> struct sample_arg<true> { typedef ReqP type; };
+// (without REQ `sp` names the kernel argument itself: those instantiations are the code they were before REQ existed)
+__device__ __forceinline__ const SampleP& params_of(const SampleP& arg, const SampleP&) { return arg; }
+__device__ __forceinline__ const SampleP& params_of(const ReqP&, const SampleP& fetched) { return fetched; }
+__device__ __forceinline__ SampleP request_params(const ReqP& rq, long r) {
+  const tcavt_sample_params* __restrict__ t = rq.table + r;
+  SampleP p;
+  p.temperature = t->temperature; p.top_p = t->top_p; p.rep_penalty = t->repetition_penalty;
+  p.top_k = t->top_k; p.no_repeat_ngram = t->no_repeat_ngram_size; p.do_sample = t->do_sample;
+  p.eos = t->eos_token_id; p.pad = rq.pad;
+  const unsigned long seed = t->seed;
+  p.seed_lo = (unsigned int)(seed & 0xffffffffu); p.seed_hi = (unsigned int)(seed >> 32);
+  return p;
+}
 constexpr int FIN_EOS = 1, FIN_STOP_TOKEN = 2, FIN_STOP_SEQ = 3, FIN_BUDGET = 4;
 
 constexpr int SMP_T = 1024;   // threads
@@ -92,9 +122,11 @@ struct SliceWs {  // views into the caller's workspace (tcavt_sample_logits: lay
 // processors: the four ids of a lane's f32x4 lie in one word of the bitmap, so one load serves all four, and the banned scores go
 // back to the row (the one-stage fallback of stage 2 reads them there).  The branch is uniform per row and nothing is loaded for
 // the ban once the minimum is reached.  step_p: the row's step word (per_slot: step_p[sb], else *step_p).
-template <bool STOP = false>
+// REQ: the parameters come from the request tables (ReqP).
+template <bool STOP = false, bool REQ = false>
 __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__ logits, int V, const long* __restrict__ history,
-                                                             int hist_cap, const int* __restrict__ hist_len, SampleP sp, SliceWs ws,
+                                                             int hist_cap, const int* __restrict__ hist_len,
+                                                             typename sample_arg<REQ>::type spa, SliceWs ws,
                                                              const int* __restrict__ slot_of_row, int S, StopP sr,
                                                              const int* __restrict__ step_p, int per_slot,
                                                              const int* __restrict__ finished) {
@@ -109,6 +141,15 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
   // (slot_of_row: logits row b belongs to slot sb of the state arrays; a row without a slot is skipped, nothing of it is written)
   const int sb = slot_of_row ? slot_of_row[b] : b;
   if (sb < 0 || sb >= S) return;  // (uniform)
+  [[maybe_unused]] SampleP sp_req;
+  const SampleP& sp = params_of(spa, sp_req);
+  [[maybe_unused]] const int* req_min = nullptr;  // REQ: the request's own minimum, when the call has them
+  if constexpr (REQ) {
+    const long r = spa.out_row ? spa.out_row[sb] : (long)b;
+    if (r < 0 || r >= (long)spa.n_req) return;  // (uniform) inert; stage 2 raises the flag
+    sp_req = request_params(spa, r);
+    if (spa.min_new) req_min = spa.min_new + r;
+  }
   float* x = logits + (long)b * V;
   const long* hist = history + (long)sb * hist_cap;
   const int hl = min(hist_len[sb], hist_cap);
@@ -164,7 +205,11 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
   const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
   bool min_ban = false;  // (uniform)
   if constexpr (STOP) {
-    if (sr.min_new > 0) min_ban = (per_slot ? step_p[sb] : *step_p) < sr.min_new && finished[sb] == 0;
+    int min_new = sr.min_new;
+    if constexpr (REQ) {
+      if (req_min) min_new = *req_min;
+    }
+    if (min_new > 0) min_ban = (per_slot ? step_p[sb] : *step_p) < min_new && finished[sb] == 0;
   }
 #pragma unroll
   for (int e = 0; e < SMP_E4; ++e) {
@@ -319,9 +364,10 @@ __global__ __launch_bounds__(SMP_T) void sample_slice_kernel(float* __restrict__
 // `finished` records finish_reason (EOS 1 > stop token 2 > stop sequence 3 > budget 4) and n_generated = step + 1 at the row's
 // out_tokens index.  Everything else of a row's step is as without STOP.
 constexpr int SMP_BATCH = 0, SMP_SLOTS = 1, SMP_ROWS = 2;
-template <int MODE, bool STOP = false>
+// REQ (tcavt_sample_tokens_per_request): the row's parameters and minimum come from the request tables, see ReqP.
+template <int MODE, bool STOP = false, bool REQ = false>
 __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logits, int V, long* __restrict__ history,
-                                                       int hist_cap, int* __restrict__ hist_len, SampleP sp,
+                                                       int hist_cap, int* __restrict__ hist_len, typename sample_arg<REQ>::type spa,
                                                        int* __restrict__ step_p, long* __restrict__ cur_tok,
                                                        int* __restrict__ pos, int* __restrict__ finished,
                                                        long* __restrict__ out_tokens, int out_cap, int advance_pos, SliceWs ws,
@@ -346,6 +392,18 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
     sb = slot_of_row[b];
     if (sb < 0 || sb >= n_state) return;  // (uniform)
   }
+  [[maybe_unused]] SampleP sp_req;
+  const SampleP& sp = params_of(spa, sp_req);
+  [[maybe_unused]] const int* req_min = nullptr;  // REQ: the request's own minimum, when the call has them
+  if constexpr (REQ) {
+    const long r = SLOTS ? out_row[sb] : (long)b;  // (batch form: the entry has checked n_req >= rows)
+    if (SLOTS && (r < 0 || r >= (long)spa.n_req)) {  // (uniform) inert: nothing of the row is written
+      if (tid == 0 && spa.bad_flag) atomicOr(spa.bad_flag, 1);
+      return;
+    }
+    sp_req = request_params(spa, r);
+    if (spa.min_new) req_min = spa.min_new + r;
+  }
   float* x = logits + (long)b * V;
   long* hist = history + (long)sb * hist_cap;
   const int hl = min(hist_len[sb], hist_cap);
@@ -360,7 +418,11 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(float* __restrict__ logit
   const bool pre_ok = pre && s_ovf == 0;  // (uniform) the slices' candidates are complete
   // ---- before the minimum: no ending token (-inf absorbs the penalty, so the order against the processors below does not matter)
   if constexpr (STOP) {
-    if (!pre && sr.min_new > 0 && step < sr.min_new && finished[sb] == 0) {  // (uniform)
+    int min_new = sr.min_new;
+    if constexpr (REQ) {
+      if (req_min) min_new = *req_min;
+    }
+    if (!pre && min_new > 0 && step < min_new && finished[sb] == 0) {  // (uniform)
       if (sr.bitmap) {
         for (int i = tid; i < V; i += SMP_T)
           if ((sr.bitmap[i >> 5] >> (i & 31)) & 1u) x[i] = -INFINITY;
@@ -756,7 +818,8 @@ extern "C" int64_t tcavt_sample_workspace_bytes(int B) {
 static int sample_logits_impl(const char* who, float* logits, int B, int V, const int32_t* slot_of_row, int n_state, int64_t* history,
                               int hist_cap, int32_t* hist_len, const tcavt_sample_params* sp, int32_t* step, const int32_t* max_new, const int64_t* out_row, int64_t* cur_tok,
                               int32_t* pos, int32_t* finished, int64_t* out_tokens, int out_cap, int advance_pos, void* workspace,
-                              int64_t workspace_bytes, tcavt_stream_t stream, const tcavt_stop_rules* rules = nullptr) {
+                              int64_t workspace_bytes, tcavt_stream_t stream, const tcavt_stop_rules* rules = nullptr,
+                              const tcavt_request_params* req = nullptr) {
   const bool slots = max_new || out_row;
   // ending rules: with none set (or rules == NULL) the launches below are the instantiations without STOP, argument for argument
   StopP sr = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
@@ -775,6 +838,21 @@ static int sample_logits_impl(const char* who, float* logits, int B, int V, cons
     sr.finish_reason = rules->finish_reason; sr.n_generated = rules->n_generated;
     sr.n_seqs = rules->n_seqs; sr.min_new = rules->min_new_tokens;
     stop = sr.bitmap || sr.n_seqs > 0 || sr.min_new > 0 || sr.finish_reason || sr.n_generated;
+  }
+  // per-request parameters: the REQ instantiations, argument for argument the launches below with the tables in the struct's place
+  ReqP rq = {nullptr, nullptr, nullptr, nullptr, 0, 0};
+  if (req) {
+    TCAVT_CHECK_ARG(req->table, "%s: request params: table is a null pointer", who);
+    TCAVT_CHECK_ARG(req->n_req >= 1, "%s: request params: n_req = %d must be >= 1", who, req->n_req);
+    TCAVT_CHECK_ARG(slots || req->n_req >= B, "%s: request params: n_req = %d is below rows = %d (batch form: the request of row b is b)",
+                    who, req->n_req, B);
+    TCAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(req->table) & 7) == 0, "%s: request params: table must be 8-byte aligned", who);
+    TCAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(req->min_new_tokens) & 3) == 0, "%s: request params: min_new_tokens must be 4-byte aligned", who);
+    TCAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(req->bad_index_flag) & 3) == 0, "%s: request params: bad_index_flag must be 4-byte aligned", who);
+    rq.table = req->table; rq.min_new = req->min_new_tokens; rq.bad_flag = req->bad_index_flag;
+    rq.out_row = slots ? reinterpret_cast<const long*>(out_row) : nullptr;
+    rq.pad = sp->pad_token_id; rq.n_req = req->n_req;
+    stop = stop || rq.min_new;  // (a request's own minimum needs the ban of the STOP forms)
   }
   TCAVT_CHECK_ARG(!sp->do_sample || (sp->temperature > 0.f && sp->top_k >= 1 && sp->top_k <= SMP_CAP && sp->top_p > 0.f && sp->top_p <= 1.f),
                   "%s: sampling needs temperature > 0, 1 <= top_k <= %d, 0 < top_p <= 1", who, SMP_CAP);
@@ -799,8 +877,26 @@ static int sample_logits_impl(const char* who, float* logits, int B, int V, cons
     ws.lb = reinterpret_cast<float*>(w + off); off += (size_t)B * SMP_G * 4;
     ws.cand_v = reinterpret_cast<float*>(w + off); off += (size_t)B * SMP_G * SMP_LCAP * 4;
     ws.cand_i = reinterpret_cast<int*>(w + off);
-    hipLaunchKernelGGL(stop ? sample_slice_kernel<true> : sample_slice_kernel<false>, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V,
-                       reinterpret_cast<const long*>(history), hist_cap, hist_len, p, ws, slot_of_row, n_state, sr, step, slots ? 1 : 0, finished);
+    if (req) {
+      auto* skern = sample_slice_kernel<false, true>;
+      if (stop) skern = sample_slice_kernel<true, true>;
+      hipLaunchKernelGGL(skern, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V, reinterpret_cast<const long*>(history), hist_cap, hist_len,
+                         rq, ws, slot_of_row, n_state, sr, step, slots ? 1 : 0, finished);
+    } else {
+      hipLaunchKernelGGL(stop ? sample_slice_kernel<true> : sample_slice_kernel<false>, dim3(B * SMP_G), dim3(SMP_T), 0, st, logits, V,
+                         reinterpret_cast<const long*>(history), hist_cap, hist_len, p, ws, slot_of_row, n_state, sr, step, slots ? 1 : 0, finished);
+    }
+  }
+  if (req) {
+    auto* rkern = slot_of_row ? sample_kernel<SMP_ROWS, false, true> : slots ? sample_kernel<SMP_SLOTS, false, true> : sample_kernel<SMP_BATCH, false, true>;
+    if (stop) rkern = slot_of_row ? sample_kernel<SMP_ROWS, true, true> : slots ? sample_kernel<SMP_SLOTS, true, true> : sample_kernel<SMP_BATCH, true, true>;
+    hipLaunchKernelGGL(rkern, dim3(B), dim3(SMP_T),
+                       0, st, logits, V, reinterpret_cast<long*>(history), hist_cap, hist_len, rq, step, reinterpret_cast<long*>(cur_tok), pos,
+                       finished, reinterpret_cast<long*>(out_tokens), out_cap, advance_pos, ws, B, max_new,
+                       reinterpret_cast<const long*>(out_row), slot_of_row, n_state, sr);
+    if (!ws.cand_v && !slots) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
+    TCAVT_CHECK_LAUNCH(who);
+    return TCAVT_OK;
   }
   auto* kern = slot_of_row ? sample_kernel<SMP_ROWS> : slots ? sample_kernel<SMP_SLOTS> : sample_kernel<SMP_BATCH>;
   if (stop) kern = slot_of_row ? sample_kernel<SMP_ROWS, true> : slots ? sample_kernel<SMP_SLOTS, true> : sample_kernel<SMP_BATCH, true>;
@@ -873,4 +969,50 @@ extern "C" int tcavt_sample_tokens(const tcavt_sample_args* a, tcavt_stream_t st
   return sample_logits_impl("sample_tokens", a->logits, a->rows, a->V, a->slot_of_row, rows ? a->n_state : a->rows, a->history, a->hist_cap,
                             a->hist_len, a->params, a->step, a->max_new, a->out_row, a->cur_tok, a->pos, a->finished, a->out_tokens,
                             a->out_cap, a->advance_pos, a->workspace, a->workspace_bytes, stream, a->stop);
+}
+
+// tcavt_sample_tokens with the parameters per request: the same pointer rules, then the REQ launches
+extern "C" int tcavt_sample_tokens_per_request(const tcavt_sample_args* a, const tcavt_request_params* req, tcavt_stream_t stream) {
+  const char* who = "sample_tokens_per_request";
+  TCAVT_CHECK_ARG(a, "%s: args is a null pointer", who);
+  TCAVT_CHECK_ARG(req, "%s: request params is a null pointer", who);
+  const bool rows = a->slot_of_row != nullptr, slots = rows || a->max_new || a->out_row;
+  const struct { const void* p; const char* name; bool need; } ptrs[] = {
+      {a->logits, "logits", true}, {a->history, "history", true}, {a->hist_len, "hist_len", true}, {a->params, "params", true},
+      {a->step, "step", true}, {a->max_new, "max_new", slots}, {a->out_row, "out_row", slots}, {a->cur_tok, "cur_tok", true},
+      {a->pos, "pos", true}, {a->finished, "finished", true}, {a->out_tokens, "out_tokens", true}};
+  for (const auto& q : ptrs) TCAVT_CHECK_ARG(q.p || !q.need, "%s: %s is a null pointer", who, q.name);
+  TCAVT_CHECK_ARG(a->rows > 0, "%s: rows = %d must be > 0", who, a->rows);
+  TCAVT_CHECK_ARG(a->V > 0, "%s: V = %d must be > 0", who, a->V);
+  TCAVT_CHECK_ARG(!rows || a->n_state > 0, "%s: n_state = %d must be > 0 with slot_of_row", who, a->n_state);
+  TCAVT_CHECK_ARG(a->hist_cap > 0, "%s: hist_cap = %d must be > 0", who, a->hist_cap);
+  TCAVT_CHECK_ARG(a->out_cap > 0, "%s: out_cap = %d must be > 0", who, a->out_cap);
+  return sample_logits_impl(who, a->logits, a->rows, a->V, a->slot_of_row, rows ? a->n_state : a->rows, a->history, a->hist_cap,
+                            a->hist_len, a->params, a->step, a->max_new, a->out_row, a->cur_tok, a->pos, a->finished, a->out_tokens,
+                            a->out_cap, a->advance_pos, a->workspace, a->workspace_bytes, stream, a->stop, req);
+}
+
+// the checks sample_logits_impl makes on the one struct, on every entry of a HOST table (no device needed)
+extern "C" int tcavt_request_params_check(const tcavt_sample_params* t, const int32_t* min_new, int n_req, int has_stop_bitmap) {
+  const char* who = "request_params_check";
+  TCAVT_CHECK_ARG(t, "%s: host_table is a null pointer", who);
+  TCAVT_CHECK_ARG(n_req >= 1, "%s: n_req = %d must be >= 1", who, n_req);
+  for (int r = 0; r < n_req; ++r) {
+    const tcavt_sample_params& p = t[r];
+    if (p.do_sample) {
+      TCAVT_CHECK_ARG(p.temperature > 0.f, "%s: table[%d].temperature = %g must be > 0 when sampling", who, r, (double)p.temperature);
+      TCAVT_CHECK_ARG(p.top_k >= 1 && p.top_k <= SMP_CAP, "%s: table[%d].top_k = %d outside [1, %d] when sampling", who, r, p.top_k, SMP_CAP);
+      TCAVT_CHECK_ARG(p.top_p > 0.f && p.top_p <= 1.f, "%s: table[%d].top_p = %g outside (0, 1] when sampling", who, r, (double)p.top_p);
+    }
+    TCAVT_CHECK_ARG(p.repetition_penalty > 0.f, "%s: table[%d].repetition_penalty = %g must be > 0", who, r, (double)p.repetition_penalty);
+    TCAVT_CHECK_ARG(p.no_repeat_ngram_size >= 0, "%s: table[%d].no_repeat_ngram_size = %d must be >= 0", who, r, p.no_repeat_ngram_size);
+    TCAVT_CHECK_ARG(p.pad_token_id == t[0].pad_token_id, "%s: table[%d].pad_token_id = %lld differs from table[0].pad_token_id = %lld (one per call)",
+                    who, r, (long long)p.pad_token_id, (long long)t[0].pad_token_id);
+    if (min_new) {
+      TCAVT_CHECK_ARG(min_new[r] >= 0, "%s: min_new_tokens[%d] = %d must be >= 0", who, r, min_new[r]);
+      TCAVT_CHECK_ARG(min_new[r] == 0 || p.eos_token_id >= 0 || has_stop_bitmap,
+                      "%s: min_new_tokens[%d] = %d with neither table[%d].eos_token_id nor a stop bitmap (nothing to ban)", who, r, min_new[r], r);
+    }
+  }
+  return TCAVT_OK;
 }

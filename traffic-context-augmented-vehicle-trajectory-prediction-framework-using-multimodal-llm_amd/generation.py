@@ -13,6 +13,7 @@ one piece per job:
                    tcavt_ngram_draft -> tcavt_llama_decode_step_multi -> tcavt_spec_verify that commits 1 .. k + 1 tokens
   beam_search      generate_batch(num_beams > 1): tcavt_beam_select / tcavt_beam_reorder around the shared-prefix decode step
   decode_args      the tcavt_decode_args of the decode step
+  request_params   the nine sampling arguments -> the call's struct and, when one of them is given per request, the device table
   sample_params, eval_arithmetic, the check_* / stop_rules argument checks, cache_buffers (with the KV8 plane table)
 
 Workspace names and the order in which they are first requested are part of what tests/test_generation_trace_cpu.py pins;
@@ -78,6 +79,81 @@ def sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram
     return capi.SampleParams(float(temperature), float(top_p), float(repetition_penalty), int(top_k), int(no_repeat_ngram_size),
                              int(bool(do_sample)), -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id),
                              int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+PER_REQUEST_ARGS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "eos_token_id", "seed",
+                    "min_new_tokens")
+
+
+def per_request_names(**nine):
+    """The names among the nine sampling arguments that are given per request: a list, a tuple or a 1-D tensor."""
+    return [k for k, v in nine.items() if isinstance(v, (list, tuple)) or (isinstance(v, torch.Tensor) and v.dim() >= 1)]
+
+
+def request_params(who, n_req, repeat, rules, pad_token_id, **nine):
+    """The nine sampling arguments -> (sp, table).  sp: the call's tcavt_sample_params (the values of request 0 where an argument is
+    given per request; it carries pad_token_id).  table: None when every argument is one value -- the call is then the call of
+    today -- else an ops.RequestTable of n_req * repeat entries, request-major (generate_batch: a prompt's value serves its
+    ``repeat`` continuations), built and checked on the host; ``table.to(device)`` uploads it.  A wrong length or an illegal
+    element raises ValueError naming the argument and the index; nothing here touches a device."""
+    assert tuple(nine) == PER_REQUEST_ARGS
+    names = per_request_names(**nine)
+    if not names:
+        return sample_params(nine["temperature"], nine["top_p"], nine["repetition_penalty"], nine["top_k"], nine["no_repeat_ngram_size"],
+                             nine["do_sample"], nine["eos_token_id"], pad_token_id, nine["seed"]), None
+    cols = {}
+    for k, v in nine.items():
+        if k in names:
+            v = v.tolist() if isinstance(v, torch.Tensor) else list(v)
+            if isinstance(nine[k], torch.Tensor) and nine[k].dim() != 1:
+                raise ValueError(f"{who}: {k} must be one value or a 1-D sequence, got a {nine[k].dim()}-D tensor")
+            if len(v) != n_req:
+                raise ValueError(f"{who}: {k} has {len(v)} values for {n_req} requests")
+        else:
+            v = [v] * n_req
+        cols[k] = v
+    if n_req == 0:
+        return None, None
+    has_stop = bool(rules.stop_token_ids)
+    params, mins = [], []
+    for r in range(n_req):
+        c = {k: cols[k][r] for k in PER_REQUEST_ARGS}
+
+        def bad(k, why):
+            return ValueError(f"{who}: {k}[{r}] = {c[k]!r} {why}" if k in names else f"{who}: {k} = {c[k]!r} {why} (request {r})")
+
+        for k in PER_REQUEST_ARGS:  # numbers only (bool counts as one); eos_token_id may be None
+            if not (isinstance(c[k], numbers.Real) or (k == "eos_token_id" and c[k] is None)):
+                raise bad(k, "is not a number")
+        for k in ("top_k", "no_repeat_ngram_size", "seed", "min_new_tokens", "eos_token_id"):
+            if c[k] is not None and int(c[k]) != c[k]:
+                raise bad(k, "is not an integer")
+        if c["do_sample"]:
+            if not c["temperature"] > 0:
+                raise bad("temperature", "must be > 0 when sampling")
+            if not 1 <= c["top_k"] <= 256:
+                raise bad("top_k", "outside [1, 256] when sampling")
+            if not 0 < c["top_p"] <= 1:
+                raise bad("top_p", "outside (0, 1] when sampling")
+        if not c["repetition_penalty"] > 0:
+            raise bad("repetition_penalty", "must be > 0")
+        if c["no_repeat_ngram_size"] < 0:
+            raise bad("no_repeat_ngram_size", "must be >= 0")
+        if c["min_new_tokens"] < 0:
+            raise bad("min_new_tokens", "must be >= 0")
+        try:
+            rules.check_bannable(int(c["min_new_tokens"]), c["eos_token_id"])
+        except ValueError:
+            raise bad("min_new_tokens", "needs the request's eos_token_id or stop_token_ids (nothing to ban)") from None
+        params.append(sample_params(c["temperature"], c["top_p"], c["repetition_penalty"], c["top_k"], c["no_repeat_ngram_size"],
+                                    c["do_sample"], c["eos_token_id"], pad_token_id, c["seed"]))
+        mins.append(int(c["min_new_tokens"]))
+    try:
+        table = ops.RequestTable([p_ for p_ in params for _ in range(repeat)],
+                                 [m_ for m_ in mins for _ in range(repeat)] if any(mins) else None, has_stop_bitmap=has_stop)
+    except capi.TcavtError as e:
+        raise ValueError(f"{who}: {e}") from None
+    return params[0], table
 
 
 def sample_workspace(ws, name, rows, dev):
@@ -203,19 +279,24 @@ def rank_continuations(sum_logprob, n_scored, n, length_penalty=1.0):
     return torch.argsort(score, dim=1, descending=True, stable=True)
 
 
-def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None):
+def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None, table=None):
     """Logits processors + token selection on the state ``st``.  The form follows from the arguments: ``slot_of_row`` -> the rows
     of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
     (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``lp`` (a LogprobRecord; its workspace
     under ``lp_tag``): the selection is bracketed by tcavt_logprob_begin / _finish, which read the raw row before the processors
-    touch it and the chosen token afterwards; the selection itself is the one without."""
+    touch it and the chosen token afterwards; the selection itself is the one without.  ``table`` (an uploaded ops.RequestTable):
+    tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take."""
     if lp is not None:
         largs = lp.args(lp_tag, logits, st, slot_of_row)
         ops.logprob_begin(largs)
-        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row)
+        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table)
         ops.logprob_finish(largs)
         return
-    if drules is not None:
+    if table is not None:
+        ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
+                          workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules,
+                          per_request=table)
+    elif drules is not None:
         ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
                           workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules)
     elif slot_of_row is not None:
@@ -409,6 +490,12 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     the same Philox rows and the same tokens as the batch form) and a step is prompt_lookup_step above; None is the call without."""
     who = "generate_batch"
     k = m = None
+    nine = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)
+    listed = per_request_names(**nine)
+    if listed and (num_beams != 1 or prompt_lookup_num_tokens is not None):  # (beam search and tcavt_spec_verify keep the one struct)
+        raise ValueError(f"{who}: per-request values ({', '.join(listed)}) are not built for "
+                         f"{'num_beams > 1' if num_beams != 1 else 'prompt_lookup_num_tokens'}: one value per call there")
     if prompt_lookup_num_tokens is not None:  # (before anything touches a device, and before the beam search takes over)
         k, m = check_prompt_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, kv_cache, share_prefix, num_beams,
                                    return_logprobs, stop_sequences)
@@ -452,6 +539,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                              f"got {B} * {k + 1}")
         if not 0 <= int(pad_token_id) < mllm.llama_wrapper.shape.vocab:  # (the rows behind a draft feed the pad token to the step)
             raise ValueError(f"{who}: prompt_lookup_num_tokens needs pad_token_id inside [0, vocab), got {pad_token_id}")
+    sp, table = request_params(who, src_B, n, rules, pad_token_id, **nine)  # (host only; a table: one entry per decode row)
+    mllm._request_flag = None
     dev = vision_embs_batch.device
     input_ids = input_ids.to(dev).contiguous()
     attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
@@ -497,14 +586,14 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             st.step, st.max_new = torch.zeros(B, dtype=I32, device=dev), torch.full((B,), N, dtype=I32, device=dev)
             st.out_row = torch.arange(B, dtype=I64, device=dev)
         out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
-        sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
-                           pad_token_id, seed)
+        if table is not None:  # one upload per call: the device arrays are fixed, so the captured step stays valid
+            mllm._request_flag = table.to(dev).flag
         # two-stage token selection (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form, A/B)
         sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
         # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
         drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
         lp = LogprobRecord(mllm._ws, out) if return_logprobs else None  # (the flag alone does not change the sampler entry)
-        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen")
+        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen", table=table)
         steps_run = 0
         drafted = accepted = None
         if N > 1 and k is not None:
@@ -520,7 +609,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                     ops.llama_decode_step(a)
                 else:
                     ops.llama_decode_step_shared(a, prefix)
-                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen")
+                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen", table=table)
 
             steps_run = decode_loop(one_step, N, B, dev, use_graph, poll_every, st.finished)
         info = None
@@ -685,6 +774,10 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
     if not 0 <= int(pad_token_id) < ll.vocab:  # (idle and finished slots feed the pad token to the decode step)
         raise ValueError(f"generate_pool: pad_token_id = {pad_token_id} outside [0, vocab = {ll.vocab})")
     check_fp8_weights(who, decode_weights, S, "slots")
+    sp, table = request_params(who, R, 1, rules, pad_token_id, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                               repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                               eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)  # (host only)
+    mllm._request_flag = None
     dev = vision_embs.device
     out = torch.full((R, Nmax), int(pad_token_id), dtype=I64, device=dev)
     stats = mllm.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
@@ -720,8 +813,8 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
         logits = ws.get("pool.logits", (S, ll.vocab), torch.float32, dev)
         pf.reserve("logits", "kvlen", "final16", "x16", "h")
         poll = FinishedPoll(S, dev)
-        sp = sample_params(temperature, top_p, repetition_penalty, top_k, no_repeat_ngram_size, do_sample, eos_token_id,
-                           pad_token_id, seed)
+        if table is not None:  # one upload per call: the device arrays are fixed, so the captured graphs stay valid
+            mllm._request_flag = table.to(dev).flag
         # two-stage token selection, as generate_batch (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form)
         two_stage = os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1"
         sws = sample_workspace(ws, "pool.sample_ws", S, dev) if two_stage else None
@@ -736,14 +829,14 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
 
         def one_step():
             ops.llama_decode_step(a)
-            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool")
+            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool", table=table)
 
         def admit(s, r):
             # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
             # and the first token from the one-row logits with the slot's state (views that start at slot s)
             logits1 = pf.run(vision_embs[r:r + 1], input_ids[r:r + 1], mask64[r:r + 1], after_stack=lambda: ops.slot_admit(
                 pf.buf("cache"), cache, s, *geometry, input_ids[r], pf.buf("kvlen"), Nq, budgets[r], r, *state))
-            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf")
+            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf", table=table)
 
         if G > 1:
             # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
@@ -775,7 +868,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             def group_pass():
                 logits_g = pg.run(pg_vis, pg_ids, pg_mask, after_stack=lambda: ops.slot_admit_group(
                     pg.buf("cache"), cache, pg_slot, *geometry, pg_ids, pg.buf("kvlen"), Nq, pg_budget, pg_outrow, bad_slot, *state))
-                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg")
+                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg", table=table)
 
         sched = SlotScheduler(R, S, G)
         step = later_pass = None

@@ -43,7 +43,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
         self._ws = _Workspace()
         self._prep = None
         self._pf_stream = self._pf = self._img_consumed = None
-        self._last_flags = self._lm_flag = self._pool_flag = None  # device error flags of the passes so far (check_flags)
+        self._last_flags = self._lm_flag = self._pool_flag = self._request_flag = None  # device error flags of the passes so far (check_flags)
 
     def _image_tokens(self, vision_embs):
         """Q-Former + q_proj (train.py:519-521): image tokens [B*Nq, H] fp32, before the modality embedding."""
@@ -211,6 +211,9 @@ class LlamaMultiModal(nn.Module, _Prepared):
         if self._pool_flag is not None and self._pool_flag.item():
             self._pool_flag.zero_()
             raise ValueError("generate_pool: a grouped admission named a slot outside the pool (tcavt_slot_admit_group)")
+        if self._request_flag is not None and self._request_flag.item():
+            self._request_flag.zero_()
+            raise ValueError("a sampler row named a request outside the per-request parameter table (tcavt_sample_tokens_per_request)")
         if self._last_flags is None:
             return
         f = self._last_flags.tolist()
@@ -318,6 +321,19 @@ class LlamaMultiModal(nn.Module, _Prepared):
         stop_sequences, S * (k + 1) > 32, a pad_token_id outside the vocabulary (the rows behind a draft feed it to the step), a k
         or max_matching_ngram_size outside its range.  None, the default, is launch for launch the call without the argument.
         generate_pool does not take the two.
+        Per-request parameters ("per-request parameters"): each of ``do_sample``, ``temperature``, ``top_k``,
+        ``top_p``, ``repetition_penalty``, ``no_repeat_ngram_size``, ``eos_token_id`` (entries may be None), ``seed`` and
+        ``min_new_tokens`` is one value, or a list / tuple / 1-D tensor of exactly B values, one per prompt; with
+        ``num_return_sequences`` = n prompt b's value serves its n rows.  With a sequence among them the values go to the device
+        once per call as a table of B * n entries (checked on the host first: a wrong length or an illegal element raises
+        ValueError naming the argument and the index, before anything touches a device) and every sampler launch is
+        tcavt_sample_tokens_per_request, which reads row r's parameters at entry r; a row then gets exactly the tokens, finish_reason,
+        n_generated and log-probabilities it gets in the call where every prompt uses its values (wherever the decode step's logits
+        do not depend on the row count).  share_prefix, kv_cache, decode_weights, the ending rules, poll_every, return_info and
+        return_logprobs work as above; a positive minimum needs that prompt's own eos_token_id, or stop_token_ids.  ``pad_token_id``,
+        ``stop_token_ids`` and ``stop_sequences`` stay one value per call.  Refused with ValueError together with num_beams > 1 or
+        prompt_lookup_num_tokens (beam search and tcavt_spec_verify keep the one struct).  With nine single values the call is
+        launch for launch, buffer for buffer and bit for bit the call without this.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
@@ -372,7 +388,20 @@ class LlamaMultiModal(nn.Module, _Prepared):
         ``return_logprobs`` = True (a bool, anything else raises ValueError): returns (out, stats) and the stats gain the host tensors
         "token_logprobs" float32 [R, max budget], "sum_logprob" float32 [R] and "n_scored" int32 [R], as in generate_batch: the
         log-softmax of the raw logits row at every token request r emitted, 0.0 after its end.  The bracket sits around all three
-        sampler uses, and a request's three results do not depend on its slot, the schedule or its partners (for a fixed G)."""
+        sampler uses, and a request's three results do not depend on its slot, the schedule or its partners (for a fixed G).
+        Per-request parameters ("per-request parameters"): each of ``do_sample``, ``temperature``, ``top_k``,
+        ``top_p``, ``repetition_penalty``, ``no_repeat_ngram_size``, ``eos_token_id`` (entries may be None), ``seed`` and
+        ``min_new_tokens`` is one value, or a list / tuple / 1-D tensor of exactly R values -- a greedy request next to sampled ones,
+        every request its own temperature or seed, in ONE call.  With a sequence among them the values are checked on the host (a
+        wrong length or an illegal element raises ValueError naming the argument and the index; nothing is launched, no workspace
+        buffer requested), uploaded once as a table of R entries, and all three sampler uses become
+        tcavt_sample_tokens_per_request, which reads a row's parameters at its request index out_row[slot]; the captured graphs
+        stay valid.  Request r then gets exactly the tokens, finish_reason, n_generated and log-probabilities that it gets in the
+        call where all requests use its values: the independence from slot, schedule, group row and partners extends to the
+        partners' parameters (for a fixed G).  A positive minimum needs that request's own eos_token_id, or stop_token_ids.
+        ``pad_token_id`` (idle and finished slots feed it to the decode step), ``stop_token_ids`` and ``stop_sequences`` stay one
+        value per call.  A row that names a request outside the table is inert and sets a flag that check_flags() reports.  With
+        nine single values the call is launch for launch, buffer for buffer and bit for bit the call without this."""
         out, stats = generation.generate_pool(
             self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
             repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,

@@ -1193,12 +1193,50 @@ def sample_logits_rows(logits, slot_of_row, history, hist_len, params, step, max
           "tcavt_sample_logits_rows")
 
 
+class RequestTable:
+    """Per-request sampler parameters (tcavt_request_params): ``params`` -- a sequence of capi.SampleParams, one per request -- and
+    optionally one min_new_tokens per request, checked on the host by tcavt_request_params_check when built (TcavtError names the
+    failing index and field; has_stop_bitmap: a stop set exists, so a positive minimum has something to ban without an EOS).
+    ``to(device)`` uploads the tables, once, and makes ``flag``: device int32 [1], zeroed, that a row whose request index lies
+    outside the table sets."""
+
+    def __init__(self, params, min_new_tokens=None, has_stop_bitmap=False):
+        n = self.n_req = len(params)
+        if min_new_tokens is not None and len(min_new_tokens) != n:
+            raise capi.TcavtError(f"RequestTable: {len(min_new_tokens)} min_new_tokens for {n} requests")
+        self.host = (capi.SampleParams * max(n, 1))(*params)
+        self.host_min = None if min_new_tokens is None else (ctypes.c_int32 * max(n, 1))(*[int(m) for m in min_new_tokens])
+        # (host only: the library itself, also where ops runs against a stand-in)
+        rc = capi.lib().tcavt_request_params_check(self.host, self.host_min, n, int(bool(has_stop_bitmap)))
+        if rc != 0:
+            raise capi.TcavtError(f"tcavt_request_params_check failed (code {rc}): {capi.lib().tcavt_last_error().decode()}")
+        self.table = self.min_new = self.flag = self._struct = None
+
+    def to(self, device):
+        self.table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(device)
+        self.min_new = None if self.host_min is None else torch.tensor(list(self.host_min), dtype=torch.int32).to(device)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self._struct = None
+        return self
+
+    def pointer(self):
+        if self._struct is None:
+            r = capi.RequestParams()
+            r.table = ctypes.cast(self.table.data_ptr(), ctypes.POINTER(capi.SampleParams))
+            capi.bind(r, min_new_tokens=self.min_new, bad_index_flag=self.flag)
+            r.n_req = self.n_req
+            self._struct = r
+        return ctypes.pointer(self._struct)
+
+
 def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finished, out_tokens, advance_pos, workspace=None,
-                  max_new=None, out_row=None, slot_of_row=None, stop=None):
+                  max_new=None, out_row=None, slot_of_row=None, stop=None, per_request=None):
     """The three token-selection entries in one, with optional ending rules (tcavt_sample_tokens).  The form follows from the
     arguments as in the C entry: slot_of_row -> sample_logits_rows, max_new / out_row -> sample_logits_slots, neither ->
     sample_logits.  stop: a stopping.DeviceStopRules (or a capi.StopRules struct), or None -- then, and with nothing set in it,
-    the launches are those of the corresponding existing entry."""
+    the launches are those of the corresponding existing entry.  per_request: a RequestTable (or a capi.RequestParams struct) ->
+    tcavt_sample_tokens_per_request: every row takes its parameters from the table at its request index (the row in the batch
+    form, out_row[slot] otherwise); ``params`` still carries the call's pad_token_id."""
     rows, V = logits.shape
     if history.dim() != 2 or out_tokens.dim() != 2:
         raise capi.TcavtError("sample_tokens: history needs one row per sample / slot, out_tokens one row per sample / request")
@@ -1219,6 +1257,17 @@ def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finishe
     if stop is not None:
         a.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
     a.rows, a.V, a.n_state, a.hist_cap, a.out_cap, a.advance_pos = rows, V, n, history.shape[1], out_tokens.shape[1], int(advance_pos)
+    if per_request is not None:
+        if not isinstance(per_request, capi.RequestParams):
+            _req(per_request.table, torch.uint8, "sample_tokens.per_request.table")
+            _req(per_request.min_new, torch.int32, "sample_tokens.per_request.min_new")
+            _need(per_request.min_new, per_request.n_req, "sample_tokens.per_request.min_new")
+            _need(per_request.table, per_request.n_req * ctypes.sizeof(capi.SampleParams), "sample_tokens.per_request.table")
+            if not slots and per_request.n_req < rows:
+                raise capi.TcavtError(f"sample_tokens: per_request has {per_request.n_req} entries for {rows} rows")
+        req = ctypes.pointer(per_request) if isinstance(per_request, capi.RequestParams) else per_request.pointer()
+        check(lib().tcavt_sample_tokens_per_request(ctypes.byref(a), req, stream_ptr()), "tcavt_sample_tokens_per_request")
+        return
     check(lib().tcavt_sample_tokens(ctypes.byref(a), stream_ptr()), "tcavt_sample_tokens")
 
 

@@ -36,7 +36,12 @@ class StopRules:
             for t in s:
                 if not 0 <= t < self.vocab:
                     raise ValueError(f"StopRules: stop sequence id {t} outside [0, vocab = {self.vocab})")
-        self.min_new_tokens = int(min_new_tokens)
+        # one minimum, or one per request: then the struct's own stays 0 and the sampler reads the request table's (the generate
+        # entries check the elements, with their index, when they build it)
+        if isinstance(min_new_tokens, torch.Tensor) and min_new_tokens.dim() >= 1:
+            min_new_tokens = min_new_tokens.tolist()
+        self.min_new_per_request = tuple(min_new_tokens) if isinstance(min_new_tokens, (list, tuple)) else None
+        self.min_new_tokens = 0 if self.min_new_per_request is not None else int(min_new_tokens)
         if self.min_new_tokens < 0:
             raise ValueError(f"StopRules: min_new_tokens must be >= 0, got {min_new_tokens}")
         self.stop_token_ids = tuple(sorted(set(ids)))
@@ -55,21 +60,36 @@ class StopRules:
     @property
     def empty(self):
         """No rule at all: the sampler runs exactly as without rules."""
-        return not self.stop_token_ids and not self.stop_sequences and self.min_new_tokens == 0
+        return not self.stop_token_ids and not self.stop_sequences and self.min_new_tokens == 0 and not any(self.min_new_per_request or ())
+
+    def min_new(self, request=None):
+        """The minimum of request ``request`` (the one minimum when it is not given per request)."""
+        return self.min_new_tokens if self.min_new_per_request is None or request is None else int(self.min_new_per_request[request])
+
+    def check_bannable(self, min_new_tokens, eos_token_id):
+        """A positive minimum needs something to ban: the request's own eos_token_id or the stop set."""
+        if min_new_tokens > 0 and (eos_token_id is None or eos_token_id < 0) and not self.stop_token_ids:
+            raise ValueError("StopRules: min_new_tokens needs eos_token_id or stop_token_ids (nothing to ban)")
 
     def to(self, device):
         """The arrays on ``device`` (one upload per call of a generate entry): a DeviceStopRules."""
         return DeviceStopRules(self, device)
 
-    def first_end(self, tokens, eos_token_id, budget=None):
+    def first_end(self, tokens, eos_token_id, budget=None, request=None):
         """Where a request that generates ``tokens`` (its own tokens only, no prompt) ends: -> (n_generated, reason).  Token i ends
         it -- in this order of precedence -- as EOS (1), as a stop token (2), when the last n tokens up to and including it equal a
         stop sequence of length n <= i + 1 (3), or when i + 1 == budget (4).  None of the rules fires: (len(tokens), 0).  The ban
-        before ``min_new_tokens`` acts on the scores, not here: a banned token cannot appear in ``tokens`` to begin with."""
+        before ``min_new_tokens`` acts on the scores, not here: a banned token cannot appear in ``tokens`` to begin with.  ``request``
+        (with per-request minima, and eos_token_id then the request's own): the request's minimum is taken -- an ending token
+        before it is a token the sampler cannot have emitted, which is an error of the caller's token list."""
         toks = [int(t) for t in tokens]
         stop = set(self.stop_token_ids)
+        floor = self.min_new(request) if request is not None else 0
         for i, t in enumerate(toks):
-            if eos_token_id is not None and eos_token_id >= 0 and t == int(eos_token_id):
+            is_eos = eos_token_id is not None and eos_token_id >= 0 and t == int(eos_token_id)
+            if i < floor and (is_eos or t in stop):
+                raise ValueError(f"StopRules.first_end: token {i} = {t} of request {request} is banned before its minimum {floor}")
+            if is_eos:
                 return i + 1, EOS
             if t in stop:
                 return i + 1, STOP_TOKEN
