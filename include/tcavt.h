@@ -1518,6 +1518,77 @@ int64_t tcavt_logprob_workspace_bytes(int rows, int hist_cap);
 int tcavt_logprob_begin(const tcavt_logprob_args* args, tcavt_stream_t stream);
 int tcavt_logprob_finish(const tcavt_logprob_args* args, tcavt_stream_t stream);
 
+/* Token-automaton constrained decoding: the sampler may only emit tokens that keep a row inside a form the caller can parse (HF
+ * prefix_allowed_tokens_fn / suppress_tokens with the rule held on the device).  The constraint is a deterministic automaton over
+ * token ids, stored by token class:
+ *   token_class   device int32 [V]: the class of every id, 0 <= class < n_classes; 16-byte aligned.
+ *   trans         device int32 [n_states][n_classes]: the next state, -1 = the class is not allowed in the state.
+ *   bitmap        device uint32 [n_states][(V + 31) / 32], written by tcavt_constraint_build: bit (id & 31) of word (id >> 5) of
+ *                 row s is set when id is allowed in state s -- the bit order of tcavt_stop_rules.stop_bitmap; bits at or beyond V
+ *                 are 0.
+ *   count         device int32 [n_states], written by tcavt_constraint_build: the number of tokens state s allows.
+ * Bounds: 1 <= n_states <= 4096, 1 <= n_classes <= 4096 (at the bounds: 64 MiB of trans; 4096 * (V + 31) / 32 * 4 bytes of bitmap,
+ * 62.6 MiB at V = 128 256).  A class or a target state outside its range counts as "not allowed"; no value makes a kernel read or
+ * write out of bounds.
+ * tcavt_constraint_build makes bitmap and count from token_class and trans (one launch, one workgroup per state); it runs once per
+ * table.  Refused before the launch (tcavt_last_error names the argument): a null pointer, V < 1, n_states or n_classes outside
+ * its bounds, a token_class that is not 16-byte aligned, another array that is not 4-byte aligned. */
+typedef struct tcavt_constraint_table {
+  const int32_t* token_class;
+  const int32_t* trans;
+  uint32_t* bitmap;
+  int32_t* count;
+  int32_t V, n_states, n_classes, reserved0;
+} tcavt_constraint_table;
+
+int tcavt_constraint_build(const tcavt_constraint_table* table, tcavt_stream_t stream);
+
+/* Two launches bracket ONE call of any token-selection entry (tcavt_sample_logits / _slots / _rows / tcavt_sample_tokens /
+ * tcavt_sample_tokens_per_request) on the same logits and state, stream-ordered; with tcavt_logprob_begin / _finish the order is
+ * logprob_begin, constraint_mask, the selection, constraint_advance, logprob_finish (the log-probabilities stay those of the raw
+ * row).  The form follows from the pointers as in tcavt_sample_tokens: slot_of_row != NULL: the rows form (logits row g works on
+ * slot slot_of_row[g] of n_state slots; entries < 0 or >= n_state are skipped; out_row required); else out_row != NULL: the slots
+ * form (step is [rows]); else the batch form (step is one word, n_req >= rows).  The REQUEST INDEX r of a row is the one of
+ * tcavt_sample_tokens_per_request: the row b, out_row[s], out_row[slot_of_row[row]].
+ *   tcavt_constraint_mask     a LIVE row (finished == 0; its slot and its r in range) has the state start[r] when its step word
+ *                             is 0 -- so an admission into a slot resets the state without a launch of its own -- and state[s]
+ *                             otherwise.  Every score of the row whose token the state does not allow becomes -inf; every other
+ *                             score keeps its bits (it is not even rewritten).  A state that allows all V tokens costs the read of
+ *                             its count.  rows x 16 workgroups; per row the traffic is at most the row itself plus V / 8 bytes
+ *                             of bitmap; token_class is not read.  What the row was -- live, slot, state, request -- is recorded
+ *                             in the workspace.
+ *   tcavt_constraint_advance  for the rows recorded live: state[s] = trans[state][token_class[cur_tok[s]]], also stored at
+ *                             request_state[r] when given (a request's record outlives its slot).  If the token is not allowed
+ *                             in the state (or lies outside [0, V)) the state stays and bit 0 of *flag is set.
+ * Inert, finished and skipped rows: no score, no state and no flag is written.  *flag (optional, caller-zeroed) collects: bit 0 a
+ * chosen token that its state does not allow; bit 1 a request index outside [0, n_req); bit 2 a state word outside [0, n_states)
+ * -- rows of the last two kinds are inert.
+ * workspace: tcavt_constraint_workspace_bytes(rows) bytes (0 for rows <= 0), 16-byte aligned, no initial contents needed; the
+ * pair of calls owns it from mask to advance.  Both entries are capturable and read nothing on the host.
+ * Refused before any launch (tcavt_last_error names the argument): what tcavt_constraint_build refuses of the table; a null
+ * pointer (slot_of_row, request_state and flag optional; out_row optional without slot_of_row); rows or n_req <= 0; slot_of_row
+ * with n_state <= 0; n_req < rows in the batch form; a misaligned array; a workspace that is too small or not 16-byte aligned. */
+typedef struct tcavt_constraint_args {
+  const tcavt_constraint_table* table;
+  float* logits;                     /* fp32 [rows][V], V = table->V; banned scores are overwritten in place */
+  const int32_t* slot_of_row;        /* rows form: device int32 [rows]; else NULL */
+  const int32_t* step;
+  const int64_t* out_row;            /* slots / rows forms; else NULL */
+  const int32_t* finished;
+  const int64_t* cur_tok;            /* the selection's result, read by _advance */
+  int32_t* state;                    /* device int32, one word per sample / slot */
+  const int32_t* start;              /* device int32 [n_req]: the start state of every request, in [0, n_states) */
+  int32_t* request_state;            /* optional: device int32 [n_req] */
+  int32_t* flag;                     /* optional: device int32 */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t rows, n_state, n_req, reserved0;
+} tcavt_constraint_args;
+
+int64_t tcavt_constraint_workspace_bytes(int rows);
+int tcavt_constraint_mask(const tcavt_constraint_args* args, tcavt_stream_t stream);
+int tcavt_constraint_advance(const tcavt_constraint_args* args, tcavt_stream_t stream);
+
 /* ---- Beam search (HF GenerationMixin._beam_search, num_beams = n, do_sample = False) on R = B * n decode rows, row r = b * n + j --
  * One step of the search is tcavt_beam_select on the step's logits followed by tcavt_beam_reorder; between two steps the caller
  * runs the decode step on cur_tok / pos.  Step 0 uses the prefill's logits (every row of a prompt holds a copy).  Prompts are

@@ -261,6 +261,21 @@ class LogprobArgs(ctypes.Structure):
         ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "V", "n_state", "hist_cap", "out_cap")]
 
 
+class ConstraintTable(ctypes.Structure):
+    """Mirror of ``tcavt_constraint_table`` (include/tcavt.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("token_class", "trans", "bitmap", "count")] + [
+        (n, ctypes.c_int32) for n in ("V", "n_states", "n_classes", "reserved0")]
+
+
+class ConstraintArgs(ctypes.Structure):
+    """Mirror of ``tcavt_constraint_args`` (include/tcavt.h)."""
+
+    _fields_ = [("table", ctypes.POINTER(ConstraintTable))] + [(n, c_void_p) for n in (
+        "logits", "slot_of_row", "step", "out_row", "finished", "cur_tok", "state", "start", "request_state", "flag", "workspace")] + [
+        ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "n_state", "n_req", "reserved0")]
+
+
 class BeamArgs(ctypes.Structure):
     """Mirror of ``tcavt_beam_args`` (include/tcavt.h)."""
 
@@ -513,10 +528,14 @@ _SIGNATURES = {
     "tcavt_spec_verify": [ctypes.POINTER(SpecVerifyArgs), c_void_p],
     "tcavt_sample_tokens_per_request": [ctypes.POINTER(SampleArgs), ctypes.POINTER(RequestParams), c_void_p],
     "tcavt_request_params_check": [ctypes.POINTER(SampleParams), c_void_p, c_int, c_int],
+    "tcavt_constraint_build": [ctypes.POINTER(ConstraintTable), c_void_p],
+    "tcavt_constraint_workspace_bytes": [c_int],
+    "tcavt_constraint_mask": [ctypes.POINTER(ConstraintArgs), c_void_p],
+    "tcavt_constraint_advance": [ctypes.POINTER(ConstraintArgs), c_void_p],
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64,
-             "tcavt_beam_workspace_bytes": c_int64}
+             "tcavt_beam_workspace_bytes": c_int64, "tcavt_constraint_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -6,6 +6,8 @@ one piece per job:
   select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens)
   LogprobRecord    return_logprobs: the three score tensors and the tcavt_logprob_begin / _finish bracket that select puts around
                    the sampler entry; rank_continuations orders a prompt's n continuations by them (host only)
+  ConstraintRecord, check_constraint   constraint=: the device table, the per-row states and the tcavt_constraint_mask / _advance
+                   bracket that select puts around the sampler entry, inside the log-probability bracket; the argument checks
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
   FinishedPoll     the finished flags to pinned host memory and an event wait
   decode_loop      the N - 1 steps behind the first selection: one eager, the rest replayed, polled or not
@@ -28,6 +30,7 @@ import torch
 
 from . import capi, ops
 from .pool import SlotScheduler
+from .constraint import TokenConstraint
 from .stopping import BUDGET, StopRules
 
 I32, I64 = torch.int32, torch.int64
@@ -224,16 +227,17 @@ class Prefill:
         return logits
 
 
-def slot_state(history, hist_len, step, cur, pos, finished, max_new=None, out_row=None):
+def slot_state(history, hist_len, step, cur, pos, finished, max_new=None, out_row=None, cstate=None):
     """The device-resident generation state the samplers advance: one row / entry per sample (step: one word), or -- with
-    max_new and out_row -- per decode slot."""
+    max_new and out_row -- per decode slot.  cstate: the automaton state words of a constrained call (ConstraintRecord)."""
     return SimpleNamespace(history=history, hist_len=hist_len, step=step, cur=cur, pos=pos, finished=finished, max_new=max_new,
-                           out_row=out_row)
+                           out_row=out_row, cstate=cstate)
 
 
 def slot_view(st, s):
     """The state of slot s alone, as views (the one-row logits of a request being admitted)."""
-    return slot_state(*(t[s:s + 1] for t in (st.history, st.hist_len, st.step, st.cur, st.pos, st.finished, st.max_new, st.out_row)))
+    return slot_state(*(t[s:s + 1] for t in (st.history, st.hist_len, st.step, st.cur, st.pos, st.finished, st.max_new, st.out_row)),
+                      cstate=None if st.cstate is None else st.cstate[s:s + 1])
 
 
 def check_bool(who, name, value):
@@ -279,18 +283,81 @@ def rank_continuations(sum_logprob, n_scored, n, length_penalty=1.0):
     return torch.argsort(score, dim=1, descending=True, stable=True)
 
 
-def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None, table=None):
+def check_constraint(who, mllm, constraint, constraint_start, num_beams, prompt_lookup_num_tokens, no_repeat_ngram_size, min_new_tokens):
+    """The arguments of a call with ``constraint`` or ``constraint_start`` set (the start states themselves are checked by
+    TokenConstraint.starts once the number of requests is known).  Nothing here touches a device."""
+    if constraint is None:
+        raise ValueError(f"{who}: constraint_start needs a constraint")
+    if not isinstance(constraint, TokenConstraint):
+        raise ValueError(f"{who}: constraint must be a constraint.TokenConstraint or None, got {type(constraint).__name__}")
+    for name, bad, why in (("num_beams > 1", num_beams != 1, "the per-row state would have to follow tcavt_beam_reorder"),
+                           ("prompt_lookup_num_tokens", prompt_lookup_num_tokens is not None,
+                            "the verification runs the sampler pass by pass inside one kernel")):
+        if bad:
+            raise ValueError(f"{who}: constraint is not built for {name} ({why})")
+
+    def values(v):
+        return v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else list(v) if isinstance(v, (list, tuple)) else [v]
+
+    # either can ban every token a state allows, and the sampler has no defined answer on a row without a finite score
+    if any(isinstance(v, numbers.Real) and v > 0 for v in values(no_repeat_ngram_size)):
+        raise ValueError(f"{who}: constraint needs no_repeat_ngram_size = 0, got {no_repeat_ngram_size!r} (the default is the reference's "
+                         "3: pass 0; a form repeats n-grams, and the ban can empty a row's allowed set)")
+    if any(isinstance(v, numbers.Real) and v > 0 for v in values(min_new_tokens)):
+        raise ValueError(f"{who}: constraint needs min_new_tokens = 0, got {min_new_tokens!r} (the automaton states a minimum length "
+                         "itself, and the ban can empty a row's allowed set)")
+    vocab = mllm.llama_wrapper.shape.vocab
+    if constraint.vocab != vocab:
+        raise ValueError(f"{who}: constraint is over {constraint.vocab} token ids, the model's vocabulary has {vocab}")
+
+
+class ConstraintRecord:
+    """The device side of a call's ``constraint``: the table (uploaded and built here, once per call: tcavt_constraint_build), the
+    start state of every request, the state word of every sample / slot, the final state per request, the flag word, and the
+    workspaces of the tcavt_constraint_mask / _advance bracket, one per logits shape, under ``{tag}.cs.ws`` -- new names,
+    requested only with a constraint."""
+
+    def __init__(self, ws, constraint, starts, n_state, dev):
+        self.ws, self.dev = ws, dev
+        self.table = ops.ConstraintTable(constraint.token_class, constraint.trans, dev).build()
+        self.start = starts.to(dev)
+        self.state = torch.zeros(n_state, dtype=I32, device=dev)
+        self.request_state = self.start.clone()
+        self.flag = torch.zeros(1, dtype=I32, device=dev)
+
+    def reserve(self, tag, rows):
+        """The bracket's workspace for ``rows`` logits rows under ``tag`` (requested here, so before any capture)."""
+        return self.ws.get(f"{tag}.cs.ws", (ops.constraint_workspace_bytes(rows),), torch.uint8, self.dev)
+
+    def args(self, tag, logits, st, slot_of_row):
+        return ops.constraint_args(self.table, logits, st.step, st.finished, st.cur, st.cstate, self.start,
+                                   self.reserve(tag, logits.shape[0]), out_row=st.out_row, slot_of_row=slot_of_row,
+                                   request_state=self.request_state, flag=self.flag)
+
+    def host(self):
+        return dict(constraint_state=self.request_state.cpu())
+
+
+def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None, table=None, cs=None):
     """Logits processors + token selection on the state ``st``.  The form follows from the arguments: ``slot_of_row`` -> the rows
     of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
     (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``lp`` (a LogprobRecord; its workspace
     under ``lp_tag``): the selection is bracketed by tcavt_logprob_begin / _finish, which read the raw row before the processors
     touch it and the chosen token afterwards; the selection itself is the one without.  ``table`` (an uploaded ops.RequestTable):
-    tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take."""
+    tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take.  ``cs`` (a ConstraintRecord; its
+    workspace under ``lp_tag`` too): tcavt_constraint_mask before and tcavt_constraint_advance after the selection, inside the
+    log-probability bracket -- the scores stay those of the raw row."""
     if lp is not None:
         largs = lp.args(lp_tag, logits, st, slot_of_row)
         ops.logprob_begin(largs)
-        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table)
+        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table, cs=cs, lp_tag=lp_tag)
         ops.logprob_finish(largs)
+        return
+    if cs is not None:
+        cargs = cs.args(lp_tag, logits, st, slot_of_row)
+        ops.constraint_mask(cargs)
+        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table)
+        ops.constraint_advance(cargs)
         return
     if table is not None:
         ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
@@ -479,7 +546,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
                    num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1, length_penalty=1.0,
-                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
+                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, constraint=None, constraint_start=None):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
@@ -492,6 +559,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     k = m = None
     nine = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                 no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)
+    if constraint is not None or constraint_start is not None:  # (before anything touches a device, and before the beam search)
+        check_constraint(who, mllm, constraint, constraint_start, num_beams, prompt_lookup_num_tokens, no_repeat_ngram_size, min_new_tokens)
     listed = per_request_names(**nine)
     if listed and (num_beams != 1 or prompt_lookup_num_tokens is not None):  # (beam search and tcavt_spec_verify keep the one struct)
         raise ValueError(f"{who}: per-request values ({', '.join(listed)}) are not built for "
@@ -540,7 +609,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         if not 0 <= int(pad_token_id) < mllm.llama_wrapper.shape.vocab:  # (the rows behind a draft feed the pad token to the step)
             raise ValueError(f"{who}: prompt_lookup_num_tokens needs pad_token_id inside [0, vocab), got {pad_token_id}")
     sp, table = request_params(who, src_B, n, rules, pad_token_id, **nine)  # (host only; a table: one entry per decode row)
-    mllm._request_flag = None
+    starts = constraint.starts(who, constraint_start, src_B, n) if constraint is not None else None  # (host only, likewise)
+    mllm._request_flag = mllm._constraint_flag = None
     dev = vision_embs_batch.device
     input_ids = input_ids.to(dev).contiguous()
     attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
@@ -593,7 +663,11 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
         drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
         lp = LogprobRecord(mllm._ws, out) if return_logprobs else None  # (the flag alone does not change the sampler entry)
-        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen", table=table)
+        cs = None
+        if constraint is not None:  # one upload and one build per call; the device arrays are fixed, so the captured step stays valid
+            cs = ConstraintRecord(mllm._ws, constraint, starts, B, dev)
+            st.cstate, mllm._constraint_flag = cs.state, cs.flag
+        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen", table=table, cs=cs)
         steps_run = 0
         drafted = accepted = None
         if N > 1 and k is not None:
@@ -609,7 +683,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                     ops.llama_decode_step(a)
                 else:
                     ops.llama_decode_step_shared(a, prefix)
-                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen", table=table)
+                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen", table=table, cs=cs)
 
             steps_run = decode_loop(one_step, N, B, dev, use_graph, poll_every, st.finished)
         info = None
@@ -623,6 +697,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                 info.update(drafted=zero if drafted is None else drafted.cpu(), accepted=zero.clone() if accepted is None else accepted.cpu())
         if lp is not None:
             info = dict(info or dict(steps=steps_run), **lp.host())
+        if cs is not None and return_info:
+            info.update(cs.host())
     return out, info
 
 
@@ -743,13 +819,16 @@ def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input
 # --------------------------------------------------------------------------------------
 def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k,
                   top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights,
-                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs=False):
+                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs=False,
+                  constraint=None, constraint_start=None):
     """-> (out int64 [R, max budget] on the device, mllm.pool_stats)."""
     who = "generate_pool"
     # ---- every illegal value is refused before anything touches a device
     check_format(who, "kv_cache", kv_cache)
     check_format(who, "decode_weights", decode_weights)
     check_bool(who, "return_logprobs", return_logprobs)
+    if constraint is not None or constraint_start is not None:
+        check_constraint(who, mllm, constraint, constraint_start, 1, None, no_repeat_ngram_size, min_new_tokens)
     rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
     S, poll_every = int(slots), int(poll_every)
     if S < 1:
@@ -777,7 +856,8 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
     sp, table = request_params(who, R, 1, rules, pad_token_id, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)  # (host only)
-    mllm._request_flag = None
+    starts = constraint.starts(who, constraint_start, R, 1) if constraint is not None else None  # (host only, likewise)
+    mllm._request_flag = mllm._constraint_flag = None
     dev = vision_embs.device
     out = torch.full((R, Nmax), int(pad_token_id), dtype=I64, device=dev)
     stats = mllm.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
@@ -787,6 +867,8 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             stats.update(finish_reason=torch.zeros(0, dtype=I32), n_generated=torch.zeros(0, dtype=I32))
         if return_logprobs:
             stats.update(token_logprobs=torch.zeros(0, Nmax), sum_logprob=torch.zeros(0), n_scored=torch.zeros(0, dtype=I32))
+        if constraint is not None and return_info:
+            stats.update(constraint_state=torch.zeros(0, dtype=I32))
         return out, stats
     input_ids = input_ids.to(dev).contiguous()
     mask64 = attention_mask.to(dev).to(I64).contiguous()
@@ -823,20 +905,24 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
         # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
         drules = rules.to(dev).records(R, dev) if return_info or not rules.empty else None
         lp = LogprobRecord(ws, out) if return_logprobs else None
+        cs = None
+        if constraint is not None:  # one upload and one build per call; a slot's state word is reset by the rule itself (step 0)
+            cs = ConstraintRecord(ws, constraint, starts, S, dev)
+            st.cstate, mllm._constraint_flag = cs.state, cs.flag
         # what both admission launches share: rows, src_lmax, kv_lmax, n_layers, S, nkv ... and the eight state arrays
         geometry = (L, L, Lmax, ll.layers, S, ll.n_kv_heads)
         state = (st.history, st.hist_len, st.step, st.max_new, st.out_row, st.pos, st.finished, st.cur)
 
         def one_step():
             ops.llama_decode_step(a)
-            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool", table=table)
+            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool", table=table, cs=cs)
 
         def admit(s, r):
             # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
             # and the first token from the one-row logits with the slot's state (views that start at slot s)
             logits1 = pf.run(vision_embs[r:r + 1], input_ids[r:r + 1], mask64[r:r + 1], after_stack=lambda: ops.slot_admit(
                 pf.buf("cache"), cache, s, *geometry, input_ids[r], pf.buf("kvlen"), Nq, budgets[r], r, *state))
-            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf", table=table)
+            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf", table=table, cs=cs)
 
         if G > 1:
             # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
@@ -868,7 +954,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             def group_pass():
                 logits_g = pg.run(pg_vis, pg_ids, pg_mask, after_stack=lambda: ops.slot_admit_group(
                     pg.buf("cache"), cache, pg_slot, *geometry, pg_ids, pg.buf("kvlen"), Nq, pg_budget, pg_outrow, bad_slot, *state))
-                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg", table=table)
+                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg", table=table, cs=cs)
 
         sched = SlotScheduler(R, S, G)
         step = later_pass = None
@@ -904,4 +990,6 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
         if lp is not None:
             stats.update(lp.host())
+        if cs is not None and return_info:
+            stats.update(cs.host())
     return out, stats

@@ -43,7 +43,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
         self._ws = _Workspace()
         self._prep = None
         self._pf_stream = self._pf = self._img_consumed = None
-        self._last_flags = self._lm_flag = self._pool_flag = self._request_flag = None  # device error flags of the passes so far (check_flags)
+        self._last_flags = self._lm_flag = self._pool_flag = self._request_flag = self._constraint_flag = None  # device error flags of the passes so far (check_flags)
 
     def _image_tokens(self, vision_embs):
         """Q-Former + q_proj (train.py:519-521): image tokens [B*Nq, H] fp32, before the modality embedding."""
@@ -214,6 +214,13 @@ class LlamaMultiModal(nn.Module, _Prepared):
         if self._request_flag is not None and self._request_flag.item():
             self._request_flag.zero_()
             raise ValueError("a sampler row named a request outside the per-request parameter table (tcavt_sample_tokens_per_request)")
+        if self._constraint_flag is not None and self._constraint_flag.item():
+            bits = int(self._constraint_flag.item())
+            self._constraint_flag.zero_()
+            raise RuntimeError("constrained decoding: " + "; ".join(why for bit, why in (
+                (1, "the sampler chose a token that the row's state does not allow (tcavt_constraint_advance)"),
+                (2, "a row named a request outside the table of start states"), (4, "a row's state word lies outside the automaton"))
+                if bits & bit))
         if self._last_flags is None:
             return
         f = self._last_flags.tolist()
@@ -234,7 +241,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
                        poll_every=None, num_return_sequences=1, share_prefix=False, prompt_lookup_num_tokens=None,
-                       max_matching_ngram_size=2, return_logprobs=False, num_beams=1, length_penalty=1.0, early_stopping=False):
+                       max_matching_ngram_size=2, constraint=None, constraint_start=None, return_logprobs=False, num_beams=1,
+                       length_penalty=1.0, early_stopping=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -334,6 +342,26 @@ class LlamaMultiModal(nn.Module, _Prepared):
         ``stop_token_ids`` and ``stop_sequences`` stay one value per call.  Refused with ValueError together with num_beams > 1 or
         prompt_lookup_num_tokens (beam search and tcavt_spec_verify keep the one struct).  With nine single values the call is
         launch for launch, buffer for buffer and bit for bit the call without this.
+        ``constraint`` = a constraint.TokenConstraint ("constrained decoding"): every row may only emit tokens
+        that its automaton state allows -- HF's prefix_allowed_tokens_fn / suppress_tokens / allowed vocabulary, with the rule held
+        on the device.  The automaton goes to the device once per call (tcavt_constraint_build: one allowed-token bitmap per
+        state), and every token selection, in the captured step too, becomes [logprob_begin ->] tcavt_constraint_mask -> the
+        selection entry the call takes anyway -> tcavt_constraint_advance [-> logprob_finish]: the mask writes -inf over the scores
+        of the tokens the row's state does not allow (the sampler treats -inf as banned on every path; the repetition penalty and
+        the warpers never un-ban a score, so this equals HF's order), the advance follows the chosen token.  Log-probabilities stay
+        those of the raw row.  ``constraint_start``: None (the constraint's own start state), one state, or a list / tuple / 1-D
+        tensor of B states, one per prompt (TokenConstraint.union returns the start of each member); with
+        ``num_return_sequences`` = n every continuation of a prompt starts in the prompt's state.  return_info adds
+        "constraint_state": the final state per row, host int32 [B * n].  decode_weights, kv_cache, num_return_sequences,
+        share_prefix, return_logprobs, stop tokens and stop sequences, poll_every and per-request parameters work as above.
+        Refused with ValueError before anything touches a device: num_beams > 1 (the per-row state would have to follow
+        tcavt_beam_reorder), prompt_lookup_num_tokens (the verification runs the sampler pass by pass inside one kernel),
+        no_repeat_ngram_size > 0 or min_new_tokens > 0 as one value or in any list element (either can ban every token a state
+        allows, and the sampler has no defined answer on a row without a finite score; an automaton states a minimum length
+        itself, and a form needs repeated n-grams) -- no_repeat_ngram_size defaults to 3 from the reference: pass 0 --, a
+        constraint over another vocabulary, a start state outside the automaton.  With those excluded and every state validated
+        non-empty no row reaches the sampler empty; a chosen token outside the state would set a flag that check_flags() raises
+        as RuntimeError.  None, the default, is launch for launch and bit for bit the call without the argument.
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
@@ -341,7 +369,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
             stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
             return_logprobs, num_beams, length_penalty, early_stopping, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size)
+            max_matching_ngram_size=max_matching_ngram_size, constraint=constraint, constraint_start=constraint_start)
         res = self._generated_texts(out)
         return (res, info) if return_info or return_logprobs else res
 
@@ -354,7 +382,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
     def generate_pool(self, vision_embs, input_ids, attention_mask, max_new_tokens=128, slots=8, poll_every=1, do_sample=True,
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
                       pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1,
-                      stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False, return_logprobs=False):
+                      stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False, return_logprobs=False,
+                      constraint=None, constraint_start=None):
         """Text generation over a LIST of R requests on a fixed pool of ``slots`` decode slots ("slot
         pool"): request r is served exactly once, first in first out, and the moment a request ends (EOS, or its budget) the
         next one of the queue is prefilled into its slot -- no decode row computes pad tokens for longer than one poll interval.
@@ -401,10 +430,18 @@ class LlamaMultiModal(nn.Module, _Prepared):
         partners' parameters (for a fixed G).  A positive minimum needs that request's own eos_token_id, or stop_token_ids.
         ``pad_token_id`` (idle and finished slots feed it to the decode step), ``stop_token_ids`` and ``stop_sequences`` stay one
         value per call.  A row that names a request outside the table is inert and sets a flag that check_flags() reports.  With
-        nine single values the call is launch for launch, buffer for buffer and bit for bit the call without this."""
+        nine single values the call is launch for launch, buffer for buffer and bit for bit the call without this.
+        ``constraint`` / ``constraint_start``: constrained decoding as in generate_batch, around all three sampler uses;
+        ``constraint_start`` is one state or one per request, so that the requests of one list can follow different forms
+        (TokenConstraint.union).  A slot's state is reset by the rule itself -- a row whose step word is 0 takes its request's start
+        state -- so the admission launches are unchanged, and a request's tokens stay independent of slot, schedule and partners
+        (for a fixed G).  return_info adds "constraint_state": host int32 [R], every request's final state.  Refused with
+        ValueError before anything touches a device: no_repeat_ngram_size > 0 (the default is 3: pass 0) or min_new_tokens > 0, as
+        one value or in any list element; a constraint over another vocabulary; a start state outside the automaton."""
         out, stats = generation.generate_pool(
             self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
             repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs)
+            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs, constraint=constraint,
+            constraint_start=constraint_start)
         res = self._generated_texts(out)
         return (res, stats) if return_info or return_logprobs else res

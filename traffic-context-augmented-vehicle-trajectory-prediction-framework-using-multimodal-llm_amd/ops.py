@@ -1325,6 +1325,79 @@ def logprob_finish(args):
     check(lib().tcavt_logprob_finish(ctypes.byref(args), stream_ptr()), "tcavt_logprob_finish")
 
 
+class ConstraintTable:
+    """The device side of a constraint.TokenConstraint (tcavt_constraint_table): token_class int32 [V] and trans int32 [n_states,
+    n_classes] uploaded, bitmap int32 [n_states, ceil(V / 32)] (the uint32 words) and count int32 [n_states] made by ``build()``
+    (tcavt_constraint_build), once per call of a generate entry."""
+
+    def __init__(self, token_class, trans, device):
+        for t, dim, nm in ((token_class, 1, "token_class"), (trans, 2, "trans")):
+            if t.dtype != torch.int32 or t.dim() != dim:
+                raise capi.TcavtError(f"constraint table: {nm} must be an int32 tensor with {dim} dimension(s)")
+        self.V, (self.n_states, self.n_classes) = token_class.numel(), trans.shape
+        self.token_class, self.trans = token_class.contiguous().to(device), trans.contiguous().to(device)
+        self.bitmap = torch.empty(self.n_states, (self.V + 31) // 32, dtype=torch.int32, device=device)
+        self.count = torch.empty(self.n_states, dtype=torch.int32, device=device)
+        t = self.struct = capi.ConstraintTable()
+        capi.bind(t, token_class=self.token_class, trans=self.trans, bitmap=self.bitmap, count=self.count)
+        t.V, t.n_states, t.n_classes = self.V, self.n_states, self.n_classes
+
+    def build(self):
+        check(lib().tcavt_constraint_build(ctypes.byref(self.struct), stream_ptr()), "tcavt_constraint_build")
+        return self
+
+
+def constraint_workspace_bytes(rows):
+    """Bytes of the workspace of constraint_mask / constraint_advance for ``rows`` logits rows."""
+    return int(capi.lib().tcavt_constraint_workspace_bytes(int(rows)))
+
+
+def constraint_args(table, logits, step, finished, cur_tok, state, start, workspace, out_row=None, slot_of_row=None,
+                    request_state=None, flag=None):
+    """The tcavt_constraint_args of one bracket around a token selection on the same logits and state (the form follows from
+    slot_of_row / out_row as in sample_tokens), each tensor checked first.  table: a built ConstraintTable; state int32, one word
+    per sample / slot; start int32 [n_req], the start state of every request; request_state int32 [n_req] and flag int32 [1]
+    optional; workspace uint8 of constraint_workspace_bytes(rows)."""
+    who = "constraint"
+    rows, V = logits.shape
+    if V != table.V:
+        raise capi.TcavtError(f"constraint: the table is over {table.V} token ids, the logits have {V}")
+    if slot_of_row is not None and out_row is None:
+        raise capi.TcavtError("constraint: out_row is missing (slot_of_row is given)")
+    slots = out_row is not None
+    n = state.numel() if slot_of_row is not None else rows
+    n_req = start.numel()
+    if not slots and n_req < rows:
+        raise capi.TcavtError(f"constraint: start has {n_req} entries for {rows} rows")
+    _req(logits, torch.float32, f"{who}.logits")
+    per_slot = ((out_row, torch.int64, n, "out_row"),) if slots else ()
+    per_row = ((slot_of_row, torch.int32, rows, "slot_of_row"),) if slot_of_row is not None else ()
+    optional = tuple((t, torch.int32, k, nm) for t, k, nm in ((request_state, n_req, "request_state"), (flag, 1, "flag")) if t is not None)
+    for t, dt, k, nm in ((step, torch.int32, n if slots else 1, "step"), *per_slot, *per_row, (finished, torch.int32, n, "finished"),
+                         (cur_tok, torch.int64, n, "cur_tok"), (state, torch.int32, n, "state"), (start, torch.int32, 1, "start"),
+                         *optional, (workspace, torch.uint8, constraint_workspace_bytes(rows), "workspace")):
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+    a = capi.ConstraintArgs()
+    a.table = ctypes.pointer(table.struct)
+    capi.bind(a, logits=logits, slot_of_row=slot_of_row, step=step, out_row=out_row, finished=finished, cur_tok=cur_tok, state=state,
+              start=start, request_state=request_state, flag=flag, workspace=workspace)
+    a.workspace_bytes, a.rows, a.n_state, a.n_req = workspace.numel(), rows, n, n_req
+    return a
+
+
+def constraint_mask(args):
+    """Before the token selection: -inf over the tokens the row's state does not allow (tcavt_constraint_mask)."""
+    check(lib().tcavt_constraint_mask(ctypes.byref(args), stream_ptr()), "tcavt_constraint_mask")
+
+
+def constraint_advance(args):
+    """After the token selection: the state of every row that was live follows the chosen token (tcavt_constraint_advance)."""
+    check(lib().tcavt_constraint_advance(ctypes.byref(args), stream_ptr()), "tcavt_constraint_advance")
+
+
 BEAMS_MAX = 16  # beams per prompt of tcavt_beam_select / tcavt_beam_reorder
 
 
