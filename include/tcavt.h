@@ -1518,6 +1518,39 @@ int64_t tcavt_logprob_workspace_bytes(int rows, int hist_cap);
 int tcavt_logprob_begin(const tcavt_logprob_args* args, tcavt_stream_t stream);
 int tcavt_logprob_finish(const tcavt_logprob_args* args, tcavt_stream_t stream);
 
+/* Top-k alternatives: the k most likely tokens of the raw row with their log-probabilities, at every position a live row
+ * generates (OpenAI top_logprobs, vLLM logprobs=k).  One call inside the bracket of tcavt_logprob_begin / _finish, after begin
+ * and before anything writes the logits -- the order is logprob_begin, logprob_topk, [constraint_mask], the selection,
+ * [constraint_advance], logprob_finish -- because the repetition penalty and tcavt_constraint_mask rewrite scores in place and
+ * the list is of the row as the lm_head wrote it.  `lp` is the bracket's own struct: the logits, the form, step, out_row, finished,
+ * out_cap and the workspace in which begin recorded, per row, whether it was live, its step word, its slot and the 16 partials.
+ * For every LIVE row, at row * out_cap + step_before with `row` as for token_logprobs (the sample, out_row[s] or
+ * out_row[slot_of_row[g]]), k innermost:
+ *     top_ids[..][0 .. k)     the k first token ids of the row by (raw fp32 score descending, id ascending): decided by comparisons
+ *                             of the exact fp32 inputs alone, so fully determined -- ties, -inf entries and +-0.0 (equal) included
+ *     top_logprobs[..][i]     (x_id - M) - log S, M and log S formed from the 16 partials in slice order exactly as
+ *                             tcavt_logprob_finish forms them: when the emitted token is in the list its entry equals
+ *                             token_logprobs at that position bit for bit
+ * Inert, finished and skipped rows write nothing; the caller initialises both arrays (generate_*: -1 / -inf).  A row's lists are
+ * the same bits whatever logits row, slot or partner rows it runs with; no atomics; nothing is read on the host; capturable.
+ * Two launches: rows x 16 workgroups take each slice's k best from registers, one wave per row merges the 16 * k candidates.
+ * Bounds: 1 <= k <= 20, k <= V <= 262144.  workspace: tcavt_logprob_topk_workspace_bytes(rows, k) bytes (0 for rows <= 0),
+ * 16-byte aligned, no initial contents needed, its own (not the bracket's).
+ * Refused before any launch (tcavt_last_error names the argument): a null pointer; anything tcavt_logprob_begin refuses of lp
+ * (reported as "lp: ..."); k outside [1, 20] or k > V; V > 262144; top_ids or top_logprobs not 4-byte aligned; a workspace that
+ * is too small or not 16-byte aligned. */
+typedef struct tcavt_logprob_topk_args {
+  const tcavt_logprob_args* lp;      /* the bracket this launch belongs to */
+  int32_t* top_ids;                  /* device int32 [n_out][out_cap][k], indexed like lp->token_logprobs, k innermost */
+  float* top_logprobs;               /* device fp32  [n_out][out_cap][k] */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t k, reserved0;
+} tcavt_logprob_topk_args;
+
+int64_t tcavt_logprob_topk_workspace_bytes(int rows, int k);
+int tcavt_logprob_topk(const tcavt_logprob_topk_args* args, tcavt_stream_t stream);
+
 /* Token-automaton constrained decoding: the sampler may only emit tokens that keep a row inside a form the caller can parse (HF
  * prefix_allowed_tokens_fn / suppress_tokens with the rule held on the device).  The constraint is a deterministic automaton over
  * token ids, stored by token class:
@@ -1545,8 +1578,8 @@ int tcavt_constraint_build(const tcavt_constraint_table* table, tcavt_stream_t s
 
 /* Two launches bracket ONE call of any token-selection entry (tcavt_sample_logits / _slots / _rows / tcavt_sample_tokens /
  * tcavt_sample_tokens_per_request) on the same logits and state, stream-ordered; with tcavt_logprob_begin / _finish the order is
- * logprob_begin, constraint_mask, the selection, constraint_advance, logprob_finish (the log-probabilities stay those of the raw
- * row).  The form follows from the pointers as in tcavt_sample_tokens: slot_of_row != NULL: the rows form (logits row g works on
+ * logprob_begin, [logprob_topk,] constraint_mask, the selection, constraint_advance, logprob_finish (the log-probabilities stay
+ * those of the raw row).  The form follows from the pointers as in tcavt_sample_tokens: slot_of_row != NULL: the rows form (logits row g works on
  * slot slot_of_row[g] of n_state slots; entries < 0 or >= n_state are skipped; out_row required); else out_row != NULL: the slots
  * form (step is [rows]); else the batch form (step is one word, n_req >= rows).  The REQUEST INDEX r of a row is the one of
  * tcavt_sample_tokens_per_request: the row b, out_row[s], out_row[slot_of_row[row]].

@@ -1,7 +1,7 @@
 """Text-generation throughput at the full model size (Llama-3.2-1B shape): prefill + hipGraph-replayed decode steps
 (BASELINE.json configs[4] "hipGraph-captured decode"; reference: scripts/train.py:577-654).  One MI355X.
     python tools/bench_generate.py [--batch 32] [--new 64] [--text-len 240] [--no-graph] [--greedy] [--decode-weights fp8] [--kv-cache fp8]
-        [--num-return-sequences 8 [--share-prefix]] [--logprobs]"""
+        [--num-return-sequences 8 [--share-prefix]] [--logprobs] [--top-logprobs 5 20 [--pool-slots 8 32]]"""
 import argparse
 import json
 import os
@@ -33,6 +33,12 @@ ap.add_argument("--share-prefix", action="store_true",
 ap.add_argument("--logprobs", action="store_true",
                 help="A/B of generate_batch(return_logprobs=True) against the call without it, arms alternating in one process: "
                      "ms per decode step of each arm (the two launches of the bracket and one more read of the logits)")
+ap.add_argument("--top-logprobs", type=int, nargs="+", default=None, metavar="K",
+                help="A/B of generate_batch(return_logprobs=True, top_logprobs=k) for every k given against return_logprobs=True "
+                     "alone, arms alternating in one process: ms per decode step of each arm (the two launches of "
+                     "tcavt_logprob_topk and one more read of the logits)")
+ap.add_argument("--pool-slots", type=int, nargs="*", default=[],
+                help="with --top-logprobs: also one generate_pool run per arm and slot count on a 256-request list (budgets 16 .. 128)")
 args = ap.parse_args()
 capi.init(0)
 dev = torch.device("cuda:0")
@@ -232,6 +238,77 @@ def logprobs_ab():
         "mean_logprob_per_token": round(float((info["sum_logprob"] / info["n_scored"]).mean()), 4),
         "finite": bool(torch.isfinite(info["token_logprobs"]).all().item() and ((out >= 0) & (out < ll.vocab)).all().item())}))
 
+
+def top_logprobs_ab(ks):
+    """Arm 0: return_logprobs=True; arm k: the same call with top_logprobs=k.  A timed call is a whole generation ending in a device
+    synchronise; ms per decode step = (time of args.new tokens - time of 1 token) / (args.new - 1), per round of all arms."""
+    arms = [None] + list(ks)
+
+    def arm(k, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = m.mllm.generate_batch(g["vision_emb"], None, max_new_tokens=new, return_logprobs=True, top_logprobs=k, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res
+
+    for k in arms:  # packed weights, workspaces, every kernel form, the clocks
+        arm(k, 4)
+        arm(k, args.new)
+    step, first, last = {k: [] for k in arms}, {k: [] for k in arms}, {}
+    for _ in range(args.reps):
+        for k in arms:
+            t1, _ = arm(k, 1)
+            tn, last[k] = arm(k, args.new)
+            step[k].append((tn - t1) / max(args.new - 1, 1) * 1e3)
+            first[k].append(t1 * 1e3)
+    m.mllm.check_flags()
+    stat = lambda v: dict(median=round(sorted(v)[len(v) // 2], 4), min=round(min(v), 4), max=round(max(v), 4))
+    base = stat(step[None])
+    ll = cfg.llama
+    rec = {"workload": f"generate_batch: B={args.batch}, prompt {cfg.q_num_query_tokens}+{args.text_len} tokens (ragged), {args.new} new "
+                       f"tokens, {'greedy' if args.greedy else 'sampling'}, {'eager' if args.no_graph else 'hipGraph replay'}, "
+                       f"decode_weights={args.decode_weights}, kv_cache={args.kv_cache}; {args.reps} alternating rounds",
+           "logprobs_decode_ms_per_step": base, "logprobs_spread_us": round((base["max"] - base["min"]) * 1e3, 2),
+           "logprobs_prefill_plus_first_token_ms": stat(first[None]), "logits_bytes_read_again_per_step": 4 * ll.vocab * args.batch}
+    out0, info0 = last[None]
+    for k in ks:
+        on = stat(step[k])
+        out, info = last[k]
+        ids, lps = info["top_token_ids"], info["top_token_logprobs"]
+        rec[f"top{k}"] = {
+            "decode_ms_per_step": on, "minus_logprobs_us_per_step": round((on["median"] - base["median"]) * 1e3, 2),
+            "over_logprobs_median": round(on["median"] / base["median"], 4), "prefill_plus_first_token_ms": stat(first[k]),
+            "tokens_and_logprobs_equal_to_arm_0": bool(torch.equal(out, out0) and torch.equal(info["token_logprobs"], info0["token_logprobs"])),
+            "lists_sorted_and_in_range": bool((lps[..., :-1] >= lps[..., 1:]).all().item() and ((ids >= 0) & (ids < ll.vocab)).all().item()),
+            "emitted_token_listed_frac": round(float((ids == out.cpu()[..., None]).any(-1).float().mean()), 4)}
+    print(json.dumps(rec))
+    if args.pool_slots:
+        import numpy as np
+
+        R = 256
+        b = synth.make_batch(cfg, R, text_len=args.text_len, seed=3, ragged=True, min_text=min(128, args.text_len // 2))
+        q = {k_: torch.from_numpy(v).to(dev) for k_, v in b.items()}
+        budgets = np.random.default_rng(7).integers(16, 129, size=R).tolist()  # the list of tools/bench_generate_pool.py
+        for S in args.pool_slots:
+            pool = {}
+            for rnd in range(2):  # the first round is the warm-up of every form at this pool size
+                for k in arms:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    m.mllm.generate_pool(q["vision_emb"], q["input_ids"], q["attention_mask"], max_new_tokens=budgets, slots=S,
+                                         do_sample=not args.greedy, return_logprobs=True, top_logprobs=k)
+                    torch.cuda.synchronize()
+                    pool[k] = round(time.perf_counter() - t0, 4)
+            m.mllm.check_flags()
+            print(json.dumps({"workload": f"generate_pool: {R} requests, budgets 16..128 ({sum(budgets)} tokens), {S} slots, admit_group=1, "
+                                          "poll_every=1; one timed run per arm after one warm-up run",
+                              "wall_s": {("logprobs" if k is None else f"top{k}"): v for k, v in pool.items()},
+                              "steps": m.mllm.pool_stats["steps"]}))
+
+
+if args.top_logprobs:
+    top_logprobs_ab(args.top_logprobs)
+    sys.exit(0)
 
 if args.logprobs:
     logprobs_ab()

@@ -261,6 +261,13 @@ class LogprobArgs(ctypes.Structure):
         ("workspace_bytes", c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "V", "n_state", "hist_cap", "out_cap")]
 
 
+class LogprobTopkArgs(ctypes.Structure):
+    """Mirror of ``tcavt_logprob_topk_args`` (include/tcavt.h)."""
+
+    _fields_ = [("lp", ctypes.POINTER(LogprobArgs)), ("top_ids", c_void_p), ("top_logprobs", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_int64), ("k", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+
 class ConstraintTable(ctypes.Structure):
     """Mirror of ``tcavt_constraint_table`` (include/tcavt.h)."""
 
@@ -517,6 +524,8 @@ _SIGNATURES = {
     "tcavt_logprob_workspace_bytes": [c_int, c_int],
     "tcavt_logprob_begin": [ctypes.POINTER(LogprobArgs), c_void_p],
     "tcavt_logprob_finish": [ctypes.POINTER(LogprobArgs), c_void_p],
+    "tcavt_logprob_topk_workspace_bytes": [c_int, c_int],
+    "tcavt_logprob_topk": [ctypes.POINTER(LogprobTopkArgs), c_void_p],
     "tcavt_beam_workspace_bytes": [c_int],
     "tcavt_beam_select": [ctypes.POINTER(BeamArgs), c_void_p],
     "tcavt_beam_reorder": [ctypes.POINTER(BeamReorderArgs), c_void_p],
@@ -535,7 +544,8 @@ _SIGNATURES = {
 }
 _RESTYPES = {"tcavt_last_error": ctypes.c_char_p, "tcavt_sample_workspace_bytes": c_int64, "tcavt_pack_weight8_bytes": ctypes.c_size_t,
              "tcavt_lm_loss_workspace_bytes": c_int64, "tcavt_lm_eval_workspace_bytes": c_int64, "tcavt_logprob_workspace_bytes": c_int64,
-             "tcavt_beam_workspace_bytes": c_int64, "tcavt_constraint_workspace_bytes": c_int64}
+             "tcavt_beam_workspace_bytes": c_int64, "tcavt_constraint_workspace_bytes": c_int64,
+             "tcavt_logprob_topk_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

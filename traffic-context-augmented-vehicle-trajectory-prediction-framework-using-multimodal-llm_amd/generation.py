@@ -5,7 +5,8 @@ one piece per job:
   Prefill          image tokens + prompt through the decoder into a KV cache, last rows through the lm_head -> first logits
   select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens)
   LogprobRecord    return_logprobs: the three score tensors and the tcavt_logprob_begin / _finish bracket that select puts around
-                   the sampler entry; rank_continuations orders a prompt's n continuations by them (host only)
+                   the sampler entry; rank_continuations orders a prompt's n continuations by them (host only);
+                   top_logprobs = k (check_top_logprobs): the two list tensors and tcavt_logprob_topk right after begin
   ConstraintRecord, check_constraint   constraint=: the device table, the per-row states and the tcavt_constraint_mask / _advance
                    bracket that select puts around the sampler entry, inside the log-probability bracket; the argument checks
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
@@ -248,14 +249,19 @@ def check_bool(who, name, value):
 class LogprobRecord:
     """The scores of return_logprobs: device tensors indexed like ``out`` (token_logprobs fp32 [rows, N] filled with 0.0, as out
     is with the pad id; sum_logprob fp32 [rows]; n_scored int32 [rows]) and the workspaces of the tcavt_logprob_begin / _finish
-    bracket, one per logits shape, under ``{tag}.lp.ws`` -- new names, requested only with the flag."""
+    bracket, one per logits shape, under ``{tag}.lp.ws`` -- new names, requested only with the flag.  ``top_k`` (top_logprobs = k):
+    also top_ids int32 and top_logprobs fp32 [rows, N, k], filled with -1 / -inf (the kernel writes the positions a live row
+    generates and nothing else), and the workspaces of tcavt_logprob_topk under ``{tag}.lp.top.ws``, requested only with it."""
 
-    def __init__(self, ws, out):
+    def __init__(self, ws, out, top_k=None):
         rows, dev = out.shape[0], out.device
-        self.ws, self.out = ws, out
+        self.ws, self.out, self.top_k = ws, out, top_k
         self.token_logprobs = torch.zeros(out.shape, dtype=torch.float32, device=dev)
         self.sum_logprob = torch.zeros(rows, dtype=torch.float32, device=dev)
         self.n_scored = torch.zeros(rows, dtype=I32, device=dev)
+        if top_k is not None:
+            self.top_ids = torch.full(tuple(out.shape) + (top_k,), -1, dtype=I32, device=dev)
+            self.top_logprobs = torch.full(tuple(out.shape) + (top_k,), float("-inf"), dtype=torch.float32, device=dev)
 
     def reserve(self, tag, rows, hist_cap):
         """The bracket's workspace for ``rows`` logits rows under ``tag`` (requested here, so before any capture)."""
@@ -266,8 +272,28 @@ class LogprobRecord:
                                 self.n_scored, self.reserve(tag, logits.shape[0], st.history.shape[1]), out_row=st.out_row,
                                 slot_of_row=slot_of_row)
 
+    def topk_args(self, tag, largs):
+        """The tcavt_logprob_topk launch inside the bracket ``largs`` (its workspace requested here, so before any capture)."""
+        wsb = self.ws.get(f"{tag}.lp.top.ws", (ops.logprob_topk_workspace_bytes(largs.rows, self.top_k),), torch.uint8, self.out.device)
+        return ops.logprob_topk_args(largs, self.out, self.top_ids, self.top_logprobs, wsb)
+
     def host(self):
-        return dict(token_logprobs=self.token_logprobs.cpu(), sum_logprob=self.sum_logprob.cpu(), n_scored=self.n_scored.cpu())
+        res = dict(token_logprobs=self.token_logprobs.cpu(), sum_logprob=self.sum_logprob.cpu(), n_scored=self.n_scored.cpu())
+        if self.top_k is not None:
+            res.update(top_token_ids=self.top_ids.cpu().to(I64), top_token_logprobs=self.top_logprobs.cpu())
+        return res
+
+
+def check_top_logprobs(who, top_logprobs, return_logprobs):
+    """top_logprobs = k -> k as an int, None -> None.  Nothing here touches a device."""
+    if top_logprobs is None:
+        return None
+    k = top_logprobs
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= ops.TOP_LOGPROBS_MAX:
+        raise ValueError(f"{who}: top_logprobs must be None or an int in [1, {ops.TOP_LOGPROBS_MAX}], got {top_logprobs!r}")
+    if return_logprobs is not True:
+        raise ValueError(f"{who}: top_logprobs needs return_logprobs=True (got return_logprobs={return_logprobs!r})")
+    return int(k)
 
 
 def rank_continuations(sum_logprob, n_scored, n, length_penalty=1.0):
@@ -343,13 +369,16 @@ def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None
     of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
     (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``lp`` (a LogprobRecord; its workspace
     under ``lp_tag``): the selection is bracketed by tcavt_logprob_begin / _finish, which read the raw row before the processors
-    touch it and the chosen token afterwards; the selection itself is the one without.  ``table`` (an uploaded ops.RequestTable):
+    touch it and the chosen token afterwards; the selection itself is the one without; a record with ``top_k`` adds
+    tcavt_logprob_topk right after begin.  ``table`` (an uploaded ops.RequestTable):
     tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take.  ``cs`` (a ConstraintRecord; its
     workspace under ``lp_tag`` too): tcavt_constraint_mask before and tcavt_constraint_advance after the selection, inside the
     log-probability bracket -- the scores stay those of the raw row."""
     if lp is not None:
         largs = lp.args(lp_tag, logits, st, slot_of_row)
         ops.logprob_begin(largs)
+        if lp.top_k is not None:  # the raw row's k best, before the mask or the selection rewrites a score
+            ops.logprob_topk(lp.topk_args(lp_tag, largs))
         select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table, cs=cs, lp_tag=lp_tag)
         ops.logprob_finish(largs)
         return
@@ -546,7 +575,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                    top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
                    decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
                    num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1, length_penalty=1.0,
-                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, constraint=None, constraint_start=None):
+                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, constraint=None, constraint_start=None,
+                   top_logprobs=None):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
@@ -557,6 +587,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     the same Philox rows and the same tokens as the batch form) and a step is prompt_lookup_step above; None is the call without."""
     who = "generate_batch"
     k = m = None
+    n_top = check_top_logprobs(who, top_logprobs, return_logprobs)  # (before anything touches a device; beams and prompt lookup
+    #                                                                   refuse return_logprobs=True below, and with it this)
     nine = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                 no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)
     if constraint is not None or constraint_start is not None:  # (before anything touches a device, and before the beam search)
@@ -662,7 +694,7 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
         sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
         # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
         drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
-        lp = LogprobRecord(mllm._ws, out) if return_logprobs else None  # (the flag alone does not change the sampler entry)
+        lp = LogprobRecord(mllm._ws, out, n_top) if return_logprobs else None  # (the flag alone does not change the sampler entry)
         cs = None
         if constraint is not None:  # one upload and one build per call; the device arrays are fixed, so the captured step stays valid
             cs = ConstraintRecord(mllm._ws, constraint, starts, B, dev)
@@ -820,9 +852,10 @@ def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input
 def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k,
                   top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights,
                   kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs=False,
-                  constraint=None, constraint_start=None):
+                  constraint=None, constraint_start=None, top_logprobs=None):
     """-> (out int64 [R, max budget] on the device, mllm.pool_stats)."""
     who = "generate_pool"
+    n_top = check_top_logprobs(who, top_logprobs, return_logprobs)
     # ---- every illegal value is refused before anything touches a device
     check_format(who, "kv_cache", kv_cache)
     check_format(who, "decode_weights", decode_weights)
@@ -867,6 +900,8 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             stats.update(finish_reason=torch.zeros(0, dtype=I32), n_generated=torch.zeros(0, dtype=I32))
         if return_logprobs:
             stats.update(token_logprobs=torch.zeros(0, Nmax), sum_logprob=torch.zeros(0), n_scored=torch.zeros(0, dtype=I32))
+            if n_top is not None:
+                stats.update(top_token_ids=torch.zeros(0, Nmax, n_top, dtype=I64), top_token_logprobs=torch.zeros(0, Nmax, n_top))
         if constraint is not None and return_info:
             stats.update(constraint_state=torch.zeros(0, dtype=I32))
         return out, stats
@@ -904,7 +939,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
         a = decode_args(mllm, "pool", who, S, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, flags)
         # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
         drules = rules.to(dev).records(R, dev) if return_info or not rules.empty else None
-        lp = LogprobRecord(ws, out) if return_logprobs else None
+        lp = LogprobRecord(ws, out, n_top) if return_logprobs else None
         cs = None
         if constraint is not None:  # one upload and one build per call; a slot's state word is reset by the rule itself (step 0)
             cs = ConstraintRecord(ws, constraint, starts, S, dev)

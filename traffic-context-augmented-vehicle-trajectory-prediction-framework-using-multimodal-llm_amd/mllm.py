@@ -241,8 +241,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
                        no_repeat_ngram_size=3, eos_token_id=None, pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16",
                        kv_cache="fp16", stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False,
                        poll_every=None, num_return_sequences=1, share_prefix=False, prompt_lookup_num_tokens=None,
-                       max_matching_ngram_size=2, constraint=None, constraint_start=None, return_logprobs=False, num_beams=1,
-                       length_penalty=1.0, early_stopping=False):
+                       max_matching_ngram_size=2, constraint=None, constraint_start=None, top_logprobs=None, return_logprobs=False,
+                       num_beams=1, length_penalty=1.0, early_stopping=False):
         """Autoregressive text generation (train.py:577-654; scripts/check_generation.py:152-222) on the HIP path.
 
         Same leading arguments as the reference; the prompt arrives as ``input_ids`` / ``attention_mask`` (right padded,
@@ -298,6 +298,17 @@ class LlamaMultiModal(nn.Module, _Prepared):
         order, n_scored their number.  Two small launches (tcavt_logprob_begin / _finish) bracket every token selection, in the
         captured step too; the tokens, the sampler entry chosen and every other launch are those of the call without the flag.
         generation.rank_continuations orders the n continuations of a prompt by it.
+        ``top_logprobs`` = k, an int with 1 <= k <= 20 (OpenAI's name; vLLM logprobs=k; DESIGN.md section 7, "top-k alternatives");
+        it needs return_logprobs=True, and a bool, another type or a k outside the range raises ValueError.  info gains
+        "top_token_ids" int64 and "top_token_logprobs" float32 [B * n, max_new_tokens, k]: at every position a row generated, the
+        k most likely tokens of the raw logits row by (score descending, id ascending) with their log_softmax(raw) values, from
+        the sums token_logprobs uses -- where the emitted token is in the list its entry equals token_logprobs bit for bit.
+        Positions a row never generated hold -1 / -inf.  One call of tcavt_logprob_topk (two launches) follows every
+        logprob_begin, in the captured step too; tokens, token_logprobs, sum_logprob and n_scored are those of the call without.
+        The list is of the model's own distribution: it ignores the sampling arguments, and with ``constraint`` it is of the
+        unmasked row and may name tokens the row's state bans.  Everything return_logprobs works with works here; num_beams > 1
+        and prompt_lookup_num_tokens refuse it as they refuse return_logprobs.  None, the default, is launch for launch and
+        buffer for buffer the call without the argument, return_logprobs=True included.
         ``num_beams`` = n with 2 <= n <= 16 ("beam search"): the deterministic search of HF's
         generate(num_beams=n, do_sample=False), per prompt and independent of the other prompts, on the shared prompt cache
         (share_prefix is implied; passing it makes no difference).  It needs ``do_sample=False`` (beam sampling is not built:
@@ -369,7 +380,8 @@ class LlamaMultiModal(nn.Module, _Prepared):
             top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
             stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
             return_logprobs, num_beams, length_penalty, early_stopping, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, constraint=constraint, constraint_start=constraint_start)
+            max_matching_ngram_size=max_matching_ngram_size, constraint=constraint, constraint_start=constraint_start,
+            top_logprobs=top_logprobs)
         res = self._generated_texts(out)
         return (res, info) if return_info or return_logprobs else res
 
@@ -383,7 +395,7 @@ class LlamaMultiModal(nn.Module, _Prepared):
                       temperature=0.9, top_k=40, top_p=0.9, repetition_penalty=1.2, no_repeat_ngram_size=3, eos_token_id=None,
                       pad_token_id=0, seed=0, use_graph=True, decode_weights="fp16", kv_cache="fp16", admit_group=1,
                       stop_token_ids=None, stop_sequences=None, min_new_tokens=0, return_info=False, return_logprobs=False,
-                      constraint=None, constraint_start=None):
+                      constraint=None, constraint_start=None, top_logprobs=None):
         """Text generation over a LIST of R requests on a fixed pool of ``slots`` decode slots ("slot
         pool"): request r is served exactly once, first in first out, and the moment a request ends (EOS, or its budget) the
         next one of the queue is prefilled into its slot -- no decode row computes pad tokens for longer than one poll interval.
@@ -418,6 +430,11 @@ class LlamaMultiModal(nn.Module, _Prepared):
         "token_logprobs" float32 [R, max budget], "sum_logprob" float32 [R] and "n_scored" int32 [R], as in generate_batch: the
         log-softmax of the raw logits row at every token request r emitted, 0.0 after its end.  The bracket sits around all three
         sampler uses, and a request's three results do not depend on its slot, the schedule or its partners (for a fixed G).
+        ``top_logprobs`` = k (1 <= k <= 20, needs return_logprobs=True; anything else raises ValueError): as in generate_batch,
+        the stats gain "top_token_ids" int64 and "top_token_logprobs" float32 [R, max budget, k] -- the k most likely tokens of the
+        raw row at every position request r generated, -1 / -inf elsewhere -- written by tcavt_logprob_topk after every
+        logprob_begin of the three sampler uses; with ``constraint`` the list is of the unmasked row and may name banned tokens.
+        A request's lists do not depend on its slot, the schedule or its partners (for a fixed G).
         Per-request parameters ("per-request parameters"): each of ``do_sample``, ``temperature``, ``top_k``,
         ``top_p``, ``repetition_penalty``, ``no_repeat_ngram_size``, ``eos_token_id`` (entries may be None), ``seed`` and
         ``min_new_tokens`` is one value, or a list / tuple / 1-D tensor of exactly R values -- a greedy request next to sampled ones,
@@ -442,6 +459,6 @@ class LlamaMultiModal(nn.Module, _Prepared):
             self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
             repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
             admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs, constraint=constraint,
-            constraint_start=constraint_start)
+            constraint_start=constraint_start, top_logprobs=top_logprobs)
         res = self._generated_texts(out)
         return (res, stats) if return_info or return_logprobs else res

@@ -1325,6 +1325,48 @@ def logprob_finish(args):
     check(lib().tcavt_logprob_finish(ctypes.byref(args), stream_ptr()), "tcavt_logprob_finish")
 
 
+TOP_LOGPROBS_MAX = 20  # k of tcavt_logprob_topk
+
+
+def logprob_topk_workspace_bytes(rows, k):
+    """Bytes of the workspace of logprob_topk for ``rows`` logits rows and lists of ``k`` entries."""
+    return int(capi.lib().tcavt_logprob_topk_workspace_bytes(int(rows), int(k)))
+
+
+def logprob_topk_args(lp_args, out_tokens, top_ids, top_logprobs, workspace):
+    """The tcavt_logprob_topk_args of one launch inside the bracket ``lp_args`` (a capi.LogprobArgs from logprob_args, made with
+    the same ``out_tokens``), each tensor checked first.  top_ids int32 and top_logprobs fp32 [*out_tokens.shape, k], k = their
+    last dimension; workspace uint8 of logprob_topk_workspace_bytes(rows, k), its own."""
+    who = "logprob_topk"
+    if not isinstance(lp_args, capi.LogprobArgs):
+        raise capi.TcavtError(f"{who}: lp_args must be the capi.LogprobArgs of the bracket")
+    if top_ids is None or top_logprobs is None or workspace is None:
+        raise capi.TcavtError(f"{who}: top_ids, top_logprobs and workspace are required")
+    if out_tokens.dim() != 2 or out_tokens.data_ptr() != lp_args.out_tokens or out_tokens.shape[1] != lp_args.out_cap:
+        raise capi.TcavtError(f"{who}: out_tokens is not the one of the bracket")
+    if top_ids.dim() != 3 or tuple(top_ids.shape[:2]) != tuple(out_tokens.shape) or top_logprobs.shape != top_ids.shape:
+        raise capi.TcavtError(f"{who}: top_ids and top_logprobs must be [*out_tokens.shape, k], got {tuple(top_ids.shape)} and "
+                              f"{tuple(top_logprobs.shape)} for out_tokens {tuple(out_tokens.shape)}")
+    k = int(top_ids.shape[2])
+    if not 1 <= k <= TOP_LOGPROBS_MAX or k > lp_args.V:
+        raise capi.TcavtError(f"{who}: k = {k} must be in [1, {TOP_LOGPROBS_MAX}] and <= V = {lp_args.V}")
+    for t, dt, n, nm in ((top_ids, torch.int32, out_tokens.numel() * k, "top_ids"),
+                         (top_logprobs, torch.float32, out_tokens.numel() * k, "top_logprobs"),
+                         (workspace, torch.uint8, logprob_topk_workspace_bytes(lp_args.rows, k), "workspace")):
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, n, f"{who}.{nm}")
+    a = capi.LogprobTopkArgs()
+    a.lp = ctypes.pointer(lp_args)  # (the struct keeps the bracket's alive)
+    a.top_ids, a.top_logprobs = top_ids.data_ptr(), top_logprobs.data_ptr()
+    a.workspace, a.workspace_bytes, a.k = workspace.data_ptr(), workspace.numel(), k
+    return a
+
+
+def logprob_topk(args):
+    """Between logprob_begin and the first writer of the logits: the raw row's k most likely tokens (tcavt_logprob_topk)."""
+    check(lib().tcavt_logprob_topk(ctypes.byref(args), stream_ptr()), "tcavt_logprob_topk")
+
+
 class ConstraintTable:
     """The device side of a constraint.TokenConstraint (tcavt_constraint_table): token_class int32 [V] and trans int32 [n_states,
     n_classes] uploaded, bitmap int32 [n_states, ceil(V / 32)] (the uint32 words) and count int32 [n_states] made by ``build()``
