@@ -196,6 +196,18 @@ def test_the_flag_is_reported_as_a_runtime_error():
         assert m.mllm._constraint_flag is None
 
 
+def test_a_beam_call_drops_the_flags_of_the_call_before():
+    with GS.stubbed():
+        cfg, m = GS.tiny_model()
+        vis, ids, mask = GS._requests(cfg, 3)
+        A = TokenConstraint.from_sequences(cfg.llama.vocab, [[11, 12], [30]], 5)
+        m.mllm.generate_batch(vis, input_ids=ids, attention_mask=mask, use_graph=False, max_new_tokens=3, no_repeat_ngram_size=0, constraint=A,
+                              temperature=[0.9, 0.8, 0.7])
+        assert m.mllm._constraint_flag is not None and m.mllm._request_flag is not None
+        m.mllm.generate_batch(vis, input_ids=ids, attention_mask=mask, use_graph=False, max_new_tokens=3, num_beams=2, do_sample=False)
+        assert m.mllm._constraint_flag is None and m.mllm._request_flag is None
+
+
 # ---- the condition of the GPU sampler test
 def test_the_reference_alone_decides_the_sampler_tests_cases():
     scores, hist, hl = CR.sampler_inputs()

@@ -2,6 +2,7 @@
 tcavt_slot_admit_args against the header compiled with the host C compiler, the refusals that need no device, the slot scheduler
 on a scripted `finished` feed, generate_pool's argument errors, and its host call sequence against a stub library."""
 import ctypes
+import itertools
 import os
 import subprocess
 
@@ -309,3 +310,33 @@ def test_generate_pool_call_sequence_against_a_stub_library(monkeypatch):
         assert calls.count("tcavt_llama_decode_step") == steps
         assert calls.count("tcavt_sample_logits_slots") == steps + R
         assert calls.count("tcavt_sample_logits") == 0
+
+
+# every combination the entry accepts (top_logprobs needs return_logprobs=True: the others are refused, test_top_logprobs_trace_cpu)
+@pytest.mark.parametrize("return_info, return_logprobs, top_logprobs, constrained",
+                         [c for c in itertools.product([False, True], [False, True], [None, 4], [False, True]) if c[1] or c[2] is None])
+def test_the_stats_of_an_empty_request_list_are_those_of_a_served_one_with_no_rows(return_info, return_logprobs, top_logprobs, constrained):
+    """generate_pool on no request against generation_stub.POOL_1's five: the same keys, and every per-request tensor with the same
+    dtype and trailing shape and a leading dimension of 0 -- with nothing called and no workspace buffer requested."""
+    import generation_stub as GS
+    from tcavt_amd.constraint import TokenConstraint
+
+    with GS.stubbed() as stub:
+        cfg, m = GS.tiny_model()
+        kw = dict(GS.POOL_1, use_graph=False, pad_token_id=7, return_info=return_info, return_logprobs=return_logprobs, top_logprobs=top_logprobs)
+        if constrained:
+            kw.update(constraint=TokenConstraint.from_sequences(cfg.llama.vocab, [[11, 12], [30]], 5), no_repeat_ngram_size=0)
+        vis, ids, mask = GS._requests(cfg, 5)
+        m.mllm.generate_pool(vis, ids, mask, **kw)
+        served = m.mllm.pool_stats
+        _, m0 = GS.tiny_model()
+        n_calls = len(stub.calls)
+        m0.mllm.generate_pool(vis[:0], ids[:0], mask[:0], **dict(kw, max_new_tokens=max(GS.POOL_1["max_new_tokens"])))
+        empty = m0.mllm.pool_stats
+        assert len(stub.calls) == n_calls and not m0.mllm._ws._bufs
+    assert list(empty) == list(served)
+    for key, t in served.items():
+        if isinstance(t, torch.Tensor):
+            assert t.shape[0] == 5 and empty[key].dtype == t.dtype and tuple(empty[key].shape) == (0,) + tuple(t.shape[1:]), key
+        else:
+            assert empty[key] == (0 if key == "steps" else []), key

@@ -3,12 +3,17 @@ contract -- arguments, defaults, semantics -- is documented on those two methods
 one piece per job:
 
   Prefill          image tokens + prompt through the decoder into a KV cache, last rows through the lm_head -> first logits
-  select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens)
-  LogprobRecord    return_logprobs: the three score tensors and the tcavt_logprob_begin / _finish bracket that select puts around
-                   the sampler entry; rank_continuations orders a prompt's n continuations by them (host only);
+  select           the one place that chooses a sampler entry (tcavt_sample_logits[_slots|_rows] / tcavt_sample_tokens[_per_request])
+  Selection        what one call puts around every select: built once per call from the request table, the ending rules and the
+                   two records below, called at every token selection ([logprob_begin -> [logprob_topk]] -> [constraint_mask] ->
+                   select -> [constraint_advance] -> [logprob_finish]), and the source of the records' host-side results
+  LogprobRecord    return_logprobs: the three score tensors and the arguments of the tcavt_logprob_begin / _finish bracket;
+                   rank_continuations orders a prompt's n continuations by them (host only);
                    top_logprobs = k (check_top_logprobs): the two list tensors and tcavt_logprob_topk right after begin
-  ConstraintRecord, check_constraint   constraint=: the device table, the per-row states and the tcavt_constraint_mask / _advance
-                   bracket that select puts around the sampler entry, inside the log-probability bracket; the argument checks
+  ConstraintRecord, check_constraint   constraint=: the device table, the per-row states and the arguments of the
+                   tcavt_constraint_mask / _advance bracket, inside the log-probability bracket; the argument checks
+  prompt_tokens, begin, shared_prefix_state   what generate_batch and beam_search share: the prompt and its checks, the move to
+                   the device (begin: every entry; it drops the last call's error flags), the rows on a shared prompt cache
   capture          "it has run eagerly once; capture it as a hipGraph" -> the callable that replays it
   FinishedPoll     the finished flags to pinned host memory and an event wait
   decode_loop      the N - 1 steps behind the first selection: one eager, the rest replayed, polled or not
@@ -161,7 +166,10 @@ def request_params(who, n_req, repeat, rules, pad_token_id, **nine):
 
 
 def sample_workspace(ws, name, rows, dev):
-    """Workspace of the two-stage token selection (rows x 16 workgroups + one per sample) for ``rows`` logits rows."""
+    """Workspace of the two-stage token selection (rows x 16 workgroups + one per sample) for ``rows`` logits rows, or None:
+    the samplers then take their one-workgroup form."""
+    if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") == "1":  # (A/B switch)
+        return None
     return ws.get(name, (int(capi.lib().tcavt_sample_workspace_bytes(rows)),), torch.uint8, dev, zero=True)
 
 
@@ -341,11 +349,11 @@ class ConstraintRecord:
     """The device side of a call's ``constraint``: the table (uploaded and built here, once per call: tcavt_constraint_build), the
     start state of every request, the state word of every sample / slot, the final state per request, the flag word, and the
     workspaces of the tcavt_constraint_mask / _advance bracket, one per logits shape, under ``{tag}.cs.ws`` -- new names,
-    requested only with a constraint."""
+    requested only with a constraint.  Without a state row (an empty request list) there is no table: nothing is launched."""
 
     def __init__(self, ws, constraint, starts, n_state, dev):
         self.ws, self.dev = ws, dev
-        self.table = ops.ConstraintTable(constraint.token_class, constraint.trans, dev).build()
+        self.table = ops.ConstraintTable(constraint.token_class, constraint.trans, dev).build() if n_state else None
         self.start = starts.to(dev)
         self.state = torch.zeros(n_state, dtype=I32, device=dev)
         self.request_state = self.start.clone()
@@ -364,37 +372,15 @@ class ConstraintRecord:
         return dict(constraint_state=self.request_state.cpu())
 
 
-def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, lp=None, lp_tag=None, table=None, cs=None):
+def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None, table=None):
     """Logits processors + token selection on the state ``st``.  The form follows from the arguments: ``slot_of_row`` -> the rows
     of a grouped admission, a state with max_new / out_row -> decode slots, neither -> a batch.  Without ending rules or records
-    (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``lp`` (a LogprobRecord; its workspace
-    under ``lp_tag``): the selection is bracketed by tcavt_logprob_begin / _finish, which read the raw row before the processors
-    touch it and the chosen token afterwards; the selection itself is the one without; a record with ``top_k`` adds
-    tcavt_logprob_topk right after begin.  ``table`` (an uploaded ops.RequestTable):
-    tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take.  ``cs`` (a ConstraintRecord; its
-    workspace under ``lp_tag`` too): tcavt_constraint_mask before and tcavt_constraint_advance after the selection, inside the
-    log-probability bracket -- the scores stay those of the raw row."""
-    if lp is not None:
-        largs = lp.args(lp_tag, logits, st, slot_of_row)
-        ops.logprob_begin(largs)
-        if lp.top_k is not None:  # the raw row's k best, before the mask or the selection rewrites a score
-            ops.logprob_topk(lp.topk_args(lp_tag, largs))
-        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table, cs=cs, lp_tag=lp_tag)
-        ops.logprob_finish(largs)
-        return
-    if cs is not None:
-        cargs = cs.args(lp_tag, logits, st, slot_of_row)
-        ops.constraint_mask(cargs)
-        select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row, table=table)
-        ops.constraint_advance(cargs)
-        return
-    if table is not None:
+    (``drules`` None) the launch is the form's own entry, otherwise tcavt_sample_tokens.  ``table`` (an uploaded
+    ops.RequestTable): tcavt_sample_tokens_per_request in the place of whichever entry the call would otherwise take."""
+    if table is not None or drules is not None:
         ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
                           workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules,
                           per_request=table)
-    elif drules is not None:
-        ops.sample_tokens(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
-                          workspace=workspace, max_new=st.max_new, out_row=st.out_row, slot_of_row=slot_of_row, stop=drules)
     elif slot_of_row is not None:
         ops.sample_logits_rows(logits, slot_of_row, st.history, st.hist_len, sp, st.step, st.max_new, st.out_row, st.cur, st.pos,
                                st.finished, out, advance_pos=advance_pos, workspace=workspace)
@@ -404,6 +390,61 @@ def select(logits, st, sp, out, advance_pos, workspace, drules, slot_of_row=None
     else:
         ops.sample_logits(logits, st.history, st.hist_len, sp, st.step, st.cur, st.pos, st.finished, out, advance_pos=advance_pos,
                           workspace=workspace)
+
+
+class Selection:
+    """What one call of a generate entry puts around every ``select``, built once per call (the device arrays are then fixed, so
+    a captured step stays valid): the request table uploaded, the ending rules with the per-request records (``drules``: with
+    rules or return_info), the LogprobRecord (return_logprobs; ``n_top``: top_logprobs) and the ConstraintRecord (one upload and
+    one tcavt_constraint_build) over the output rows ``out``, and the two flags that mllm.check_flags reads.  ``st``: the state
+    the call selects on, which gains the constraint's state words (a slot's is reset by the rule itself, at step 0) -- or None
+    for an empty request list: the records alone, and nothing is launched."""
+
+    def __init__(self, mllm, sp, table, rules, return_info, return_logprobs, n_top, constraint, starts, out, st):
+        ws, dev = mllm._ws, out.device
+        self.sp, self.out, self.return_info = sp, out, return_info
+        self.table = self.cs = None
+        if table is not None:
+            self.table = table.to(dev)
+            mllm._request_flag = table.flag
+        self.drules = rules.to(dev).records(out.shape[0], dev) if return_info or not rules.empty else None
+        self.lp = LogprobRecord(ws, out, n_top) if return_logprobs else None  # (the flag alone does not change the sampler entry)
+        if constraint is not None:
+            self.cs = ConstraintRecord(ws, constraint, starts, 0 if st is None else st.finished.shape[0], dev)
+            if st is not None:
+                st.cstate, mllm._constraint_flag = self.cs.state, self.cs.flag
+
+    def __call__(self, logits, st, advance_pos, tag, workspace, slot_of_row=None):
+        """One token selection on ``logits`` and ``st`` (the call's state, or a slot_view of it).  The brackets' workspaces live
+        under ``tag``, one per logits shape, requested at first use.  tcavt_logprob_begin / _finish read the raw row before
+        anything touches it and the chosen token afterwards, tcavt_logprob_topk takes the raw row's k best right after begin;
+        tcavt_constraint_mask / _advance sit inside them -- the scores stay those of the raw row; select is the one without."""
+        lp, cs = self.lp, self.cs
+        if lp is not None:
+            largs = lp.args(tag, logits, st, slot_of_row)
+            ops.logprob_begin(largs)
+            if lp.top_k is not None:
+                ops.logprob_topk(lp.topk_args(tag, largs))
+        if cs is not None:
+            cargs = cs.args(tag, logits, st, slot_of_row)
+            ops.constraint_mask(cargs)
+        select(logits, st, self.sp, self.out, advance_pos, workspace, self.drules, slot_of_row, self.table)
+        if cs is not None:
+            ops.constraint_advance(cargs)
+        if lp is not None:
+            ops.logprob_finish(largs)
+
+    def host(self, finish=True):
+        """The records on the host, as the entries return them: finish_reason / n_generated (``finish``, and where the call has
+        them), the scores of return_logprobs, constraint_state under return_info."""
+        res = {}
+        if finish and self.drules is not None:
+            res.update(finish_reason=self.drules.finish_reason.cpu(), n_generated=self.drules.n_generated.cpu())
+        if self.lp is not None:
+            res.update(self.lp.host())
+        if self.cs is not None and self.return_info:
+            res.update(self.cs.host())
+        return res
 
 
 def capture(fn, dev, use_graph):
@@ -543,11 +584,13 @@ def check_prompt_lookup(who, k, m, kv_cache, share_prefix, num_beams, return_log
     return int(k), int(m)
 
 
-def prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out, drules, pad_token_id, flags):
+def prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, selection, pad_token_id, flags):
     """-> (one_step, drafted, accepted).  one_step: tcavt_ngram_draft (every sequence's draft of up to k ids and the S * (k + 1)
     token / position rows) -> tcavt_llama_decode_step_multi (the logits of all k + 1 positions in one step) -> tcavt_spec_verify
-    (select every position with the plain sampler on the state the plain loop has there, commit while it equals the draft).
+    (select every position with the plain sampler on the state the plain loop has there, commit while it equals the draft; the
+    call's ``selection`` gives the parameters, the output and the ending rules -- the checks have refused what else it could hold).
     The device arrays are fixed for the call, so the captured step stays valid.  Buffers under ``gen.pl.*``."""
+    sp, out, drules = selection.sp, selection.out, selection.drules
     ws, LW, dev = mllm._ws, mllm.llama_wrapper, out.device
     S, T = out.shape[0], k + 1
     R = S * T
@@ -555,7 +598,7 @@ def prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out
     scratch = ws.get("gen.pl.slot", (R + S,), I32, dev, zero=True)
     drafted, accepted = torch.zeros(S, dtype=I32, device=dev), torch.zeros(S, dtype=I32, device=dev)
     logits = ws.get("gen.pl.logits", (R, LW.shape.vocab), torch.float32, dev)
-    sws = sample_workspace(ws, "gen.pl.sample_ws", R, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
+    sws = sample_workspace(ws, "gen.pl.sample_ws", R, dev)
     a = decode_args(mllm, "gen.pl", who, R, Lmax, decode_weights, cache, cur_rows, pos_rows, logits, flags)
     v = ops.spec_verify_args(logits, T, n_draft, cur_rows, scratch, drafted, accepted, st.history, st.hist_len, sp, st.step, st.max_new,
                              st.out_row, st.cur, st.pos, st.finished, out, advance_pos=True, workspace=sws, stop=drules)
@@ -568,15 +611,75 @@ def prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out
     return one_step, drafted, accepted
 
 
+# what the entries share between their own refusals and the first launch (each entry calls them at its own, fixed point)
+def the_nine(kw):
+    """The keywords an entry does not name are the nine per-request arguments, all of them -> in PER_REQUEST_ARGS' order."""
+    assert sorted(kw) == sorted(PER_REQUEST_ARGS), sorted(kw)
+    return {k: kw[k] for k in PER_REQUEST_ARGS}
+
+
+def check_poll_every(who, poll_every):
+    if poll_every is not None and int(poll_every) < 1:
+        raise ValueError(f"{who}: poll_every must be None or >= 1, got {poll_every}")
+
+
+def prompt_tokens(mllm, context_str_list, input_ids, attention_mask, max_new_tokens):
+    """The prompt of generate_batch -> (input_ids, attention_mask, B, Lt, N): the ids as given, or the tokenizer's as the
+    reference makes them; N = max_new_tokens, checked.  Nothing here touches a device."""
+    if input_ids is None:
+        if mllm.tokenizer is None or context_str_list is None:
+            raise NotImplementedError(
+                "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
+        enc = mllm.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
+                             return_tensors="pt")
+        input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
+    B, Lt = input_ids.shape
+    N = int(max_new_tokens)
+    if N < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    return input_ids, attention_mask, B, Lt, N
+
+
+def begin(mllm, dev, input_ids, attention_mask):
+    """Every entry passes here once it has refused what it refuses: the error flags of the last call's request table and
+    constraint are dropped (mllm.check_flags), and the prompt goes to the device -> (input_ids, the mask as int64; None: ones)."""
+    mllm._request_flag = mllm._constraint_flag = None
+    input_ids = input_ids.to(dev).contiguous()
+    mask = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
+    return input_ids, mask.to(dev).to(I64).contiguous()
+
+
+def fanout_state(rows, hist_cap, step_words, dev):
+    """The state of ``rows`` decode rows that a fan-out launch fills: hist_len and pos are left to it."""
+    return slot_state(torch.zeros(rows, hist_cap, dtype=I64, device=dev), torch.empty(rows, dtype=I32, device=dev),
+                      torch.zeros(step_words, dtype=I32, device=dev), torch.zeros(rows, dtype=I64, device=dev),
+                      torch.empty(rows, dtype=I32, device=dev), torch.zeros(rows, dtype=I32, device=dev))
+
+
+def shared_prefix_state(mllm, pf, logits_src, input_ids, n, N, step_words):
+    """n decode rows per prompt on the shared prompt cache (share_prefix=True, beam search) -> (st, logits, cache, prefix).  The
+    prompts' cache stays where the prefill ``pf`` wrote it (``prefix``: what tcavt_llama_decode_step_shared reads in place);
+    the rows own the suffix cache ``gen.sfx.*`` of the N - 1 tokens a row can append (``cache``, its row count last), and one
+    tcavt_state_fanout makes their state -- ``step_words`` step words -- and first logits ``gen.logits`` of ``logits_src``."""
+    LW, ws, dev = mllm.llama_wrapper, mllm._ws, input_ids.device
+    Nq, (B, Lt), kv_len = mllm.qformer.num_query_tokens, input_ids.shape, pf.buf("kvlen")
+    sfx_rows = max(N - 1, 1)
+    cache = cache_buffers(ws, "gen.sfx", LW, "fp16", B * n, sfx_rows, dev) + (sfx_rows,)
+    pk, pv = pf.buf("cache")
+    prefix = capi.KvPrefix(pk.data_ptr(), pv.data_ptr(), kv_len.data_ptr(), n, Nq + Lt)
+    st = fanout_state(B * n, Lt + N, step_words, dev)
+    logits = ws.get("gen.logits", (B * n, LW.shape.vocab), torch.float32, dev)
+    ops.state_fanout(n, input_ids, kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+    return st, logits, cache, prefix
+
+
 # --------------------------------------------------------------------------------------
 # LlamaMultiModal.generate_batch
 # --------------------------------------------------------------------------------------
-def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature,
-                   top_k, top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph,
-                   decode_weights, kv_cache, stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every,
-                   num_return_sequences=1, share_prefix=False, return_logprobs=False, num_beams=1, length_penalty=1.0,
-                   early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, constraint=None, constraint_start=None,
-                   top_logprobs=None):
+def generate_batch(mllm, vision_embs_batch, *, context_str_list, max_new_tokens, input_ids, attention_mask, pad_token_id, use_graph,
+                   decode_weights, kv_cache, stop_token_ids, stop_sequences, return_info, poll_every, num_return_sequences,
+                   share_prefix, return_logprobs, num_beams, length_penalty, early_stopping, prompt_lookup_num_tokens,
+                   max_matching_ngram_size, constraint, constraint_start, top_logprobs, **nine):
     """-> (out int64 [B * num_return_sequences, max_new_tokens] on the device, info or None).  With n = num_return_sequences > 1
     the prompts are prefilled once, at B rows (``gen.src.*``), one tcavt_kv_fanout makes the state of B * n decode rows of it, and
     everything from the first token selection on runs at B * n rows; n = 1 is launch for launch the call without the argument.
@@ -589,10 +692,10 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     k = m = None
     n_top = check_top_logprobs(who, top_logprobs, return_logprobs)  # (before anything touches a device; beams and prompt lookup
     #                                                                   refuse return_logprobs=True below, and with it this)
-    nine = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)
+    nine = the_nine(nine)
     if constraint is not None or constraint_start is not None:  # (before anything touches a device, and before the beam search)
-        check_constraint(who, mllm, constraint, constraint_start, num_beams, prompt_lookup_num_tokens, no_repeat_ngram_size, min_new_tokens)
+        check_constraint(who, mllm, constraint, constraint_start, num_beams, prompt_lookup_num_tokens, nine["no_repeat_ngram_size"],
+                         nine["min_new_tokens"])
     listed = per_request_names(**nine)
     if listed and (num_beams != 1 or prompt_lookup_num_tokens is not None):  # (beam search and tcavt_spec_verify keep the one struct)
         raise ValueError(f"{who}: per-request values ({', '.join(listed)}) are not built for "
@@ -603,34 +706,24 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     if isinstance(num_beams, bool) or not isinstance(num_beams, numbers.Integral) or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate_batch: num_beams must be an int in [1, {ops.BEAMS_MAX}], got {num_beams!r}")
     if num_beams > 1:
-        return beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample,
-                           repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, use_graph, decode_weights, kv_cache,
-                           stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences,
-                           return_logprobs, int(num_beams), length_penalty, early_stopping)
+        return beam_search(mllm, vision_embs_batch, int(num_beams), nine, context_str_list=context_str_list,
+                           max_new_tokens=max_new_tokens, input_ids=input_ids, attention_mask=attention_mask, pad_token_id=pad_token_id,
+                           use_graph=use_graph, decode_weights=decode_weights, kv_cache=kv_cache, stop_token_ids=stop_token_ids,
+                           stop_sequences=stop_sequences, return_info=return_info, poll_every=poll_every,
+                           num_return_sequences=num_return_sequences, return_logprobs=return_logprobs, length_penalty=length_penalty,
+                           early_stopping=early_stopping)
     check_format(who, "kv_cache", kv_cache)  # (before anything touches a device)
     check_bool(who, "return_logprobs", return_logprobs)
-    if not isinstance(share_prefix, bool):
-        raise ValueError(f"generate_batch: share_prefix must be a bool, got {share_prefix!r}")
+    check_bool(who, "share_prefix", share_prefix)
     if share_prefix and kv_cache == "fp8":
         raise ValueError("generate_batch: share_prefix=True reads the 16-bit prompt cache in place; kv_cache='fp8' has no shared form")
-    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
-    if poll_every is not None and int(poll_every) < 1:
-        raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
+    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, nine["min_new_tokens"], nine["eos_token_id"])
+    check_poll_every(who, poll_every)
     n = num_return_sequences
     if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
         raise ValueError(f"generate_batch: num_return_sequences must be an int >= 1, got {num_return_sequences!r}")
     n = int(n)
-    if input_ids is None:
-        if mllm.tokenizer is None or context_str_list is None:
-            raise NotImplementedError(
-                "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
-        enc = mllm.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
-                             return_tensors="pt")
-        input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
-    B, Lt = input_ids.shape
-    N = int(max_new_tokens)
-    if N < 1:
-        raise ValueError("max_new_tokens must be >= 1")
+    input_ids, attention_mask, B, Lt, N = prompt_tokens(mllm, context_str_list, input_ids, attention_mask, max_new_tokens)
     check_format(who, "decode_weights", decode_weights)
     src_B, B = B, B * n  # the prefill's rows; from here on B counts decode rows (n continuations per prompt, prompt-major)
     check_fp8_weights(who, decode_weights, B, "B" if n == 1 else "B * num_return_sequences")
@@ -642,10 +735,8 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
             raise ValueError(f"{who}: prompt_lookup_num_tokens needs pad_token_id inside [0, vocab), got {pad_token_id}")
     sp, table = request_params(who, src_B, n, rules, pad_token_id, **nine)  # (host only; a table: one entry per decode row)
     starts = constraint.starts(who, constraint_start, src_B, n) if constraint is not None else None  # (host only, likewise)
-    mllm._request_flag = mllm._constraint_flag = None
     dev = vision_embs_batch.device
-    input_ids = input_ids.to(dev).contiguous()
-    attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
+    input_ids, mask64 = begin(mllm, dev, input_ids, attention_mask)
     Nq = mllm.qformer.num_query_tokens
     Lmax = Nq + Lt + N + (k or 0)  # (a verify step writes k rows beyond the last position a row can reach)
     # n > 1: the prompts alone, into a cache of the prompt's own 16 + Lt rows (the width of the pool's one-sample prefill)
@@ -653,57 +744,36 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
     pf = Prefill(mllm, "gen", B, Lt, Lmax, kv_cache, dev) if own_cache else Prefill(mllm, "gen.src", src_B, Lt, Nq + Lt, kv_cache, dev)
     with eval_arithmetic(mllm):
         # ---- prefill: image tokens + prompt through the decoder, keys / values of every layer into the cache
-        logits = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
-        kv_len = pf.buf("kvlen")
+        logits = pf.run(vision_embs_batch, input_ids, mask64)
         # ---- device-resident generation state
-        history = torch.zeros(B, Lt + N, dtype=I64, device=dev)
         prefix = None
         if own_cache:
-            cache = pf.buf("cache") + (Lmax,)
+            cache, kv_len = pf.buf("cache") + (Lmax,), pf.buf("kvlen")
+            history = torch.zeros(B, Lt + N, dtype=I64, device=dev)
             history[:, :Lt] = input_ids
             st = slot_state(history, (kv_len - Nq).to(I32), torch.zeros(1, dtype=I32, device=dev),
                             torch.zeros(B, dtype=I64, device=dev), kv_len.clone(), torch.zeros(B, dtype=I32, device=dev))
+        elif share_prefix:  # the state and the first logits alone: the prompts' cache is read where it is
+            st, logits, cache, prefix = shared_prefix_state(mllm, pf, logits, input_ids, n, N, 1)
         else:
             # one launch: every prompt's cache rows, first logits, history, hist_len, pos and finished to its n decode rows
-            # (share_prefix: the state and the first logits alone; the prompts' cache is read where it is, and the rows' own
-            #  cache holds the N - 1 tokens a row can append)
             LW = mllm.llama_wrapper
-            if share_prefix:
-                sfx_rows = max(N - 1, 1)
-                cache = cache_buffers(mllm._ws, "gen.sfx", LW, "fp16", B, sfx_rows, dev) + (sfx_rows,)
-                pk, pv = pf.buf("cache")
-                prefix = capi.KvPrefix(pk.data_ptr(), pv.data_ptr(), kv_len.data_ptr(), n, Nq + Lt)
-            else:
-                cache = cache_buffers(mllm._ws, "gen", LW, kv_cache, B, Lmax, dev) + (Lmax,)
-            st = slot_state(history, torch.empty(B, dtype=I32, device=dev), torch.zeros(1, dtype=I32, device=dev),
-                            torch.zeros(B, dtype=I64, device=dev), torch.empty(B, dtype=I32, device=dev),
-                            torch.zeros(B, dtype=I32, device=dev))
+            cache = cache_buffers(mllm._ws, "gen", LW, kv_cache, B, Lmax, dev) + (Lmax,)
+            st = fanout_state(B, Lt + N, 1, dev)
             logits_src, logits = logits, mllm._ws.get("gen.logits", (B, LW.shape.vocab), torch.float32, dev)
-            if share_prefix:
-                ops.state_fanout(n, input_ids, kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
-            else:
-                ops.kv_fanout(pf.buf("cache"), cache[:-1], n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids,
-                              kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
+            ops.kv_fanout(pf.buf("cache"), cache[:-1], n, Nq + Lt, Nq + Lt, Lmax, LW.shape.layers, LW.shape.n_kv_heads, input_ids,
+                          pf.buf("kvlen"), Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
         if k is not None:  # the per-slot form of the same state: every row has its own step word and the budget N
             st.step, st.max_new = torch.zeros(B, dtype=I32, device=dev), torch.full((B,), N, dtype=I32, device=dev)
             st.out_row = torch.arange(B, dtype=I64, device=dev)
         out = torch.full((B, N), int(pad_token_id), dtype=I64, device=dev)
-        if table is not None:  # one upload per call: the device arrays are fixed, so the captured step stays valid
-            mllm._request_flag = table.to(dev).flag
-        # two-stage token selection (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form, A/B)
-        sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev) if os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1" else None
-        # ending rules / the per-row records: the device arrays are fixed for the call, so the captured step stays valid
-        drules = rules.to(dev).records(B, dev) if return_info or not rules.empty else None
-        lp = LogprobRecord(mllm._ws, out, n_top) if return_logprobs else None  # (the flag alone does not change the sampler entry)
-        cs = None
-        if constraint is not None:  # one upload and one build per call; the device arrays are fixed, so the captured step stays valid
-            cs = ConstraintRecord(mllm._ws, constraint, starts, B, dev)
-            st.cstate, mllm._constraint_flag = cs.state, cs.flag
-        select(logits, st, sp, out, False, sws, drules, lp=lp, lp_tag="gen", table=table, cs=cs)
+        sws = sample_workspace(mllm._ws, "gen.sample_ws", B, dev)
+        selection = Selection(mllm, sp, table, rules, return_info, return_logprobs, n_top, constraint, starts, out, st)
+        selection(logits, st, False, "gen", sws)
         steps_run = 0
         drafted = accepted = None
         if N > 1 and k is not None:
-            one_step, drafted, accepted = prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, sp, out, drules,
+            one_step, drafted, accepted = prompt_lookup_step(mllm, who, k, m, Lmax, decode_weights, cache, st, selection,
                                                              int(pad_token_id), pf.flags)
             steps_run = decode_loop(one_step, N, B, dev, use_graph, PROMPT_LOOKUP_POLL if poll_every is None else poll_every,
                                     st.finished)
@@ -715,42 +785,40 @@ def generate_batch(mllm, vision_embs_batch, context_str_list, max_new_tokens, in
                     ops.llama_decode_step(a)
                 else:
                     ops.llama_decode_step_shared(a, prefix)
-                select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="gen", table=table, cs=cs)
+                selection(logits, st, True, "gen", sws)
 
             steps_run = decode_loop(one_step, N, B, dev, use_graph, poll_every, st.finished)
         info = None
+        if return_info or return_logprobs:
+            info = dict(selection.host(finish=return_info), steps=steps_run)
         if return_info:
-            reason, n_gen = drules.finish_reason.cpu(), drules.n_generated.cpu()
-            ran_out = reason == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
-            reason[ran_out], n_gen[ran_out] = BUDGET, N
-            info = dict(finish_reason=reason, n_generated=n_gen, steps=steps_run)
+            ran_out = info["finish_reason"] == 0  # (no device budget in this form: a row that never ended ran out at max_new_tokens)
+            info["finish_reason"][ran_out], info["n_generated"][ran_out] = BUDGET, N
             if k is not None:
                 zero = torch.zeros(B, dtype=I32)
                 info.update(drafted=zero if drafted is None else drafted.cpu(), accepted=zero.clone() if accepted is None else accepted.cpu())
-        if lp is not None:
-            info = dict(info or dict(steps=steps_run), **lp.host())
-        if cs is not None and return_info:
-            info.update(cs.host())
     return out, info
 
 
 # --------------------------------------------------------------------------------------
 # LlamaMultiModal.generate_batch(num_beams = n > 1)
 # --------------------------------------------------------------------------------------
-def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, repetition_penalty,
-                no_repeat_ngram_size, eos_token_id, pad_token_id, use_graph, decode_weights, kv_cache, stop_token_ids, stop_sequences,
-                min_new_tokens, return_info, poll_every, num_return_sequences, return_logprobs, n, length_penalty, early_stopping):
+def beam_search(mllm, vision_embs_batch, n, nine, *, context_str_list, max_new_tokens, input_ids, attention_mask, pad_token_id, use_graph,
+                decode_weights, kv_cache, stop_token_ids, stop_sequences, return_info, poll_every, num_return_sequences, return_logprobs,
+                length_penalty, early_stopping):
     """Beam search with n beams per prompt on the shared prompt cache -> (out int64 [B * r, max_new_tokens] on the device, info or
     None), r = num_return_sequences <= n.  The prompts are prefilled at B rows (``gen.src.*``), tcavt_state_fanout makes the state
     and first logits of the R = B * n beam rows, which own the suffix cache ``gen.sfx.*``; the first selection runs on the
     prefill's logits, then one step is tcavt_llama_decode_step_shared -> tcavt_beam_select -> tcavt_beam_reorder.  Scores, beams,
     the finished store and the done flags live on the device (include/tcavt.h states the semantics); the result is copied out
-    of the finished store at the end."""
+    of the finished store at the end.  ``nine``: the call's nine sampling arguments, every one a single value; the search reads
+    do_sample, repetition_penalty, no_repeat_ngram_size, eos_token_id and (to refuse it) min_new_tokens."""
     who = "generate_batch"
+    eos_token_id, min_new_tokens = nine["eos_token_id"], nine["min_new_tokens"]
     # ---- every illegal value is refused before anything touches a device
     check_format(who, "kv_cache", kv_cache)
     check_format(who, "decode_weights", decode_weights)
-    if do_sample:
+    if nine["do_sample"]:
         raise ValueError("generate_batch: num_beams > 1 needs do_sample=False (beam sampling is not built)")
     if kv_cache == "fp8":
         raise ValueError("generate_batch: num_beams > 1 reads the 16-bit prompt cache in place; kv_cache='fp8' has no beam form")
@@ -771,41 +839,22 @@ def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input
     if isinstance(r, bool) or not isinstance(r, numbers.Integral) or not 1 <= r <= n:
         raise ValueError(f"generate_batch: num_return_sequences must be an int in [1, num_beams = {n}], got {num_return_sequences!r}")
     r = int(r)
-    if poll_every is not None and int(poll_every) < 1:
-        raise ValueError(f"generate_batch: poll_every must be None or >= 1, got {poll_every}")
-    if input_ids is None:
-        if mllm.tokenizer is None or context_str_list is None:
-            raise NotImplementedError(
-                "generate_batch needs input_ids / attention_mask: no tokenizer can be fetched offline (train.py:500,590-598)")
-        enc = mllm.tokenizer(["<image> " + c for c in context_str_list], padding=True, truncation=True, max_length=256,
-                             return_tensors="pt")
-        input_ids, attention_mask = enc["input_ids"], enc["attention_mask"]
-    B, Lt = input_ids.shape
-    N = int(max_new_tokens)
-    if N < 1:
-        raise ValueError("max_new_tokens must be >= 1")
+    check_poll_every(who, poll_every)
+    input_ids, attention_mask, B, Lt, N = prompt_tokens(mllm, context_str_list, input_ids, attention_mask, max_new_tokens)
     R, K = B * n, 2 * n
     check_fp8_weights(who, decode_weights, R, "B * num_beams")
     dev = vision_embs_batch.device
-    input_ids = input_ids.to(dev).contiguous()
-    attention_mask = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev)
+    input_ids, mask64 = begin(mllm, dev, input_ids, attention_mask)
     LW, ws = mllm.llama_wrapper, mllm._ws
     Nq = mllm.qformer.num_query_tokens
     Lmax = Nq + Lt + N
     pf = Prefill(mllm, "gen.src", B, Lt, Nq + Lt, "fp16", dev)
     with eval_arithmetic(mllm):
-        logits_src = pf.run(vision_embs_batch, input_ids, attention_mask.to(I64).contiguous())
+        logits_src = pf.run(vision_embs_batch, input_ids, mask64)
+        # ---- device-resident state: the rows' (one step word per prompt), the prompts' and the finished store
+        st, logits, sfx, prefix = shared_prefix_state(mllm, pf, logits_src, input_ids, n, N, B)
         kv_len = pf.buf("kvlen")
-        sfx_rows = max(N - 1, 1)
-        sfx = cache_buffers(ws, "gen.sfx", LW, "fp16", R, sfx_rows, dev)
-        pk, pv = pf.buf("cache")
-        prefix = capi.KvPrefix(pk.data_ptr(), pv.data_ptr(), kv_len.data_ptr(), n, Nq + Lt)
-        # ---- device-resident state: the rows', the prompts' and the finished store
         z32 = lambda *shape: torch.zeros(*shape, dtype=I32, device=dev)  # noqa: E731
-        st = slot_state(torch.zeros(R, Lt + N, dtype=I64, device=dev), torch.empty(R, dtype=I32, device=dev), z32(B),
-                        torch.zeros(R, dtype=I64, device=dev), torch.empty(R, dtype=I32, device=dev), z32(R))
-        logits = ws.get("gen.logits", (R, V), torch.float32, dev)
-        ops.state_fanout(n, input_ids, kv_len, Nq, logits_src, logits, st.history, st.hist_len, st.pos, st.finished)
         run_score = torch.zeros(R, dtype=torch.float32, device=dev)
         live = z32(B, n)
         live[:, 0] = 1
@@ -817,14 +866,14 @@ def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input
         bws = ws.get("gen.beam_ws", (ops.beam_workspace_bytes(R),), torch.uint8, dev)
         sel = ops.beam_args(logits, n, N, st.history, st.hist_len, run_score, live, fin_tokens, fin_score, fin_flag, fin_len, unsat, done,
                             st.cur, st.pos, st.finished, st.step, kv_len, len_pow, parent, plan, bws, eos_token_id, pad_token_id,
-                            repetition_penalty, no_repeat_ngram_size, early_stopping, trace=trace)
+                            nine["repetition_penalty"], nine["no_repeat_ngram_size"], early_stopping, trace=trace)
         reo = ops.beam_reorder_args(n, parent, plan, st.cur, st.history, st.hist_len, st.pos, st.step, sfx[0], sfx[1], LW.shape.layers,
                                     LW.shape.n_kv_heads)
         ops.beam_select(sel)  # the first selection: from the prefill's logits
         ops.beam_reorder(reo)
         steps_run = 0
         if N > 1:
-            a = decode_args(mllm, "gen", who, R, Lmax, decode_weights, sfx + (sfx_rows,), st.cur, st.pos, logits, pf.flags)
+            a = decode_args(mllm, "gen", who, R, Lmax, decode_weights, sfx, st.cur, st.pos, logits, pf.flags)
 
             def one_step():
                 ops.llama_decode_step_shared(a, prefix)
@@ -849,20 +898,20 @@ def beam_search(mllm, vision_embs_batch, context_str_list, max_new_tokens, input
 # --------------------------------------------------------------------------------------
 # LlamaMultiModal.generate_pool
 # --------------------------------------------------------------------------------------
-def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k,
-                  top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights,
-                  kv_cache, admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs=False,
-                  constraint=None, constraint_start=None, top_logprobs=None):
+def generate_pool(mllm, vision_embs, *, input_ids, attention_mask, max_new_tokens, slots, poll_every, pad_token_id, use_graph,
+                  decode_weights, kv_cache, admit_group, stop_token_ids, stop_sequences, return_info, return_logprobs, constraint,
+                  constraint_start, top_logprobs, **nine):
     """-> (out int64 [R, max budget] on the device, mllm.pool_stats)."""
     who = "generate_pool"
+    nine = the_nine(nine)
     n_top = check_top_logprobs(who, top_logprobs, return_logprobs)
     # ---- every illegal value is refused before anything touches a device
     check_format(who, "kv_cache", kv_cache)
     check_format(who, "decode_weights", decode_weights)
     check_bool(who, "return_logprobs", return_logprobs)
     if constraint is not None or constraint_start is not None:
-        check_constraint(who, mllm, constraint, constraint_start, 1, None, no_repeat_ngram_size, min_new_tokens)
-    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, min_new_tokens, eos_token_id)
+        check_constraint(who, mllm, constraint, constraint_start, 1, None, nine["no_repeat_ngram_size"], nine["min_new_tokens"])
+    rules = stop_rules(who, mllm, stop_token_ids, stop_sequences, nine["min_new_tokens"], nine["eos_token_id"])
     S, poll_every = int(slots), int(poll_every)
     if S < 1:
         raise ValueError(f"generate_pool: slots must be >= 1, got {slots}")
@@ -886,27 +935,17 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
     if not 0 <= int(pad_token_id) < ll.vocab:  # (idle and finished slots feed the pad token to the decode step)
         raise ValueError(f"generate_pool: pad_token_id = {pad_token_id} outside [0, vocab = {ll.vocab})")
     check_fp8_weights(who, decode_weights, S, "slots")
-    sp, table = request_params(who, R, 1, rules, pad_token_id, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                               repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                               eos_token_id=eos_token_id, seed=seed, min_new_tokens=min_new_tokens)  # (host only)
+    sp, table = request_params(who, R, 1, rules, pad_token_id, **nine)  # (host only)
     starts = constraint.starts(who, constraint_start, R, 1) if constraint is not None else None  # (host only, likewise)
-    mllm._request_flag = mllm._constraint_flag = None
     dev = vision_embs.device
+    input_ids, mask64 = begin(mllm, dev, input_ids, attention_mask)
     out = torch.full((R, Nmax), int(pad_token_id), dtype=I64, device=dev)
     stats = mllm.pool_stats = dict(steps=0, admitted=[], retired=[], groups=[])
     mllm._pool_flag = None  # (the grouped admission's bad-slot flag: check_flags)
-    if R == 0:
-        if return_info or not rules.empty:
-            stats.update(finish_reason=torch.zeros(0, dtype=I32), n_generated=torch.zeros(0, dtype=I32))
-        if return_logprobs:
-            stats.update(token_logprobs=torch.zeros(0, Nmax), sum_logprob=torch.zeros(0), n_scored=torch.zeros(0, dtype=I32))
-            if n_top is not None:
-                stats.update(top_token_ids=torch.zeros(0, Nmax, n_top, dtype=I64), top_token_logprobs=torch.zeros(0, Nmax, n_top))
-        if constraint is not None and return_info:
-            stats.update(constraint_state=torch.zeros(0, dtype=I32))
+    records = (mllm, sp, table, rules, return_info, return_logprobs, n_top, constraint, starts, out)
+    if R == 0:  # the records of no request: no launch, no workspace buffer
+        stats.update(Selection(*records, st=None).host())
         return out, stats
-    input_ids = input_ids.to(dev).contiguous()
-    mask64 = attention_mask.to(dev).to(I64).contiguous()
     Nq = mllm.qformer.num_query_tokens
     L = Nq + Lt
     Lmax = L + Nmax  # 16 + Lt + max budget
@@ -930,34 +969,23 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
         logits = ws.get("pool.logits", (S, ll.vocab), torch.float32, dev)
         pf.reserve("logits", "kvlen", "final16", "x16", "h")
         poll = FinishedPoll(S, dev)
-        if table is not None:  # one upload per call: the device arrays are fixed, so the captured graphs stay valid
-            mllm._request_flag = table.to(dev).flag
-        # two-stage token selection, as generate_batch (TCAVT_SAMPLE_ONE_STAGE=1: the one-workgroup form)
-        two_stage = os.environ.get("TCAVT_SAMPLE_ONE_STAGE", "0") != "1"
-        sws = sample_workspace(ws, "pool.sample_ws", S, dev) if two_stage else None
-        sws1 = sample_workspace(ws, "pool.pf.sample_ws", 1, dev) if two_stage else None
+        sws, sws1 = sample_workspace(ws, "pool.sample_ws", S, dev), sample_workspace(ws, "pool.pf.sample_ws", 1, dev)
         a = decode_args(mllm, "pool", who, S, Lmax, decode_weights, cache + (Lmax,), st.cur, st.pos, logits, flags)
-        # ending rules / the per-request records: device arrays fixed for the call, so the captured graphs stay valid
-        drules = rules.to(dev).records(R, dev) if return_info or not rules.empty else None
-        lp = LogprobRecord(ws, out, n_top) if return_logprobs else None
-        cs = None
-        if constraint is not None:  # one upload and one build per call; a slot's state word is reset by the rule itself (step 0)
-            cs = ConstraintRecord(ws, constraint, starts, S, dev)
-            st.cstate, mllm._constraint_flag = cs.state, cs.flag
+        selection = Selection(*records, st=st)
         # what both admission launches share: rows, src_lmax, kv_lmax, n_layers, S, nkv ... and the eight state arrays
         geometry = (L, L, Lmax, ll.layers, S, ll.n_kv_heads)
         state = (st.history, st.hist_len, st.step, st.max_new, st.out_row, st.pos, st.finished, st.cur)
 
         def one_step():
             ops.llama_decode_step(a)
-            select(logits, st, sp, out, True, sws, drules, lp=lp, lp_tag="pool", table=table, cs=cs)
+            selection(logits, st, True, "pool", sws)
 
         def admit(s, r):
             # the request on its own: the ordinary decoder pass at B = 1 into the one-sample cache, the copy into slot s,
             # and the first token from the one-row logits with the slot's state (views that start at slot s)
             logits1 = pf.run(vision_embs[r:r + 1], input_ids[r:r + 1], mask64[r:r + 1], after_stack=lambda: ops.slot_admit(
                 pf.buf("cache"), cache, s, *geometry, input_ids[r], pf.buf("kvlen"), Nq, budgets[r], r, *state))
-            select(logits1, slot_view(st, s), sp, out, False, sws1, drules, lp=lp, lp_tag="pool.pf", table=table, cs=cs)
+            selection(logits1, slot_view(st, s), False, "pool.pf", sws1)
 
         if G > 1:
             # ---- grouped admission: ONE decoder pass at exactly B = G rows per group (pool.pg.*); a short group is filled
@@ -970,7 +998,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             pg_budget = ws.get("pool.pg.budget", (G,), I32, dev)
             pg_outrow = ws.get("pool.pg.outrow", (G,), I64, dev)
             pg.reserve("cache", "logits", "kvlen", "final16", "x16", "h")
-            pg_sws = sample_workspace(ws, "pool.pg.sample_ws", G, dev) if two_stage else None
+            pg_sws = sample_workspace(ws, "pool.pg.sample_ws", G, dev)
             bad_slot = mllm._pool_flag = ws.get("pool.pg.bad_slot", (1,), I32, dev, zero=True)
             vis_all = vision_embs.contiguous()
             budgets_dev = torch.tensor(budgets, dtype=I32, device=dev)
@@ -989,7 +1017,7 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             def group_pass():
                 logits_g = pg.run(pg_vis, pg_ids, pg_mask, after_stack=lambda: ops.slot_admit_group(
                     pg.buf("cache"), cache, pg_slot, *geometry, pg_ids, pg.buf("kvlen"), Nq, pg_budget, pg_outrow, bad_slot, *state))
-                select(logits_g, st, sp, out, False, pg_sws, drules, slot_of_row=pg_slot, lp=lp, lp_tag="pool.pg", table=table, cs=cs)
+                selection(logits_g, st, False, "pool.pg", pg_sws, slot_of_row=pg_slot)
 
         sched = SlotScheduler(R, S, G)
         step = later_pass = None
@@ -1021,10 +1049,5 @@ def generate_pool(mllm, vision_embs, input_ids, attention_mask, max_new_tokens, 
             n_ret = len(sched.retired)
             sched.retire(poll.read(st.finished).tolist())
             stats["retired"] += [(r, s, stats["steps"]) for r, s in sched.retired[n_ret:]]
-        if drules is not None:
-            stats.update(finish_reason=drules.finish_reason.cpu(), n_generated=drules.n_generated.cpu())
-        if lp is not None:
-            stats.update(lp.host())
-        if cs is not None and return_info:
-            stats.update(cs.host())
+        stats.update(selection.host())
     return out, stats

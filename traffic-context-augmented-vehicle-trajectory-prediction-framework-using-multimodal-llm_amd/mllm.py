@@ -376,12 +376,15 @@ class LlamaMultiModal(nn.Module, _Prepared):
         Returns int64 [B * n, max_new_tokens] token ids (pad_token_id after a row's end), or a list of B * n strings in the same
         order with a tokenizer."""
         out, info = generation.generate_batch(
-            self, vision_embs_batch, context_str_list, max_new_tokens, input_ids, attention_mask, do_sample, temperature, top_k,
-            top_p, repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            stop_token_ids, stop_sequences, min_new_tokens, return_info, poll_every, num_return_sequences, share_prefix,
-            return_logprobs, num_beams, length_penalty, early_stopping, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-            max_matching_ngram_size=max_matching_ngram_size, constraint=constraint, constraint_start=constraint_start,
-            top_logprobs=top_logprobs)
+            self, vision_embs_batch, context_str_list=context_str_list, max_new_tokens=max_new_tokens, input_ids=input_ids,
+            attention_mask=attention_mask, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id,
+            pad_token_id=pad_token_id, seed=seed, use_graph=use_graph, decode_weights=decode_weights, kv_cache=kv_cache,
+            stop_token_ids=stop_token_ids, stop_sequences=stop_sequences, min_new_tokens=min_new_tokens, return_info=return_info,
+            poll_every=poll_every, num_return_sequences=num_return_sequences, share_prefix=share_prefix,
+            return_logprobs=return_logprobs, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
+            prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+            constraint=constraint, constraint_start=constraint_start, top_logprobs=top_logprobs)
         res = self._generated_texts(out)
         return (res, info) if return_info or return_logprobs else res
 
@@ -456,9 +459,12 @@ class LlamaMultiModal(nn.Module, _Prepared):
         ValueError before anything touches a device: no_repeat_ngram_size > 0 (the default is 3: pass 0) or min_new_tokens > 0, as
         one value or in any list element; a constraint over another vocabulary; a start state outside the automaton."""
         out, stats = generation.generate_pool(
-            self, vision_embs, input_ids, attention_mask, max_new_tokens, slots, poll_every, do_sample, temperature, top_k, top_p,
-            repetition_penalty, no_repeat_ngram_size, eos_token_id, pad_token_id, seed, use_graph, decode_weights, kv_cache,
-            admit_group, stop_token_ids, stop_sequences, min_new_tokens, return_info, return_logprobs, constraint=constraint,
-            constraint_start=constraint_start, top_logprobs=top_logprobs)
+            self, vision_embs, input_ids=input_ids, attention_mask=attention_mask, max_new_tokens=max_new_tokens, slots=slots,
+            poll_every=poll_every, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, eos_token_id=eos_token_id,
+            pad_token_id=pad_token_id, seed=seed, use_graph=use_graph, decode_weights=decode_weights, kv_cache=kv_cache,
+            admit_group=admit_group, stop_token_ids=stop_token_ids, stop_sequences=stop_sequences, min_new_tokens=min_new_tokens,
+            return_info=return_info, return_logprobs=return_logprobs, constraint=constraint, constraint_start=constraint_start,
+            top_logprobs=top_logprobs)
         res = self._generated_texts(out)
         return (res, stats) if return_info or return_logprobs else res

@@ -1071,6 +1071,15 @@ def sample_workspace(B, device):
     return torch.zeros(int(lib().tcavt_sample_workspace_bytes(int(B))), dtype=torch.uint8, device=device)
 
 
+def _require(who, *tensors):
+    """Every (tensor, dtype, entries, name) in turn: present, of that dtype, contiguous, of at least that many entries."""
+    for t, dt, k, nm in tensors:
+        if t is None:
+            raise capi.TcavtError(f"{who}: {nm} is missing")
+        _req(t, dt, f"{who}.{nm}")
+        _need(t, k, f"{who}.{nm}")
+
+
 def _sampler_guard(who, logits, workspace, n, step_n, out_n, history, hist_len, step, cur_tok, pos, finished, out_tokens, slots=None):
     """Host guard shared by the sampler wrappers: dtype, contiguity and minimal size of the logits, the workspace and the state
     -- ``n`` entries per state array, ``step_n`` step words, ``out_n`` output ids; slots = (max_new, out_row) in the per-slot forms."""
@@ -1078,13 +1087,45 @@ def _sampler_guard(who, logits, workspace, n, step_n, out_n, history, hist_len, 
         _req(workspace, torch.uint8, f"{who}.workspace")
     _req(logits, torch.float32, f"{who}.logits")
     per_slot = () if slots is None else ((slots[0], torch.int32, n, "max_new"), (slots[1], torch.int64, n, "out_row"))
-    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), (step, torch.int32, step_n, "step"),
-                         *per_slot, (cur_tok, torch.int64, n, "cur_tok"), (pos, torch.int32, n, "pos"),
-                         (finished, torch.int32, n, "finished"), (out_tokens, torch.int64, out_n, "out_tokens")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, k, f"{who}.{nm}")
+    _require(who, (history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), (step, torch.int32, step_n, "step"),
+             *per_slot, (cur_tok, torch.int64, n, "cur_tok"), (pos, torch.int32, n, "pos"), (finished, torch.int32, n, "finished"),
+             (out_tokens, torch.int64, out_n, "out_tokens"))
+
+
+def _form(rows, state_rows, slot_of_row, *per_slot):
+    """The form of a token selection on ``rows`` logits rows follows from its arguments, as in the C entries: slot_of_row -> the
+    rows of a grouped admission on a state of ``state_rows`` slots; one of the ``per_slot`` arrays (out_row, max_new) -> decode
+    slots; neither -> a batch.  -> (slots: a per-slot form, n: the state's rows, the number of step words)."""
+    slots = slot_of_row is not None or any(t is not None for t in per_slot)
+    n = state_rows if slot_of_row is not None else rows
+    return slots, n, n if slots else 1
+
+
+def _bracket_form(who, rows, state_rows, step, out_row, slot_of_row):
+    """_form for a bracket around a token selection (logprob, constraint), which knows the per-slot forms by out_row alone:
+    -> (slots, n, the _require entries of the three arrays the form is read from)."""
+    if slot_of_row is not None and out_row is None:
+        raise capi.TcavtError(f"{who}: out_row is missing (slot_of_row is given)")
+    slots, n, step_n = _form(rows, state_rows, slot_of_row, out_row)
+    per_slot = ((out_row, torch.int64, n, "out_row"),) if slots else ()
+    per_row = ((slot_of_row, torch.int32, rows, "slot_of_row"),) if slot_of_row is not None else ()
+    return slots, n, ((step, torch.int32, step_n, "step"), *per_slot, *per_row)
+
+
+def _sample_args(logits, rows, n_state, history, hist_len, params, step, max_new, out_row, cur_tok, pos, finished, out_tokens,
+                 advance_pos, workspace, stop, slot_of_row=None):
+    """The tcavt_sample_args of a selection on the first ``rows`` logits rows and a state of ``n_state`` rows (the tensors are
+    checked by the caller).  stop: a stopping.DeviceStopRules, a capi.StopRules struct or None."""
+    a = capi.SampleArgs()
+    a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
+    a.params, a.step, a.max_new, a.out_row = ctypes.pointer(params), step.data_ptr(), ptr(max_new), ptr(out_row)
+    a.cur_tok, a.pos, a.finished, a.out_tokens = cur_tok.data_ptr(), pos.data_ptr(), finished.data_ptr(), out_tokens.data_ptr()
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() if workspace is not None else 0
+    if stop is not None:
+        a.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
+    a.rows, a.V, a.n_state, a.hist_cap, a.out_cap = rows, logits.shape[1], n_state, history.shape[1], out_tokens.shape[1]
+    a.advance_pos = int(advance_pos)
+    return a
 
 
 def sample_logits(logits, history, hist_len, params, step, cur_tok, pos, finished, out_tokens, advance_pos, workspace=None):
@@ -1237,26 +1278,19 @@ def sample_tokens(logits, history, hist_len, params, step, cur_tok, pos, finishe
     the launches are those of the corresponding existing entry.  per_request: a RequestTable (or a capi.RequestParams struct) ->
     tcavt_sample_tokens_per_request: every row takes its parameters from the table at its request index (the row in the batch
     form, out_row[slot] otherwise); ``params`` still carries the call's pad_token_id."""
-    rows, V = logits.shape
+    rows, _ = logits.shape
     if history.dim() != 2 or out_tokens.dim() != 2:
         raise capi.TcavtError("sample_tokens: history needs one row per sample / slot, out_tokens one row per sample / request")
-    slots = slot_of_row is not None or max_new is not None or out_row is not None
-    n = history.shape[0] if slot_of_row is not None else rows
+    slots, n, step_n = _form(rows, history.shape[0], slot_of_row, max_new, out_row)
     if history.shape[0] != n or (not slots and out_tokens.shape[0] != rows):
         raise capi.TcavtError("sample_tokens: history / out_tokens need one row per sample")
     if slot_of_row is not None:
         _req(slot_of_row, torch.int32, "sample_tokens.slot_of_row")
         _need(slot_of_row, rows, "sample_tokens.slot_of_row")
-    _sampler_guard("sample_tokens", logits, workspace, n, n if slots else 1, 1, history, hist_len, step, cur_tok, pos, finished,
-                   out_tokens, slots=(max_new, out_row) if slots else None)
-    a = capi.SampleArgs()
-    a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
-    a.params, a.step, a.max_new, a.out_row = ctypes.pointer(params), step.data_ptr(), ptr(max_new), ptr(out_row)
-    a.cur_tok, a.pos, a.finished, a.out_tokens = cur_tok.data_ptr(), pos.data_ptr(), finished.data_ptr(), out_tokens.data_ptr()
-    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() if workspace is not None else 0
-    if stop is not None:
-        a.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
-    a.rows, a.V, a.n_state, a.hist_cap, a.out_cap, a.advance_pos = rows, V, n, history.shape[1], out_tokens.shape[1], int(advance_pos)
+    _sampler_guard("sample_tokens", logits, workspace, n, step_n, 1, history, hist_len, step, cur_tok, pos, finished, out_tokens,
+                   slots=(max_new, out_row) if slots else None)
+    a = _sample_args(logits, rows, n, history, hist_len, params, step, max_new, out_row, cur_tok, pos, finished, out_tokens,
+                     advance_pos, workspace, stop, slot_of_row)
     if per_request is not None:
         if not isinstance(per_request, capi.RequestParams):
             _req(per_request.table, torch.uint8, "sample_tokens.per_request.table")
@@ -1285,27 +1319,18 @@ def logprob_args(logits, history, hist_len, step, finished, out_tokens, token_lo
     rows, V = logits.shape
     if history.dim() != 2 or out_tokens.dim() != 2:
         raise capi.TcavtError("logprob: history needs one row per sample / slot, out_tokens one row per sample / request")
-    if slot_of_row is not None and out_row is None:
-        raise capi.TcavtError("logprob: out_row is missing (slot_of_row is given)")
-    slots = out_row is not None
-    n = history.shape[0] if slot_of_row is not None else rows
+    slots, n, form = _bracket_form(who, rows, history.shape[0], step, out_row, slot_of_row)
     if history.shape[0] != n or (not slots and out_tokens.shape[0] != rows):
         raise capi.TcavtError("logprob: history / out_tokens need one row per sample")
     if token_logprobs.shape != out_tokens.shape:
         raise capi.TcavtError("logprob: token_logprobs must have the shape of out_tokens")
     _req(logits, torch.float32, f"{who}.logits")
-    per_slot = ((out_row, torch.int64, n, "out_row"),) if slots else ()
-    per_row = ((slot_of_row, torch.int32, rows, "slot_of_row"),) if slot_of_row is not None else ()
     n_out = out_tokens.shape[0]
-    for t, dt, k, nm in ((history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"),
-                         (step, torch.int32, n if slots else 1, "step"), *per_slot, *per_row, (finished, torch.int32, n, "finished"),
-                         (out_tokens, torch.int64, 1, "out_tokens"), (token_logprobs, torch.float32, 1, "token_logprobs"),
-                         (sum_logprob, torch.float32, n_out, "sum_logprob"), (n_scored, torch.int32, n_out, "n_scored"),
-                         (workspace, torch.uint8, logprob_workspace_bytes(rows, history.shape[1]), "workspace")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, k, f"{who}.{nm}")
+    _require(who, (history, torch.int64, n, "history"), (hist_len, torch.int32, n, "hist_len"), *form,
+             (finished, torch.int32, n, "finished"), (out_tokens, torch.int64, 1, "out_tokens"),
+             (token_logprobs, torch.float32, 1, "token_logprobs"), (sum_logprob, torch.float32, n_out, "sum_logprob"),
+             (n_scored, torch.int32, n_out, "n_scored"),
+             (workspace, torch.uint8, logprob_workspace_bytes(rows, history.shape[1]), "workspace"))
     a = capi.LogprobArgs()
     a.logits, a.slot_of_row, a.history, a.hist_len = logits.data_ptr(), ptr(slot_of_row), history.data_ptr(), hist_len.data_ptr()
     a.step, a.out_row, a.finished, a.out_tokens = step.data_ptr(), ptr(out_row), finished.data_ptr(), out_tokens.data_ptr()
@@ -1404,24 +1429,14 @@ def constraint_args(table, logits, step, finished, cur_tok, state, start, worksp
     rows, V = logits.shape
     if V != table.V:
         raise capi.TcavtError(f"constraint: the table is over {table.V} token ids, the logits have {V}")
-    if slot_of_row is not None and out_row is None:
-        raise capi.TcavtError("constraint: out_row is missing (slot_of_row is given)")
-    slots = out_row is not None
-    n = state.numel() if slot_of_row is not None else rows
+    slots, n, form = _bracket_form(who, rows, 0 if state is None else state.numel(), step, out_row, slot_of_row)
     n_req = start.numel()
     if not slots and n_req < rows:
         raise capi.TcavtError(f"constraint: start has {n_req} entries for {rows} rows")
     _req(logits, torch.float32, f"{who}.logits")
-    per_slot = ((out_row, torch.int64, n, "out_row"),) if slots else ()
-    per_row = ((slot_of_row, torch.int32, rows, "slot_of_row"),) if slot_of_row is not None else ()
     optional = tuple((t, torch.int32, k, nm) for t, k, nm in ((request_state, n_req, "request_state"), (flag, 1, "flag")) if t is not None)
-    for t, dt, k, nm in ((step, torch.int32, n if slots else 1, "step"), *per_slot, *per_row, (finished, torch.int32, n, "finished"),
-                         (cur_tok, torch.int64, n, "cur_tok"), (state, torch.int32, n, "state"), (start, torch.int32, 1, "start"),
-                         *optional, (workspace, torch.uint8, constraint_workspace_bytes(rows), "workspace")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, k, f"{who}.{nm}")
+    _require(who, *form, (finished, torch.int32, n, "finished"), (cur_tok, torch.int64, n, "cur_tok"), (state, torch.int32, n, "state"),
+             (start, torch.int32, 1, "start"), *optional, (workspace, torch.uint8, constraint_workspace_bytes(rows), "workspace"))
     a = capi.ConstraintArgs()
     a.table = ctypes.pointer(table.struct)
     capi.bind(a, logits=logits, slot_of_row=slot_of_row, step=step, out_row=out_row, finished=finished, cur_tok=cur_tok, state=state,
@@ -1462,18 +1477,14 @@ def beam_args(logits, n, N, history, hist_len, run_score, live, fin_tokens, fin_
     B = R // n
     if history.dim() != 2 or history.shape[0] != R:
         raise capi.TcavtError(f"{who}: history needs one row per decode row")
-    for t, dt, k, nm in ((logits, torch.float32, R * V, "logits"), (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"),
-                         (run_score, torch.float32, R, "run_score"), (live, torch.int32, R, "live"),
-                         (fin_tokens, torch.int64, R * N, "fin_tokens"), (fin_score, torch.float32, R, "fin_score"),
-                         (fin_flag, torch.int32, R, "fin_flag"), (fin_len, torch.int32, R, "fin_len"), (unsat, torch.int32, B, "unsat"),
-                         (done, torch.int32, B, "done"), (cur_tok, torch.int64, R, "cur_tok"), (pos, torch.int32, R, "pos"),
-                         (finished, torch.int32, R, "finished"), (step, torch.int32, B, "step"), (prefix_len, torch.int32, B, "prefix_len"),
-                         (len_pow, torch.float32, N, "len_pow"), (parent, torch.int32, R, "parent"), (plan, torch.int32, 4 * B, "plan"),
-                         (workspace, torch.uint8, beam_workspace_bytes(R), "workspace")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, k, f"{who}.{nm}")
+    _require(who, (logits, torch.float32, R * V, "logits"), (history, torch.int64, R, "history"), (hist_len, torch.int32, R, "hist_len"),
+             (run_score, torch.float32, R, "run_score"), (live, torch.int32, R, "live"),
+             (fin_tokens, torch.int64, R * N, "fin_tokens"), (fin_score, torch.float32, R, "fin_score"),
+             (fin_flag, torch.int32, R, "fin_flag"), (fin_len, torch.int32, R, "fin_len"), (unsat, torch.int32, B, "unsat"),
+             (done, torch.int32, B, "done"), (cur_tok, torch.int64, R, "cur_tok"), (pos, torch.int32, R, "pos"),
+             (finished, torch.int32, R, "finished"), (step, torch.int32, B, "step"), (prefix_len, torch.int32, B, "prefix_len"),
+             (len_pow, torch.float32, N, "len_pow"), (parent, torch.int32, R, "parent"), (plan, torch.int32, 4 * B, "plan"),
+             (workspace, torch.uint8, beam_workspace_bytes(R), "workspace"))
     _req(trace, torch.int32, f"{who}.trace")
     _need(trace, N * B * 2 * n * 3, f"{who}.trace")
     a = capi.BeamArgs()
@@ -1728,13 +1739,9 @@ def ngram_draft(history, hist_len, cur, pos, finished, k, max_matching_ngram_siz
     if history.dim() != 2:
         raise capi.TcavtError(f"{who}: history needs one row per sequence")
     S, T = history.shape[0], int(k) + 1
-    for t, dt, n, nm in ((history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (cur, torch.int64, S, "cur"),
-                         (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (n_draft, torch.int32, S, "n_draft"),
-                         (cur_rows, torch.int64, S * T, "cur_rows"), (pos_rows, torch.int32, S * T, "pos_rows")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, n, f"{who}.{nm}")
+    _require(who, (history, torch.int64, S, "history"), (hist_len, torch.int32, S, "hist_len"), (cur, torch.int64, S, "cur"),
+             (pos, torch.int32, S, "pos"), (finished, torch.int32, S, "finished"), (n_draft, torch.int32, S, "n_draft"),
+             (cur_rows, torch.int64, S * T, "cur_rows"), (pos_rows, torch.int32, S * T, "pos_rows"))
     check(lib().tcavt_ngram_draft(ptr(history), history.shape[1], ptr(hist_len), ptr(cur), ptr(pos), ptr(finished), S, int(k),
                                   int(max_matching_ngram_size), int(pad_token_id), ptr(n_draft), ptr(cur_rows), ptr(pos_rows),
                                   stream_ptr()), "tcavt_ngram_draft")
@@ -1746,26 +1753,16 @@ def spec_verify_args(logits, T, n_draft, cur_rows, scratch, drafted, accepted, h
     arguments of sample_tokens in its slots form), each tensor checked first.  scratch: int32 [S * T + S].  The struct names fixed
     device arrays: one serves every step of a call, captured or not."""
     who = "spec_verify"
-    R, V = logits.shape
+    R, _ = logits.shape
     T = int(T)
     if history.dim() != 2 or out_tokens.dim() != 2 or T < 1 or R % T != 0 or history.shape[0] != R // T:
         raise capi.TcavtError(f"{who}: logits [S * T, V], history one row per sequence, out_tokens one row per request")
     S = R // T
     _sampler_guard(who, logits, workspace, S, S, 1, history, hist_len, step, cur_tok, pos, finished, out_tokens, slots=(max_new, out_row))
-    for t, dt, n, nm in ((n_draft, torch.int32, S, "n_draft"), (cur_rows, torch.int64, R, "cur_rows"), (scratch, torch.int32, R + S, "scratch"),
-                         (drafted, torch.int32, S, "drafted"), (accepted, torch.int32, S, "accepted")):
-        if t is None:
-            raise capi.TcavtError(f"{who}: {nm} is missing")
-        _req(t, dt, f"{who}.{nm}")
-        _need(t, n, f"{who}.{nm}")
-    sa = capi.SampleArgs()
-    sa.logits, sa.history, sa.hist_len = logits.data_ptr(), history.data_ptr(), hist_len.data_ptr()
-    sa.params, sa.step, sa.max_new, sa.out_row = ctypes.pointer(params), step.data_ptr(), max_new.data_ptr(), out_row.data_ptr()
-    sa.cur_tok, sa.pos, sa.finished, sa.out_tokens = cur_tok.data_ptr(), pos.data_ptr(), finished.data_ptr(), out_tokens.data_ptr()
-    sa.workspace, sa.workspace_bytes = ptr(workspace), workspace.numel() if workspace is not None else 0
-    if stop is not None:
-        sa.stop = ctypes.pointer(stop) if isinstance(stop, capi.StopRules) else stop.pointer()
-    sa.rows, sa.V, sa.n_state, sa.hist_cap, sa.out_cap, sa.advance_pos = R, V, S, history.shape[1], out_tokens.shape[1], int(advance_pos)
+    _require(who, (n_draft, torch.int32, S, "n_draft"), (cur_rows, torch.int64, R, "cur_rows"), (scratch, torch.int32, R + S, "scratch"),
+             (drafted, torch.int32, S, "drafted"), (accepted, torch.int32, S, "accepted"))
+    sa = _sample_args(logits, R, S, history, hist_len, params, step, max_new, out_row, cur_tok, pos, finished, out_tokens, advance_pos,
+                      workspace, stop)
     a = capi.SpecVerifyArgs()
     a.sample = ctypes.pointer(sa)
     a.n_draft, a.cur_rows, a.slot_of_row = n_draft.data_ptr(), cur_rows.data_ptr(), scratch.data_ptr()
