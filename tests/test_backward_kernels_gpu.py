@@ -888,7 +888,6 @@ def test_ltsf_backward_at_train_batch(gpu, B):
         ops.mse_grad(dec, t["target_traj"].to(dev), t["norm_stat"].to(dev), g_out, B, cfg.out_len)
         for _ in range(2):
             tr.book.grads.zero_()
-            tr.bw._poly_emb, tr.bw._fh_b, tr.bw._L = poly.to(dev), fh_b, L
             g_poly = tr.bw.ltsf(g_out, x)
             torch.cuda.synchronize()
             runs.append(({k: tr.book.g[k].cpu().clone() for k in names}, g_poly.cpu().clone()))

@@ -142,7 +142,6 @@ def test_ltsf_backward_from_fixed_hidden_states(gpu):
         ops.cast16(fh.to(dev).view(B * L, H), out=fh_b)
         dec = m.ltsf(x, poly.to(dev), fh.to(dev), final_hidden_bf16=fh_b, _fuse_last_residual=True)
         tr.book.grads.zero_()
-        tr.bw._poly_emb, tr.bw._fh_b, tr.bw._L = poly.to(dev), fh_b, L
         g_out = torch.empty_like(dec)
         ops.mse_grad(dec, t["target_traj"].to(dev), t["norm_stat"].to(dev), g_out, B, cfg.out_len)
         g_poly = tr.bw.ltsf(g_out, x)
@@ -287,7 +286,6 @@ def test_ltsf_backward_with_dropout(gpu):
         dec = m.ltsf(x, poly.to(dev), fh.to(dev), final_hidden_bf16=fh_b, _fuse_last_residual=True)
         m.ltsf.dctx = m.ltsf.attn_block.dctx = None
         tr.book.grads.zero_()
-        tr.bw._poly_emb, tr.bw._fh_b, tr.bw._L = poly.to(dev), fh_b, L
         g_out = torch.empty_like(dec)
         ops.mse_grad(dec, t["target_traj"].to(dev), t["norm_stat"].to(dev), g_out, B, cfg.out_len)
         g_poly = tr.bw.ltsf(g_out, x)

@@ -3,8 +3,9 @@
 In the reference, ``loss.backward()`` (train.py:1182) walks an autograd graph that only covers the
 lane-polygon encoder and ``TransformerLTSF``: every MLLM parameter has ``requires_grad=False``
 (train.py:1140-1142), so the LLM's final hidden states are a constant.  This module spells that
-graph out stage by stage, in reverse, on the activations the forward retained
-(``save_for_backward`` workspaces of tlayers.py / ltsf.py).  Nothing here calls torch autograd or torch math.
+graph out stage by stage, in reverse, on the activations the forward retained and handed over in its records
+(``save_for_backward``: ``LanePolygonEncoder.saved`` of tlayers.py, ``TransformerLTSF.saved`` of ltsf.py; the workspaces
+are asked for gradient buffers only).  Nothing here calls torch autograd or torch math.
 
 Precision: fp32 wherever the forward is fp32; the cross-attention projections run their backward
 contractions in bf16 MFMA with fp32 accumulation (standard mixed precision), writing fp32 gradients.
@@ -100,6 +101,7 @@ class Backward:
         self._leaf_streams, self._poly_stream, self._leaf_i = None, None, 0
         self.poly_after_chain = False  # training.Trainer: True for the LoRA-trainable variant (see _ltsf_stage)
         self._v_ready = None
+        self.kv_grads = None  # (dL/dk, dL/dv) of the last run() whose forward ran the un-absorbed cross-attention
         self._serial = os.environ.get("TCAVT_BW_SERIAL", "") == "1"
 
     # ---- streams ---------------------------------------------------------------------------
@@ -185,26 +187,20 @@ class Backward:
     # ---- TransformerLTSF ----------------------------------------------------------------------
     def ltsf(self, g_out, x_in, on_poly_grad=None):
         """g_out [B,2,To] = dL/d decoded; returns g_poly_emb [B, D_poly]."""
-        m, G, ws = self.m.ltsf, self.book.g, self.m.ltsf._ws
-        dec, sab = m.decoder, m.attn_block
+        m, G, sv = self.m.ltsf, self.book.g, self._saved()
+        dec = m.decoder
         pl = self.pl
-        B, F, T = x_in.shape
+        B, T, F = sv.B, sv.T, x_in.shape[1]
         C, To = m.d_model, m.out_len
-        dev = g_out.device
         M = B * To
         H = dec.cross_dim
         nh = dec.cross_nhead
         dh = H // nh
-        if self._ltsf_stage_specs() is not None:  # one C call per phase: tcavt_ltsf_backward (csrc/tlayers.hip)
-            return self._ltsf_stage(g_out, x_in, on_poly_grad)
-        fwd = lambda name, shape, dt=torch.float32: ws.get("lt." + name, shape, dt, dev)
-        st = m.storage  # 16-bit type of the forward's activations (fp16 by default); gradient-side tensors are bf16, and
-        # a forward activation that enters a gradient-side contraction is converted while it is transposed (ops.transpose16)
-        # saved forward activations
-        f2 = fwd("f2", (M, C)); f1 = fwd("f1", (M, C)); fn = fwd("fn", (M, C)); fused = fwd("fused", (M, C))
-        cross = fwd("cross", (M, H), st); att = fwd("att", (M, H), st)
-        q = fwd("q", (M, H), st); proj = fwd("proj", (M, H), st)
-        dec_tb = fwd("dectb", (M, C), st)
+        if self._ltsf_stage_specs(sv) is not None:  # one C call per phase: tcavt_ltsf_backward (csrc/tlayers.hip)
+            return self._ltsf_stage(sv, g_out, x_in, on_poly_grad)
+        # the forward's activations are in its 16-bit storage type (fp16 by default); gradient-side tensors are bf16, and a
+        # forward activation that enters a gradient-side contraction is converted while it is transposed (ops.transpose16)
+        f2, f1, fn, fused, cross, att, proj, dec_tb = sv.f2, sv.f1, sv.fn, sv.fused, sv.cross, sv.att, sv.proj, sv.dec_tb
         fl = dec.fusion_layer
 
         # head: out = f2 W_out^T + b (+ last position, no gradient needed)
@@ -234,13 +230,13 @@ class Backward:
         # attention core + in-projection (packed [3H, H] weight / [3H] bias)
         gWin, gbin = G[pl + "decoder.cross_attn.in_proj_weight"], G[pl + "decoder.cross_attn.in_proj_bias"]
         g_proj = self._buf("g_proj", (M, H), torch.bfloat16)
-        if m._absorbed:  # the forward ran the absorbed form: k / v never existed, their weight gradients come from q', ctx
-            g_q = self._xattn_absorbed(g_att, q, B, To, H, nh, dh, gWin, gbin)
+        if sv.absorbed:  # the forward ran the absorbed form: k / v never existed, their weight gradients come from q', ctx
+            g_q = self._xattn_absorbed(sv, g_att, To, H, nh, dh, gWin, gbin)
             self.lin_bwd_bf16("q", proj, ca.in_proj_weight[:H], g_q, gWin[:H], gbin[:H], gx=g_proj)
         else:
-            g_q, g_k, g_v, L = self._xattn_core(g_att, B, To, H, nh, dh)
+            g_q, g_k, g_v = self._xattn_core(sv, g_att, To, H, nh, dh)
             self.lin_bwd_bf16("q", proj, ca.in_proj_weight[:H], g_q, gWin[:H], gbin[:H], gx=g_proj)
-            fh_b = self._fh_b
+            fh_b, L = sv.final_hidden_bf16, sv.L
             fhT = self.lin_bwd_bf16("k", fh_b[: B * L], ca.in_proj_weight[H:2 * H], g_k[: B * L], gWin[H:2 * H],
                                     gbin[H:2 * H], pin=0)
             self.lin_bwd_bf16("v", fh_b[: B * L], ca.in_proj_weight[2 * H:], g_v[: B * L], gWin[2 * H:], gbin[2 * H:],
@@ -256,13 +252,12 @@ class Backward:
         g_d1 = self._buf("g_d1", (B, C * To))
         ops.transpose_ct(g_dt2, g_d1, None, B, To, C)
         # post MLP: d1 = relu(d0 W0^T + b0) W3^T + b3
-        d0 = fwd("dec0", (B, C * To))
+        d0, hid = sv.d0, sv.hid
         if dec.use_post_mlp:
-            hid = fwd("hid", (B, dec.post_mlp[0].weight.shape[0]))
             g_hid = self._buf("g_hid", tuple(hid.shape))
             self.lin_bwd_f32(hid, dec.post_mlp[3].weight, g_d1, G[pl + "decoder.post_mlp.3.weight"],
                              G[pl + "decoder.post_mlp.3.bias"], gx=g_hid)
-            ops.dropout_(g_hid, getattr(m, "drop_post", None))  # hid = drop(relu(.)): mask, then the ReLU gate
+            ops.dropout_(g_hid, sv.drop_post)  # hid = drop(relu(.)): mask, then the ReLU gate
             ops.relu_bwd(g_hid, hid)
             g_d0 = self._buf("g_d0", (B, C * To))
             self.lin_bwd_f32(d0, dec.post_mlp[0].weight, g_hid, G[pl + "decoder.post_mlp.0.weight"],
@@ -270,27 +265,25 @@ class Backward:
         else:
             g_d0 = g_d1
         # d0 = NLinear_dec(e) + lane_fc(poly_emb)
-        poly_emb = self._poly_emb
+        poly_emb = sv.poly_emb
         g_poly = self._buf("g_poly", tuple(poly_emb.shape))
         self.lin_bwd_f32(poly_emb, dec.lane_fc.weight, g_d0, G[pl + "decoder.lane_fc.weight"],
                          G[pl + "decoder.lane_fc.bias"], gx=g_poly)
         if on_poly_grad is not None:
             on_poly_grad(g_poly)  # the lane-polygon encoder's backward can start here, beside the rest of this one
-        e = sab._ws.get("sab.out", (B * T, C), torch.float32, dev)
         P = m._prepared()
         g_dw = self._buf("g_dw", (C, To, T))
         g_db = self._buf("g_db", (C, To))
         g_e = self._buf("g_e", (B * T, C))
-        ops.nlinear_bwd(e, P.dec_w, g_d0, (C * To, To, 1), g_dw, g_db, g_e, B, C, T, To)
+        ops.nlinear_bwd(sv.e, P.dec_w, g_d0, (C * To, To, 1), g_dw, g_db, g_e, B, C, T, To)
         self._scatter_channels(g_dw, g_db, pl + "decoder.decoder_linears.", C)
         # SelfAttentionBlock
-        g_tok = self._sab(g_e, B, T, C)
+        g_tok = self._sab(sv, g_e)
         # front: tok = NLinear_enc(conv(x)) + pos
-        xp = ws.get("lt.xp", (B * T, C), torch.float32, dev)
         g_ew = self._buf("g_ew", (C, T, T))
         g_eb = self._buf("g_eb", (C, T))
         g_xp = self._buf("g_xp", (B * T, C))
-        ops.nlinear_bwd(xp, P.enc_w, g_tok, (T * C, 1, C), g_ew, g_eb, g_xp, B, C, T, T)
+        ops.nlinear_bwd(sv.xp, P.enc_w, g_tok, (T * C, 1, C), g_ew, g_eb, g_xp, B, C, T, T)
         self._scatter_channels(g_ew, g_eb, pl + "nlinear_encoder.encoder_linears.", C)
         gpos = G[pl + "pos_encoding"]  # (1, C, seq_len): same reduction as the encoder bias
         with self._leaf():
@@ -298,19 +291,24 @@ class Backward:
         ops.conv1x1_bwd(g_xp, x_in, G[pl + "token_proj.weight"].view(C, F), G[pl + "token_proj.bias"], B, C, T, F)
         return g_poly
 
-    def _ltsf_stage_specs(self):
+    def _saved(self):
+        """The record of the last TransformerLTSF forward (ltsf.saved); a backward without one reads nothing."""
+        sv = self.m.ltsf.saved
+        if sv is None:
+            raise RuntimeError("Backward: TransformerLTSF has no saved forward (set ltsf.save_for_backward before the forward)")
+        return sv
+
+    def _ltsf_stage_specs(self, sv):
         """(p, seed, first_site) of the forward's dropout sites when tcavt_ltsf_backward covers this backward: the default
         form (fp16 storage, absorbed cross-attention, C++ stage forward) with the sites numbered as the stage numbers them
         (self-attention block first_site .. + 3, post-MLP + 4); None -> the Python composition below."""
-        m = self.m.ltsf
-        if not (m._absorbed and m._stage_ok(self.book.grads.device) and m.xattn_stage is not None):  # (both forward phases ran as stages)
+        # (both forward phases ran as stages, and the switches still say so)
+        if sv.stage is None or sv.xattn_stage is None or not self.m.ltsf._stage_ok(self.book.grads.device):
             return None
-        sp = getattr(m.attn_block, "drop_specs", None) or [None] * 4
-        post = getattr(m, "drop_post", None) if m.decoder.use_post_mlp else None
-        xs = getattr(m, "drop_xattn", None)
+        sp, post, xs = sv.sab_drop, sv.drop_post, sv.drop_xattn
         if all(s is None for s in sp) and post is None and xs is None:
             return (0.0, 0, 0)
-        if any(s is None for s in sp) or xs is None or (m.decoder.use_post_mlp and post is None):
+        if any(s is None for s in sp) or xs is None or (self.m.ltsf.decoder.use_post_mlp and post is None):
             return None
         p, seed, s0 = sp[0]
         sites = [s[2] for s in sp] + ([post[2]] if post is not None else [])
@@ -319,25 +317,24 @@ class Backward:
             return None
         return (p, seed, s0)
 
-    def _ltsf_stage(self, g_out, x_in, on_poly_grad):
+    def _ltsf_stage(self, sv, g_out, x_in, on_poly_grad):
         """Backward.ltsf as tcavt_ltsf_backward: phase 1 (head .. g_poly), the lane-polygon hand-off, phase 2 (the rest);
         the same kernels on the same buffers as the composition in ltsf()/_sab()/_xattn_absorbed(), on one stream.  The
-        forward's arguments are the struct its own two stage calls filled (TransformerLTSF.stage), not a second one."""
+        forward's arguments are the struct its own two stage calls filled (the record's sv.stage), not a second one."""
         m, G = self.m.ltsf, self.book.g
         dec, pl = m.decoder, self.pl
-        B, F, T = x_in.shape
+        B, T, F = sv.B, sv.T, x_in.shape[1]
         C, To = m.d_model, m.out_len
         Mo, Mt, H, nh = B * To, B * T, dec.cross_dim, dec.cross_nhead
-        dh, L = H // nh, self._L
-        Lp, Mp = _rup(L, XATTN_PAD), _rup(Mo, 64)
+        dh, Lp, Mp = H // nh, sv.Lp, _rup(Mo, 64)
         bf = torch.bfloat16
-        p, seed, s0 = self._ltsf_stage_specs()
+        p, seed, s0 = self._ltsf_stage_specs(sv)
         ca = dec.cross_attn
         post = dec.post_mlp[0].weight.shape[0] if dec.use_post_mlp else 0
         keep = []
         put = lambda obj, **kw: capi.bind(obj, keep, **kw)
-        f = m.stage[0]
-        xsp = getattr(m, "drop_xattn", None)
+        f = sv.stage[0]
+        xsp = sv.drop_xattn
         # under the gate of _ltsf_stage_specs the forward numbered its sites as the stage does: its struct carries the triples
         assert _carries(f, (p, seed, s0), "first_site") and _carries(f.xattn, xsp), "the forward's struct holds other dropout sites"
         # ---- gradients, workspaces
@@ -352,7 +349,7 @@ class Backward:
             d_s=b("xa.dS", (B * nh * To, Lp), bf), g_qp=b("xa.g_qp", (nh, Mo, H), bf),
             p_undropped=b("xa.Pu", (B * nh * To, Lp), torch.float16) if xsp is not None else None)
         g = lambda n: G[pl + n]
-        g_poly = b("g_poly", tuple(self._poly_emb.shape))
+        g_poly = b("g_poly", tuple(sv.poly_emb.shape))
         put(a, g_out=g_out, w_un=dec.dec_unproj.weight, w_co=ca.out_proj.weight, w_dp=dec.dec_proj.weight,
             g_out_w=g("decoder.out_proj.weight"), g_out_b=g("decoder.out_proj.bias"),
             g_fl3_w=g("decoder.fusion_layer.3.weight"), g_fl3_b=g("decoder.fusion_layer.3.bias"),
@@ -431,17 +428,15 @@ class Backward:
             bv = torch.as_strided(flat, (C, S), (stride, 1), ob)
             bv.copy_(gb.view(C, S))
 
-    def _sab(self, g_e, B, T, C):
+    def _sab(self, sv, g_e):
         m, G = self.m.ltsf.attn_block, self.book.g
         pl = self.pl + "attn_block."
-        ws, dev = m._ws, g_e.device
+        B, T, C = sv.B, sv.T, m.embed_dim
         Mt = B * T
-        f = lambda n, shape: ws.get("sab." + n, shape, torch.float32, dev)
-        tok = self.m.ltsf._ws.get("lt.tok", (Mt, C), torch.float32, dev)
-        xn, qkv, att, res1, rn, ff = f("xn", (Mt, C)), f("qkv", (Mt, 3 * C)), f("att", (Mt, C)), f("res1", (Mt, C)), \
-            f("rn", (Mt, C)), f("f", (Mt, 4 * C))
+        s, tok = sv.sab, sv.tok
+        xn, qkv, att, res1, rn, ff = s.xn, s.qkv, s.att, s.res1, s.rn, s.f
         # e = ff W3^T + b3 + rn ; ff = relu(rn W0^T + b0)
-        sp = getattr(m, "drop_specs", None) or [None] * 4  # [attention weights, after out_proj, after ReLU, after ffn.3]
+        sp = sv.sab_drop  # [attention weights, after out_proj, after ReLU, after ffn.3]
         g_ff = self._buf("sab.g_ff", (Mt, 4 * C))
         self.lin_bwd_f32(ff, m.ffn[3].weight, self._dropped(g_e, sp[3], "sab.g_e_d"), G[pl + "ffn.3.weight"],
                          G[pl + "ffn.3.bias"], gx=g_ff)
@@ -469,18 +464,12 @@ class Backward:
         ops.layernorm_bwd(tok, m.norm1.weight, g_xn, g_tok, G[pl + "norm1.weight"], G[pl + "norm1.bias"])
         return g_tok
 
-    def _xattn_core(self, g_att, B, To, H, nh, dh):
+    def _xattn_core(self, sv, g_att, To, H, nh, dh):
         """Backward of softmax(q k^T / sqrt(dh)) v per (sample, head) on batched MFMA GEMMs."""
-        ws, dev = self.m.ltsf._ws, g_att.device
-        fh_b = self._fh_b
-        L = self._L
-        Lp = _rup(L, XATTN_PAD)
+        B, L, Lp = sv.B, sv.L, sv.Lp
         Tp = _rup(To, 64)
         M = B * To
-        P = self.m.ltsf._prepared()
-        q = ws.get("lt.q", (M, H), self.m.ltsf.storage, dev)
-        kx = ws.get("lt.k", (B * L + XATTN_PAD, H), self.m.ltsf.storage, dev)
-        Pm = ws.get("lt.P", (B * nh * To, Lp), torch.float16, dev)
+        kx, Pm = sv.k, sv.P
         scale = 1.0 / math.sqrt(dh)
         # v (non-transposed, bf16) is recomputed: the forward only kept v^T in fp16.  It depends on no gradient, so
         # run() already started it on a side stream; here the chain only waits for it.
@@ -489,18 +478,18 @@ class Backward:
             self._v_ready = None
             v = self._buf("xa.v", (B * L + XATTN_PAD, H), torch.bfloat16)
         else:
-            v = self._recompute_v(B, L, H)
+            v = self._recompute_v(sv)
         # dP = dO V^T   [B*nh*To, Lp] fp32 (columns >= L are never read)
         dP = self._buf("xa.dP", (B * nh * To, Lp))
         ops.gemm_batched(g_att, v, dP, M=To, N=Lp, K=dh, lda=H, ldw=H, ldc=Lp, batch=B * nh, inner=nh,
                          sA=(To * H, dh), sW=(L * H, dh), sC=(nh * To * Lp, To * Lp))
         # attention-weight dropout (train mode): the forward kept only the dropped probabilities; the softmax
         # backward needs the un-dropped ones (recomputed from the retained scores) and the masked dP
-        xsp = getattr(self.m.ltsf, "drop_xattn", None)
+        xsp = sv.drop_xattn
         if xsp is not None:
             ops.dropout_(dP, xsp)
             Pu = self._buf("xa.Pu", (B * nh * To, Lp), torch.float16)
-            ops.softmax_rows(ws.get("lt.S", (B * nh * To, Lp), torch.float32, dev), Pu, B * nh * To, L, Lp, Lp, Lp)
+            ops.softmax_rows(sv.S, Pu, B * nh * To, L, Lp, Lp, Lp)
         else:
             Pu = Pm
         dS = self._buf("xa.dS", (B * nh * To, Lp), torch.bfloat16)
@@ -515,11 +504,11 @@ class Backward:
         # Only the k / v in-projection WEIGHT gradients consume these (the LLM's hidden states are a constant), so
         # the whole branch is leaf work.
         with self._leaf(pin=0):
-            g_k, g_v = self._xattn_kv_grads(g_att, dS, q, B, To, H, nh, dh, L, Lp, Tp)
-        return g_q, g_k, g_v, L
+            g_k, g_v = self._xattn_kv_grads(sv, g_att, dS, To, H, nh, dh, Tp)
+        return g_q, g_k, g_v
 
-    def _xattn_absorbed(self, g_att, q, B, To, H, nh, dh, gWin, gbin):
-        """Backward of the absorbed cross-attention (ltsf.TransformerLTSF.forward), per head h with F = the sample's final
+    def _xattn_absorbed(self, sv, g_att, To, H, nh, dh, gWin, gbin):
+        """Backward of the absorbed cross-attention (ltsf.TransformerLTSF._head), per head h with F = the sample's final
         hidden states (a constant: the MLLM is frozen), q' = q_h W_k[h], S = q' F^T / sqrt(dh), P = dropout(softmax(S)),
         ctx = P F, att_h = ctx W_v[h]^T + b_v:
             gW_v[h] = g_att_h^T ctx      gb_v = colsum(g_att)      g_ctx = g_att_h W_v[h]
@@ -527,22 +516,15 @@ class Backward:
             gW_k[h] = q_h^T g_q'         gb_k = 0 (softmax-invariant)                 g_q_h = g_q' W_k[h]^T
         Every contraction over the B*L hidden-state rows of the un-absorbed form (dW_k, dW_v, the V recompute: three
         chip-filling GEMMs + two transposes of the hidden states) becomes a contraction over the B*To query rows."""
-        m = self.m.ltsf
-        ws, dev = m._ws, g_att.device
-        L = self._L
-        Lp = _rup(L, XATTN_PAD)
+        B, L, Lp, q, ctx, Pm, xsp = sv.B, sv.L, sv.Lp, sv.q, sv.ctx, sv.P, sv.drop_xattn
         M = B * To
         Mp = _rup(M, 64)
-        ca = m.decoder.cross_attn
-        st = m.storage
+        ca = self.m.ltsf.decoder.cross_attn
         bf = torch.bfloat16
         scale = 1.0 / math.sqrt(dh)
-        ctx = ws.get("lt.ctx", (nh, M, H), st, dev)
-        Pm = ws.get("lt.P", (B * nh * To, Lp), torch.float16, dev)
-        if os.environ.get("TCAVT_PY_TLAYERS", "0") != "1" and m.xattn_stage is not None:
+        if os.environ.get("TCAVT_PY_TLAYERS", "0") != "1" and sv.xattn_stage is not None:
             # one C call: tcavt_cross_attn_backward (csrc/tlayers.hip) on the struct the forward's own stage call filled
-            f = m.xattn_stage[0]
-            xsp = getattr(m, "drop_xattn", None)
+            f = sv.xattn_stage[0]
             assert _carries(f, xsp), "the forward's struct holds another dropout site"
             a = capi.CrossAttnBwdArgs()
             a.fwd = ctypes.pointer(f)
@@ -563,7 +545,7 @@ class Backward:
         # bf16 copies of the hidden states for the gradient-side contractions: per-sample transposed [H][B*Lp] (converted
         # while transposing, keys padded to Lp with zeros) and, transposed back, row-major [B*Lp][H]
         fhTb = self._buf("xa.fhTb", (H, B * Lp), bf)
-        ops.transpose16(self._fh_b, fhTb, L, H, Lp, ld_in=H, ld_out=B * Lp, batch=B, s_in=L * H, s_out=Lp)
+        ops.transpose16(sv.final_hidden_bf16, fhTb, L, H, Lp, ld_in=H, ld_out=B * Lp, batch=B, s_in=L * H, s_out=Lp)
         fhb = self._buf("xa.fhb", (B * Lp, H), bf)
         ops.transpose16(fhTb, fhb, H, B * Lp, H)
         # ---- value side
@@ -585,11 +567,10 @@ class Backward:
         dP = self._buf("xa.dP", (B * nh * To, Lp))
         ops.gemm_batched(g_ctx, fhb, dP, M=To, N=Lp, K=H, lda=H, ldw=H, ldc=Lp, batch=B * nh, inner=nh,
                          sA=(To * H, M * H), sW=(Lp * H, 0), sC=(nh * To * Lp, To * Lp), tile=64)
-        xsp = getattr(m, "drop_xattn", None)
         if xsp is not None:  # the softmax backward needs the un-dropped probabilities and the masked dP
             ops.dropout_(dP, xsp)
             Pu = self._buf("xa.Pu", (B * nh * To, Lp), torch.float16)
-            ops.softmax_rows(ws.get("lt.S", (B * nh * To, Lp), torch.float32, dev), Pu, B * nh * To, L, Lp, Lp, Lp)
+            ops.softmax_rows(sv.S, Pu, B * nh * To, L, Lp, Lp, Lp)
         else:
             Pu = Pm
         dS = self._buf("xa.dS", (B * nh * To, Lp), bf)
@@ -612,19 +593,20 @@ class Backward:
                 ops.gemm_bf16(qT, gqpT, out=gWin[H + h * dh: H + (h + 1) * dh])
         return g_q
 
-    def _recompute_v(self, B, L, H):
-        P = self.m.ltsf._prepared()
-        v = self._buf("xa.v", (B * L + XATTN_PAD, H), torch.bfloat16, zero=True)
-        ops.gemm_bf16(self._fh_b[: B * L], P.w_v, out=v, bias=P.b_v)
+    def _recompute_v(self, sv):
+        P, fh_b, n = self.m.ltsf._prepared(), sv.final_hidden_bf16, sv.B * sv.L
+        v = self._buf("xa.v", (n + XATTN_PAD, fh_b.shape[1]), torch.bfloat16, zero=True)
+        ops.gemm_bf16(fh_b[:n], P.w_v, out=v, bias=P.b_v)
         return v
 
-    def _xattn_kv_grads(self, g_att, dS, q, B, To, H, nh, dh, L, Lp, Tp):
-        ws, dev = self.m.ltsf._ws, g_att.device
+    def _xattn_kv_grads(self, sv, g_att, dS, To, H, nh, dh, Tp):
+        """dL/dk, dL/dv of the un-absorbed cross-attention -> (g_k, g_v), also left in self.kv_grads: the decoder's backward
+        starts from them (training.lora_backward)."""
+        B, L, Lp, q = sv.B, sv.L, sv.Lp, sv.q
         dST = self._buf("xa.dST", (B * nh * Lp, Tp), torch.bfloat16)
         ops.transpose16(dS, dST, To, Lp, Tp, ld_in=Lp, ld_out=Tp, batch=B * nh, s_in=To * Lp, s_out=Lp * Tp)
         Pb = self._buf("xa.Pb", (B * nh * To, Lp), torch.bfloat16)
-        ops.softmax_rows(ws.get("lt.S", (B * nh * To, Lp), torch.float32, dev), Pb, B * nh * To, L, Lp, Lp, Lp,
-                         dropout=getattr(self.m.ltsf, "drop_xattn", None))  # dV uses the probabilities the forward used
+        ops.softmax_rows(sv.S, Pb, B * nh * To, L, Lp, Lp, Lp, dropout=sv.drop_xattn)  # dV uses the probabilities the forward used
         PT = self._buf("xa.PT", (B * nh * Lp, Tp), torch.bfloat16)
         ops.transpose16(Pb, PT, To, Lp, Tp, ld_in=Lp, ld_out=Tp, batch=B * nh, s_in=To * Lp, s_out=Lp * Tp)
         qT = self._buf("xa.qT", (H, B * Tp), torch.bfloat16)
@@ -637,6 +619,7 @@ class Backward:
                          sA=(nh * Lp * Tp, Lp * Tp), sW=(Tp, dh * B * Tp), sC=(L * H, dh))
         ops.gemm_batched(PT, gaT, g_v, M=L, N=dh, K=Tp, lda=Tp, ldw=B * Tp, ldc=H, batch=B * nh, inner=nh,
                          sA=(nh * Lp * Tp, Lp * Tp), sW=(Tp, dh * B * Tp), sC=(L * H, dh))
+        self.kv_grads = (g_k, g_v)
         return g_k, g_v
 
     # ---- LanePolygonEncoder -------------------------------------------------------------------
@@ -736,13 +719,14 @@ class Backward:
         return True
 
     # ---- entry ------------------------------------------------------------------------------
-    def run(self, decoded, y, norm_stat, x_in, poly_emb, fh_b, L, after_ltsf=None, seed=None):
-        """Fills book.grads (must be zeroed by the caller) from the retained forward activations.
+    def run(self, decoded, y, norm_stat, x_in, after_ltsf=None, seed=None):
+        """Fills book.grads (must be zeroed by the caller) from the forward's records (ltsf.saved, lane_polygon_encoder.saved).
         `after_ltsf` (callable) is invoked once the LTSF gradients are complete (bucket hand-off).
         `seed` = (g_loss, g_pred): autograd's gradients of the loss (device fp32 [1]) and of `decoded`, either may be None
         (ops.mse_grad_seeded); None: d loss = 1 and nothing else reads `decoded` (ops.mse_grad)."""
         B, F, To = decoded.shape
-        self._poly_emb, self._fh_b, self._L = poly_emb, fh_b, L
+        self.kv_grads = None
+        sv = self._saved()
         self._ensure_streams()
         g_out = self._buf("g_out", (B, F, To))
         if seed is None:
@@ -758,9 +742,9 @@ class Backward:
         main = torch.cuda.current_stream()
         # the cross-attention backward needs V row-major (the forward kept only V^T): a chip-filling GEMM that depends on
         # no gradient -> started now on a side stream, off the gradient chain
-        if not self.m.ltsf._absorbed:
+        if not sv.absorbed:
             with _Fork(self._leaf_streams[0]):
-                self._recompute_v(B, L, fh_b.shape[1])
+                self._recompute_v(sv)
                 self._v_ready = torch.cuda.Event()
                 self._v_ready.record()
 

@@ -66,7 +66,7 @@ def run_backward(model, bw, lbw, qbw, decoded, y, ns, x, B, L, exchange=None, bo
     (end of the LTSF, end of the train.py set, end of the book): the gradient hand-off of each bucket as it completes.
     seed = (g_loss, g_pred) (autograd): Backward.run's seeded loss gradient; None = d loss = 1."""
     after_ltsf = (lambda: exchange(0, bounds[0])) if exchange is not None else None
-    bw.run(decoded, y, ns, x, model.last.poly_emb, model.last.final_hidden_bf16, L, after_ltsf=after_ltsf, seed=seed)
+    bw.run(decoded, y, ns, x, after_ltsf=after_ltsf, seed=seed)
     if lbw is not None:
         lora_backward(model, bw, lbw, qbw, B, L)  # (the caller's chain continues; the lane-polygon encoder's backward runs beside it)
         bw.join()
@@ -79,12 +79,13 @@ def run_backward(model, bw, lbw, qbw, decoded, y, ns, x, B, L, exchange=None, bo
 
 def lora_backward(model, bw, lbw, qbw, B, L):
     """Gradient of the decoder's final hidden states = what flows back through the cross-attention's key and value
-    in-projections (k = fh W_k^T + b_k, v = fh W_v^T + b_v; the LTSF backward left dL/dk, dL/dv behind), then the
+    in-projections (k = fh W_k^T + b_k, v = fh W_v^T + b_v; the LTSF backward left dL/dk, dL/dv in bw.kv_grads), then the
     walk through the frozen layers."""
+    if bw.kv_grads is None:
+        raise RuntimeError("lora_backward: no dL/dk, dL/dv (Backward.run of an un-absorbed forward, ltsf.absorb_kv = False, first)")
     H = model.llama_hidden_size
     ca = model.ltsf.decoder.cross_attn
-    g_k = bw._buf("xa.g_k", (B * L + 64, H), torch.bfloat16)
-    g_v = bw._buf("xa.g_v", (B * L + 64, H), torch.bfloat16)
+    g_k, g_v = bw.kv_grads
     gfa = bw._buf("lora.gfa", (B * L, H), torch.bfloat16)
     gfb = bw._buf("lora.gfb", (B * L, H), torch.bfloat16)
     for W, g, out, tag in ((ca.in_proj_weight[H:2 * H], g_k, gfa, "k"), (ca.in_proj_weight[2 * H:], g_v, gfb, "v")):
